@@ -14,7 +14,13 @@ flight the captured forwards are branch-free -- see `--branch-streams`), `--stre
 data-path collective (weak scaling); the only RCCL traffic is the barrier / max-time reduction
 around the timed region.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run sets up, warms up, times exactly --steps steps once, writes the last step's outputs if --dump-outputs DIR is
+given (DIR/<name>.npy, float32 / float64, at most 64 MB in all) and prints the line: metric, value, unit, ms_per_step,
+higher_is_better, dtype, the configuration.  Everything else moves behind --full: the timed region repeated until
+--min-seconds have been measured (value from the median region), the roofline objects with the serial eager steps and the
+one / two in flight replays they need, and the CPU baseline.
+
+Extra objects in the line (--full):
   roofline      the dominant kernel class (the operand-split GEMMs on the fp16 matrix cores that hold the
                 per-point MLPs, 95 % of the FLOPs: hs_proj_kernel / gemm_pp_kernel and the fused heads /
                 conv_5 / decoder kernels), timed with HIP events on the launch stream around every one of
@@ -29,7 +35,7 @@ Extra objects in the line:
 tgpose_amd.trainer.RL_TDA: net1 with autograd, net2 under no_grad on the augmented cloud, the three consistency
 terms, the fourteen-term TDA loss, total, backward, gradient all-reduce, clip, SGD), forward + loss + backward
 replayed as one hipGraph.
-The timed region is exactly --steps steps between fences; it is repeated until --min-seconds have been
+The timed region is exactly --steps steps between fences; with --full it is repeated until --min-seconds have been
 measured and `value` is taken from the median region (`timed_regions` carries min / median / max).
 `--workload input_side` times the evaluation loader's input side: `--frames` synthetic depth frames with 6
 detections each, resident in HBM, -> (1024,3) clouds (tgp_roi_cloud + tgp_cloud_sample); detections/s, with an HBM roofline
@@ -59,6 +65,37 @@ def synth_batch(B, N, seed):
     off = torch.rand(B, 1, 3, generator=g) * torch.tensor([0.4, 0.4, 1.0]) + torch.tensor([-0.2, -0.2, 0.5])
     obj = torch.randint(0, 6, (B, 1), generator=g).float()
     return (pts + off).contiguous(), obj
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: the arrays a caller of the timed path receives from its last step, as path/<name>.npy -- floating arrays in
+    float32 (float64 stays float64), integer and boolean ones in float64 (exact for int32).  Above 64 MB in all, every array is cut
+    to the same fraction of its elements by a fixed, seeded choice of flat indices (ascending; the same for the same shapes), and
+    <name>.npy holds that flat sample."""
+    import numpy as np
+    if torch.is_tensor(out):
+        named = [("out", out)]
+    elif isinstance(out, dict):
+        named = list(out.items())
+    else:
+        named = [("out_%d" % i, t) for i, t in enumerate(out)]
+    arrays = {}
+    for name, t in named:
+        if not torch.is_tensor(t):
+            continue
+        t = t.detach()
+        dt = torch.float64 if (t.dtype == torch.float64 or not t.dtype.is_floating_point) else torch.float32
+        arrays[str(name)] = t.to(dt).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(a.size * (DUMP_LIMIT_BYTES - (1 << 20)) / total))      # (1 MB left for the .npy headers)
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(sd):
@@ -134,31 +171,34 @@ def bench_input_side(args, dev, rank, world, dist, share):
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(True)
+        out = step(args.full)
     fence()
     elapsed = time.perf_counter() - t0
     if dist is not None:
         t = torch.tensor([elapsed], device="cpu" if share else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
     if rank == 0:
-        k_roi = sum(a.elapsed_time(b) for a, b, _ in ev) * 1e-3 / len(ev)
-        k_smp = sum(b.elapsed_time(c) for _, b, c in ev) * 1e-3 / len(ev)
-        alg = D * (65536 * 3 + 1024 * 12)
         line = {"metric": "detections/sec depth frame -> cloud (256x256 ROI, 1024 pts)", "value": round(world * D * args.steps / elapsed, 1),
                 "unit": "detections/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                 "dtype": "u16/u8 in, f32 out", "data": "synthetic",
                 "config": {"workload": "evaluation loader input side (load_data_eval.py:302-357): %d frames x %d detections per step, "
                                        "frames resident in HBM, device-drawn resampling" % (args.frames, per_frame),
-                           "frames": args.frames, "detections": D, "replicas": world},
-                "roofline": {"bound": "hbm", "achieved": round(alg / k_roi / 1e9, 1), "peak": 8000.0, "unit": "GB/s",
+                           "frames": args.frames, "detections": D, "replicas": world}}
+    if rank == 0 and args.full:
+        k_roi = sum(a.elapsed_time(b) for a, b, _ in ev) * 1e-3 / len(ev)
+        k_smp = sum(b.elapsed_time(c) for _, b, c in ev) * 1e-3 / len(ev)
+        alg = D * (65536 * 3 + 1024 * 12)
+        line["roofline"] = {"bound": "hbm", "achieved": round(alg / k_roi / 1e9, 1), "peak": 8000.0, "unit": "GB/s",
                              "frac": round(alg / k_roi / 8e12, 4), "traffic": _input_side_traffic(D), "kernel": "roi_cloud_kernel",
                              "avg_launch_us": round(1e6 * k_roi, 1), "sample_launch_us": round(1e6 * k_smp, 1),
                              "algorithmic_bytes_per_launch": alg,
                              "note": "one workgroup per detection (%d workgroups on 256 CUs), each a chain of 16 + ~8 dependent "
                                      "ordered-compaction rounds: latency- and issue-bound (SQ counters under profiles/), far from the "
-                                     "HBM roof by construction; 65536 pixels x ~40 VALU instructions per detection on one CU" % D}}
+                                     "HBM roof by construction; 65536 pixels x ~40 VALU instructions per detection on one CU" % D}
         if world == 1 and not args.no_cpu_baseline:
             from oracle import input_ref as ir
             t1 = time.perf_counter()
@@ -171,6 +211,7 @@ def bench_input_side(args, dev, rank, world, dist, share):
             line["cpu_baseline"] = {"value": round(n / dt, 1), "unit": "detections/s", "cores": 1, "kind": "port",
                                     "sample": "%d detections of 4 frames through oracle/input_ref.py (numpy, one thread; the reference's "
                                               "loader runs the same passes per DataLoader worker), %.2f s" % (n, dt)}
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()
@@ -346,10 +387,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=B_PER_GPU, help="objects per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: repeated timed regions (--min-seconds), the roofline "
+                         "objects, the one / two in flight figures and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="the timed region (exactly --steps steps between fences) is repeated until this much time has been measured; "
-                         "the line reports the median region and the spread")
+                    help="--full: the timed region (exactly --steps steps between fences) is repeated until this much time has been "
+                         "measured; the line reports the median region and the spread")
     ap.add_argument("--streams", type=int, default=4,
                     help="batches in flight per GPU: step i runs on HIP stream i %% S over its own batch (independent batches "
                          "overlap each other's tail rounds and small kernels); 1 = one forward at a time")
@@ -495,12 +541,14 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
+    last = [None]                  # what the last timed step returned (--dump-outputs)
+
     def timed_region():
         """exactly --steps steps between fences; max over ranks"""
         fence()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            last[0] = step()
         fence()
         el = time.perf_counter() - t0
         if dist is not None:
@@ -511,21 +559,23 @@ def main():
 
     for _ in range(max(args.warmup, len(streams))):
         step()
-    ops.GEMM_TIMER = [] if replayers is None and not getattr(net, "graph_replay", False) and not (trainer and args.graph) else None
+    ops.GEMM_TIMER = [] if args.full and replayers is None and not getattr(net, "graph_replay", False) and not (trainer and args.graph) else None
     regions = [timed_region()]
     timer, ops.GEMM_TIMER = ops.GEMM_TIMER, None
     # the same region again until --min-seconds have been measured (every rank takes the same decision: the times are reduced)
-    while sum(regions) < args.min_seconds and len(regions) < 200:
+    while args.full and sum(regions) < args.min_seconds and len(regions) < 200:
         regions.append(timed_region())
     regions_sorted = sorted(regions)
     elapsed = regions_sorted[len(regions) // 2] if len(regions) % 2 else 0.5 * (regions_sorted[len(regions) // 2 - 1] + regions_sorted[len(regions) // 2])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(last[0], args.dump_outputs)
 
     # ---- roofline block: per-kernel durations need serial launches (graph replays have no launch to bracket, overlapping
     # streams stretch each other's kernels): the same steps once more as serial eager launches on one stream, HIP events
     # around every tile-kernel launch and every launch of the graph / HBM class
     roof_note = "HIP events around every tile-kernel launch of the timed region (eager launches)"
     graph_cls, roof_elapsed, k_roof = None, regions[0], args.steps
-    if timer is None:
+    if args.full and timer is None:
         branch, _engine.BRANCH_STREAMS = _engine.BRANCH_STREAMS, False
         replay_flag = getattr(net, "graph_replay", False)
         net.graph_replay = False
@@ -585,7 +635,7 @@ def main():
                 two_in_flight = world * B * args.steps / (time.perf_counter() - t3)
                 del pair
 
-    if rank == 0:
+    if rank == 0 and args.full:
         tile = [t for t in timer if len(t) > 6 and t[6] == "tile"]
         traffic, traffic_src = _kernel_traffic((len(tile) / max(k_roof, 1), sum(t[5] for t in tile) / max(k_roof, 1)) if tile and args.workload == "forward" else None)
         launches = len(timer)
@@ -609,6 +659,7 @@ def main():
             kernel_name = "gemm_main256_kernel / gemm_main_kernel"
             peak = PEAK_F32_MFMA_TFLOPS
             peak_basis = "fp32 MFMA (v_mfma_f32_32x32x2_f32) dense peak"
+    if rank == 0:
         per_step = [1e3 * r / args.steps for r in regions]
         fwd = args.workload == "forward"
         line = {
@@ -645,20 +696,21 @@ def main():
                        **({} if fwd else {"nan_test_in_step": True}),
                        "hipgraph": {0: "off", 1: "whole batch" if replayers is None else "whole batch, one captured forward per stream",
                                     2: "two half batches on forked streams"}[args.graph]},
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4), "traffic": traffic,
-                         "traffic_source": (traffic_src + " (committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over serial eager "
-                                                          "forwards of this workload, per kernel and launch, bytes = (2 FETCH + WRITE) KB; "
-                                                          "algorithmic bytes where a kernel serves one shape; not measured by this run)")
-                         if traffic_src else None,
-                         "kernel": kernel_name, "peak_basis": peak_basis,
-                         "launches_timed": launches, "avg_launch_us": round(1e6 * ksec / max(launches, 1), 2),
-                         "share_of_step": round(ksec / roof_elapsed, 4), "measured": roof_note},
         }
+        if args.full:
+            line["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
+                                "frac": round(achieved / peak, 4), "traffic": traffic,
+                                "traffic_source": (traffic_src + " (committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over serial eager "
+                                                                 "forwards of this workload, per kernel and launch, bytes = (2 FETCH + WRITE) KB; "
+                                                                 "algorithmic bytes where a kernel serves one shape; not measured by this run)")
+                                if traffic_src else None,
+                                "kernel": kernel_name, "peak_basis": peak_basis,
+                                "launches_timed": launches, "avg_launch_us": round(1e6 * ksec / max(launches, 1), 2),
+                                "share_of_step": round(ksec / roof_elapsed, 4), "measured": roof_note}
         #  the same launches priced one by one at THEIR roof: a launch is bound by
         # max(executed FLOPs / MFMA roof of the GEMM mode, algorithmic bytes / HBM peak) -- the layers' last GEMMs (N = K = 128) and the
         # K = 128 projections are HBM-bound launches that the class-wide "mfma" fraction above prices on the wrong roof
-        priced = [t for t in timer if len(t) > 5 and t[5]]
+        priced = [t for t in timer if len(t) > 5 and t[5]] if args.full else []
         if priced and ksec > 0:
             roof = peak * 1e12
             b_mfma = [t[2] / roof for t in priced]
@@ -672,7 +724,7 @@ def main():
                 "hbm_bound_launches_us_per_forward": round(1e6 * sum(t[0].elapsed_time(t[1]) * 1e-3 for t, a, b in zip(priced, b_mfma, b_hbm) if b > a) / max(k_roof, 1), 1),
                 "basis": "per launch max(executed FLOPs / %.0f TFLOP/s, algorithmic bytes / 8 TB/s), summed, over the summed launch times "
                          "(tile GEMMs: A + W + result(s) + residuals once; fused kernels: their operands once)" % peak}
-        if kflop_ref != kflop and ksec > 0:
+        if args.full and kflop_ref != kflop and ksec > 0:
             # the layers over the concat buffer run factored over the nearest-neighbour upsampling (DESIGN.md "Factored wide
             # layers"): `achieved` counts the FLOPs the kernels execute; for comparison, the same time priced in the FLOPs of
             # the reference's formulation (W x upsampled copies)
@@ -711,7 +763,7 @@ def main():
             line["config"]["objects_per_s_one_batch_in_flight"] = round(one_in_flight, 1)     # this rank's clock, not max-over-ranks
         if two_in_flight is not None:
             line["config"]["objects_per_s_two_batches_in_flight"] = round(two_in_flight, 1)   # (two branched replays: the default of rounds 1-2)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(sd)
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -9,7 +9,7 @@ import sys, os, json
 sys.path.insert(0, %r)
 from tgpose_amd import _lib
 _lib.LIB_PATH = os.path.join(%r, 'tg-pose_amd', sys.argv[1])
-sys.argv = ['bench.py', '--no-cpu-baseline'] + sys.argv[2:]
+sys.argv = ['bench.py', '--full', '--no-cpu-baseline'] + sys.argv[2:]
 import runpy
 runpy.run_path(os.path.join(%r, 'bench.py'), run_name='__main__')
 """ % (ROOT, ROOT, ROOT)

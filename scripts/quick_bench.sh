@@ -6,9 +6,9 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --no-cpu-baseline > $O/bench.jsonl 2> $O/bench.err
-python3 $R/bench.py --no-cpu-baseline --streams 1 > $O/bench_one_in_flight.jsonl 2>> $O/bench.err
-rocprofv3 --kernel-trace --output-format csv -d $O/prof_serial -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --graph 0 --streams 1 --no-branch-streams --min-seconds 0 > $O/bench_serial_eager.jsonl 2>> $O/prof.err
+python3 $R/bench.py --full --no-cpu-baseline > $O/bench.jsonl 2> $O/bench.err
+python3 $R/bench.py --full --no-cpu-baseline --streams 1 > $O/bench_one_in_flight.jsonl 2>> $O/bench.err
+rocprofv3 --kernel-trace --output-format csv -d $O/prof_serial -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --graph 0 --streams 1 --no-branch-streams --min-seconds 0 > $O/bench_serial_eager.jsonl 2>> $O/prof.err
 python3 $R/scripts/forward_launches.py $(find $O/prof_serial -name "*kernel_trace.csv" | head -1) $O/forward_launches.txt
 find $O -name "*kernel_trace.csv" -size +20M -delete
 python3 - <<PY

@@ -4,7 +4,7 @@ import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for branch in (1, 0):
     for streams in (1, 2, 3, 4):
-        args = ["--no-cpu-baseline", "--streams", str(streams), "--min-seconds", "0.5"] + ([] if branch else ["--no-branch-streams"])
+        args = ["--full", "--no-cpu-baseline", "--streams", str(streams), "--min-seconds", "0.5"] + ([] if branch else ["--no-branch-streams"])
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True).stdout.strip().splitlines()
         try:
             d = json.loads(out[-1])

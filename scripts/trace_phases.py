@@ -1,4 +1,4 @@
-"""Split-GEMM launch durations of a rocprofv3 kernel trace of the default `bench.py` command, by phase of the run.
+"""Split-GEMM launch durations of a rocprofv3 kernel trace of a `bench.py --full` run, by phase of the run.
 The default bench keeps two graph replays in flight during the timed region, which stretches every kernel's duration in the
 trace (two kernels share the CUs); the roofline block is measured on the serial eager steps that follow.  This script cuts
 the trace at those boundaries so the summary can be compared with `roofline.avg_launch_us`.
