@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define TGP_ABI_VERSION 7
+#define TGP_ABI_VERSION 8
 #define TGP_EINVAL (-1)       /* null pointer / non-positive size / misaligned stride */
 #define TGP_EUNSUPPORTED (-2) /* shape outside what the kernels are built for */
 
@@ -856,6 +856,45 @@ int tgp_head_post_bwd(const float *green, const float *red, int ldg, int ldr, in
  * (the caller then takes the transposed-copy form: tgp_transpose_scaled + tgp_transpose_split_f16 + tgp_gemm_f32). */
 int tgp_gemm_tn_split(const float *a, int lda, const float *b, int ldb, int rows, int N, int K, const float *scale, int Z, int chunk,
                       float *parts, tgp_stream_t stream);
+
+/* ---- the optimizer step (ABI 8; csrc/ranger.hip) ----------------------------------------------------------------------------------
+ * tools/torch_utils/solver/ranger2020.py:43-246 Ranger.step (RAdam + Lookahead + gradient centralisation) over many tensors in ONE
+ * launch.  One descriptor per tensor that has a gradient; every pointer is a device pointer to numel fp32 elements (any 4-byte
+ * alignment: 16-byte accesses where an array is 16-byte aligned at the same element as exp_avg, 4-byte ones otherwise).  Per element,
+ * in the reference's order and rounding (fmaf exactly where the reference's torch op rounds once):
+ *   flags & TGP_RANGER_GC:  g -= mean of its row (row_len elements: numel / size(0)); written back to g (the reference centralises
+ *                           p.grad in place).  Otherwise g is only read.
+ *   v = v b2 + (omb2 g) g;   m = fmaf(omb1, g, m b1)
+ *   ADAPTIVE:  G = m / (sqrt(v) + eps), then G = fmaf(p, weight_decay, G) when weight_decay != 0
+ *   otherwise: G IS m: m = fmaf(p, weight_decay, m) when weight_decay != 0 (the change persists in exp_avg, as in the reference)
+ *   p = fmaf(G, neg_step_lr, p)                (neg_step_lr = float(-step_size * lr), computed by the caller in doubles)
+ *   LOOKAHEAD: slow = fmaf(p - slow, alpha, slow); p = slow
+ * The adaptive and lookahead decisions and step_size are the caller's (host doubles: N_sma crosses its threshold between steps 5 and
+ * 6, where a device pow could round the other way); they are per tensor, since step counters differ between tensors whose grads
+ * were None on some steps.  A row's mean is summed in an order fixed by numel, row_len and the 16-byte phase of m (never by the
+ * other tensors of the launch): no atomics, bit-repeatable.
+ * tgp_ranger_plan (host only, nothing launched): checks a HOST copy of the table (non-null pointers, numel >= 0, row_len >= 1 and
+ * numel % row_len == 0 where GC is set) and fills every entry's unit0 (the tensor's first work unit); *units = the total.  The caller
+ * then copies that table to the device; tgp_ranger_step launches over it (grid from the device's CU count). */
+#define TGP_RANGER_GC 1
+#define TGP_RANGER_ADAPTIVE 2
+#define TGP_RANGER_LOOKAHEAD 4
+typedef struct tgp_ranger_tensor {
+    float *p; float *g; float *m; float *v; float *slow;   /* param, grad, exp_avg, exp_avg_sq, slow_buffer */
+    int64_t numel;
+    int row_len;        /* GC row length (read when flags & TGP_RANGER_GC) */
+    int flags;          /* TGP_RANGER_GC | TGP_RANGER_ADAPTIVE | TGP_RANGER_LOOKAHEAD */
+    int64_t unit0;      /* filled by tgp_ranger_plan */
+    float beta1, one_minus_beta1, beta2, one_minus_beta2;
+    float eps, weight_decay, neg_step_lr, alpha;
+} tgp_ranger_tensor;    /* 96 bytes */
+typedef struct tgp_ranger_args {
+    const tgp_ranger_tensor *tensors;   /* device table of n descriptors, unit0 as tgp_ranger_plan filled it */
+    int n;
+    int64_t units;                      /* tgp_ranger_plan's total */
+} tgp_ranger_args;
+int tgp_ranger_plan(tgp_ranger_tensor *host_tensors, int n, int64_t *units);
+int tgp_ranger_step(const tgp_ranger_args *args, tgp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,196 @@
+"""CPU tests of the Ranger optimizer's host side and the flat-and-anneal schedule (tgpose_amd.tools): the schedule against the
+reference's lr sequences (tests/golden/ranger.npz, tests/golden/make_ranger_golden.py), the reference's argument errors, the
+param-group / state-dict structure, the FLAGS builders, and the C ABI of tgp_ranger_step (struct layout; refusals without a launch)."""
+import ctypes
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import ranger_cases as C
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def fx():
+    return np.load(os.path.join(ROOT, "tests", "golden", "ranger.npz"))
+
+
+def _ulp_close(a, b, ulps=1):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return np.all(np.abs(a - b) <= ulps * np.spacing(np.maximum(np.abs(a), np.abs(b))))
+
+
+def _lrs(sched_kw, n, base=0.5):
+    from tgpose_amd.tools.torch_utils.solver.lr_scheduler import flat_and_anneal_lr_scheduler
+    opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=base)
+    sch = flat_and_anneal_lr_scheduler(opt, **sched_kw)
+    out = []
+    for _ in range(n):
+        out.append(opt.param_groups[0]["lr"])
+        opt.step()
+        sch.step()
+    return out
+
+
+@pytest.mark.parametrize("warm", ["linear", "constant"])
+@pytest.mark.parametrize("anneal", ["cosine", "linear", "poly", "exp", "step", "none"])
+def test_flat_and_anneal_matches_reference_sequences(fx, warm, anneal):
+    want = fx["table/%s/%s" % (warm, anneal)]
+    got = _lrs(dict(C.SCHED_TABLE, warmup_method=warm, anneal_method=anneal), len(want))
+    assert _ulp_close(got, want), (warm, anneal)
+
+
+def test_flat_and_anneal_run_schedule_matches_reference(fx):
+    got = _lrs(C.SCHED, C.STEPS, base=C.BASE_LR)
+    for config in C.CONFIGS:
+        assert _ulp_close(got, fx["%s/lr" % config]), config
+
+
+def test_argument_errors_match_reference(fx):
+    from tgpose_amd.tools.torch_utils.solver.lr_scheduler import flat_and_anneal_lr_scheduler
+    from tgpose_amd.tools.torch_utils.solver.ranger2020 import Ranger
+    want = json.loads(str(fx["errors"]))
+    p = [torch.nn.Parameter(torch.zeros(2))]
+    for name, kw in {"alpha": dict(alpha=1.5), "k": dict(k=0), "lr": dict(lr=0.0), "eps": dict(eps=0.0)}.items():
+        with pytest.raises(ValueError) as e:
+            Ranger(p, **kw)
+        assert str(e.value) == want["ranger/" + name]
+    opt = torch.optim.SGD(p, lr=1.0)
+    sbad = {"warmup": dict(warmup_method="cubic"), "anneal": dict(anneal_method="sqrt"), "point": dict(anneal_point=1.5),
+            "steps_range": dict(anneal_method="step", warmup_iters=50, steps=(0.2, 0.9)),
+            "steps_order": dict(anneal_method="step", steps=(0.9, 0.5))}
+    for name, kw in sbad.items():
+        with pytest.raises(ValueError) as e:
+            flat_and_anneal_lr_scheduler(opt, 100, **kw)
+        assert str(e.value) == want["sched/" + name]
+    with pytest.raises(NotImplementedError):
+        Ranger(p, gc_loc=False)
+
+
+def test_param_groups_and_state_dict_structure_match_reference(fx):
+    from tgpose_amd.tools.torch_utils.solver.ranger2020 import Ranger
+    ref_groups = json.loads(str(fx["sd/param_groups"]))
+    params = [torch.nn.Parameter(torch.from_numpy(p)) for p in C.init_params()]
+    opt = Ranger(params, lr=C.BASE_LR)
+    sd = opt.state_dict()
+    assert set(sd["param_groups"][0]) | {"initial_lr"} == set(ref_groups[0])
+    for k, v in ref_groups[0].items():
+        if k not in ("lr", "initial_lr", "params"):
+            got = sd["param_groups"][0][k]
+            assert (list(got) if isinstance(got, tuple) else got) == v, k
+    # the reference's per-parameter state keys: a state_dict of that form loads (flattening happens at the next step, on the GPU)
+    state = {i: {"step": int(fx["sd/step/%d" % i]), **{f: torch.from_numpy(fx["sd/%s/%d" % (f, i)]) for f in
+                                                      ("exp_avg", "exp_avg_sq", "slow_buffer")}} for i in range(len(C.SHAPES))}
+    opt.load_state_dict({"state": state, "param_groups": ref_groups})
+    assert opt.state[params[0]]["step"] == C.SD_STEP
+    assert set(opt.state[params[0]]) == {"step", "exp_avg", "exp_avg_sq", "slow_buffer"}
+    assert opt.param_groups[0]["step_counter"] == 0 and opt.param_groups[0]["N_sma_threshhold"] == 5
+
+
+def test_builders_read_flags():
+    from tgpose_amd import FLAGS
+    from tgpose_amd.tools import training_utils as TU
+    from tgpose_amd.tools.torch_utils.solver.ranger2020 import Ranger
+    defaults = dict(weight_decay=0.0, warmup_factor=0.001, warmup_iters=1000, warmup_method="linear", anneal_method="cosine",
+                    anneal_point=0.72, lr_scheduler_name="flat_and_anneal", optimizer_type="Ranger", gamma=0.1, poly_power=0.9,
+                    total_epoch=150, train_steps=2000, accumulate=1)
+    for k, v in defaults.items():
+        assert getattr(FLAGS, k) == v, k
+    saved = {k: getattr(FLAGS, k) for k in ("weight_decay", "warmup_iters", "warmup_factor", "anneal_method", "anneal_point")}
+    try:
+        FLAGS.weight_decay, FLAGS.warmup_iters, FLAGS.warmup_factor = 0.25, 4, 0.5
+        FLAGS.anneal_method, FLAGS.anneal_point = "linear", 0.5
+        p = torch.nn.Parameter(torch.zeros(3))
+        opt = TU.build_optimizer([{"params": [p], "lr": 0.2}])
+        assert isinstance(opt, Ranger) and opt.param_groups[0]["weight_decay"] == 0.25 and opt.param_groups[0]["lr"] == 0.2
+        sch = TU.build_lr_rate(opt, total_iters=10)
+        got = []
+        for _ in range(10):
+            got.append(opt.param_groups[0]["lr"])
+            opt.step()                  # no gradient: nothing to do
+            sch.step()
+        want = [0.2 * f for f in (0.5, 0.625, 0.75, 0.875, 1.0, 1.0, 0.8, 0.6, 0.4, 0.2)]
+        assert np.allclose(got, want, rtol=1e-12, atol=0), got
+    finally:
+        for k, v in saved.items():
+            setattr(FLAGS, k, v)
+
+
+def test_ranger_struct_matches_header_layout():
+    import subprocess
+    import tempfile
+    from tgpose_amd import _lib
+    fields = [n for n, _ in _lib.RangerTensor._fields_]
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "tgpose.h"\nint main(void){' + "".join(
+        'printf("%%zu ", offsetof(tgp_ranger_tensor, %s));' % f for f in fields) + \
+        'printf("%zu %zu %zu %zu ", sizeof(tgp_ranger_tensor), offsetof(tgp_ranger_args, n), offsetof(tgp_ranger_args, units), ' \
+        'sizeof(tgp_ranger_args));printf("%d %d %d", TGP_RANGER_GC, TGP_RANGER_ADAPTIVE, TGP_RANGER_LOOKAHEAD);return 0;}\n'
+    with tempfile.TemporaryDirectory() as d:
+        with open(os.path.join(d, "t.c"), "w") as f:
+            f.write(src)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")])
+        out = [int(x) for x in subprocess.check_output([os.path.join(d, "t")]).decode().split()]
+    want = [getattr(_lib.RangerTensor, f).offset for f in fields] + [
+        ctypes.sizeof(_lib.RangerTensor), _lib.RangerArgs.n.offset, _lib.RangerArgs.units.offset, ctypes.sizeof(_lib.RangerArgs),
+        _lib.RANGER_GC, _lib.RANGER_ADAPTIVE, _lib.RANGER_LOOKAHEAD]
+    assert out == want
+
+
+def test_ranger_abi_refuses_bad_arguments_without_launching():
+    """host-side checks only: every call below returns TGP_EINVAL before anything reaches a device (none is needed here)"""
+    from tgpose_amd import _lib
+    lib = _lib.lib()
+    assert lib.tgp_version() == 8 == _lib.ABI_VERSION
+    fake = 1 << 20                      # never dereferenced: the plan is host-only
+
+    def table(**kw):
+        t = (_lib.RangerTensor * 2)()
+        for d in t:
+            d.p = d.g = d.m = d.v = d.slow = fake
+            d.numel, d.row_len, d.flags = 12, 4, _lib.RANGER_GC
+        for k, v in kw.items():
+            setattr(t[1], k, v)
+        return t
+
+    units = ctypes.c_int64(-7)
+    assert lib.tgp_ranger_plan(table(), 2, ctypes.byref(units)) == 0 and units.value == 2
+    t = table(flags=0, numel=4097)
+    assert lib.tgp_ranger_plan(t, 2, ctypes.byref(units)) == 0 and units.value == 3 and t[1].unit0 == 1
+    for bad in (dict(p=None), dict(g=None), dict(m=None), dict(v=None), dict(slow=None), dict(numel=-1), dict(row_len=0),
+                dict(row_len=5), dict(flags=8), dict(p=fake + 2)):
+        assert lib.tgp_ranger_plan(table(**bad), 2, ctypes.byref(units)) == -1, bad
+    assert lib.tgp_ranger_plan(table(), -1, ctypes.byref(units)) == -1
+    assert lib.tgp_ranger_plan(None, 2, ctypes.byref(units)) == -1
+    assert lib.tgp_ranger_plan(table(), 2, None) == -1
+    args = _lib.RangerArgs()
+    assert lib.tgp_ranger_step(None, None) == -1
+    args.tensors, args.n, args.units = None, 2, 2
+    assert lib.tgp_ranger_step(ctypes.byref(args), None) == -1
+    args.tensors, args.n, args.units = fake, -1, 2
+    assert lib.tgp_ranger_step(ctypes.byref(args), None) == -1
+    args.n, args.units = 2, -3
+    assert lib.tgp_ranger_step(ctypes.byref(args), None) == -1
+    args.n, args.units = 0, 5
+    assert lib.tgp_ranger_step(ctypes.byref(args), None) == -1
+    args.n, args.units = 2, 0                       # nothing to do: returns 0 without a launch
+    assert lib.tgp_ranger_step(ctypes.byref(args), None) == 0
+
+
+def test_ranger_refuses_unsupported_tensors():
+    from tgpose_amd.tools.torch_utils.solver.ranger2020 import Ranger
+    p = torch.nn.Parameter(torch.zeros(4, 3))
+    p.grad = torch.zeros(4, 3)
+    with pytest.raises(ValueError, match="GPU"):
+        Ranger([p]).step()
+    q = torch.nn.Parameter(torch.zeros(4, 3, dtype=torch.float64))
+    q.grad = torch.zeros(4, 3, dtype=torch.float64)
+    with pytest.raises(TypeError, match="fp32"):
+        Ranger([q]).step()
+    s = torch.nn.Parameter(torch.zeros(4, 3))
+    s.grad = torch.zeros(4, 3).to_sparse()
+    with pytest.raises(RuntimeError, match="sparse"):
+        Ranger([s]).step()

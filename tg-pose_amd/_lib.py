@@ -145,6 +145,25 @@ class DecL1Args(ctypes.Structure):
     ]
 
 
+class RangerTensor(ctypes.Structure):
+    """struct tgp_ranger_tensor (include/tgpose.h): one tensor of a tgp_ranger_step launch"""
+    _fields_ = [
+        ("p", c_vp), ("g", c_vp), ("m", c_vp), ("v", c_vp), ("slow", c_vp),
+        ("numel", c_i64),
+        ("row_len", c_int), ("flags", c_int),
+        ("unit0", c_i64),
+        ("beta1", c_f32), ("one_minus_beta1", c_f32), ("beta2", c_f32), ("one_minus_beta2", c_f32),
+        ("eps", c_f32), ("weight_decay", c_f32), ("neg_step_lr", c_f32), ("alpha", c_f32),
+    ]
+
+
+class RangerArgs(ctypes.Structure):
+    """struct tgp_ranger_args (include/tgpose.h)"""
+    _fields_ = [("tensors", c_vp), ("n", c_int), ("units", c_i64)]
+
+
+RANGER_GC, RANGER_ADAPTIVE, RANGER_LOOKAHEAD = 1, 2, 4
+
 SIGNATURES = {
     "tgp_version": (c_int, []),
     "tgp_graph_node_counts": (c_int, [c_vp, c_vp]),
@@ -252,6 +271,8 @@ SIGNATURES = {
     "tgp_dec_pack_bytes": (c_i64, []),
     "tgp_dec_pack": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "tgp_dec_l1": (c_int, [ctypes.POINTER(DecL1Args), c_vp]),
+    "tgp_ranger_plan": (c_int, [ctypes.POINTER(RangerTensor), c_int, ctypes.POINTER(c_i64)]),
+    "tgp_ranger_step": (c_int, [ctypes.POINTER(RangerArgs), c_vp]),
     "tgp_sort_by_parent": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tgp_roi_cloud": (c_int, [c_vp] * 7 + [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "tgp_cloud_select": (c_int, [c_vp] * 5 + [c_int, c_int, c_int, c_vp, c_vp]),
@@ -276,7 +297,7 @@ SIGNATURES = {
     "tgp_cloud_sample": (c_int, [c_vp] * 5 + [c_int, c_int, c_int, ctypes.c_uint64, c_vp, c_vp]),
 }
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 _lib = None
 
 

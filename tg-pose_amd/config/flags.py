@@ -30,6 +30,20 @@ _DEFAULTS = dict(
     DCD_align=1.0,       # :101
     prop_sym_w=1.0,      # :114
     lr=1e-4, lr_pose=1.0,  # :118-120 (the trainer's parameter group)
+    # the optimizer and its schedule (tools/training_utils.build_optimizer / build_lr_rate)
+    total_epoch=150,     # :60
+    train_steps=2000,    # :61
+    accumulate=1,        # :63
+    lr_scheduler_name="flat_and_anneal",  # :123
+    anneal_method="cosine",  # :124
+    anneal_point=0.72,   # :125
+    optimizer_type="Ranger",  # :126
+    weight_decay=0.0,    # :127
+    warmup_factor=0.001,  # :128
+    warmup_iters=1000,   # :129
+    warmup_method="linear",  # :130
+    gamma=0.1,           # :131
+    poly_power=0.9,      # :132
 )
 
 

@@ -1697,3 +1697,20 @@ def cloud_sample(rr, n_pts, seed, counts=None):
     check(_lib.lib().tgp_cloud_sample(_p(rr.recs), _p(counts), _p(rr.det_img), _p(rr.window), _p(rr.camk), D, rr.roi_size, n_pts,
                                       int(seed) & (2 ** 64 - 1), _p(out), _stream(rr.recs)), "tgp_cloud_sample")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------- the optimizer step
+def ranger_plan(table):
+    """Check a host descriptor table (a ctypes array of _lib.RangerTensor) and fill its unit0 fields (tgp_ranger_plan, host only:
+    nothing is launched); returns the launch's number of work units."""
+    units = ctypes.c_int64(0)
+    check(_lib.lib().tgp_ranger_plan(table, len(table), ctypes.byref(units)), "tgp_ranger_plan")
+    return units.value
+
+
+def ranger_step(table_dev, n, units):
+    """One Ranger step (tgp_ranger_step) over the n descriptors of table_dev: a uint8 device tensor holding the bytes of the table
+    ranger_plan filled, on the current stream of its device."""
+    a = _lib.RangerArgs()
+    a.tensors, a.n, a.units = _p(table_dev), int(n), int(units)
+    check(_lib.lib().tgp_ranger_step(ctypes.byref(a), _stream(table_dev)), "tgp_ranger_step")

@@ -9,9 +9,11 @@ batch-statistics BatchNorm that moves its running statistics), ``feat_consistenc
 so forward + loss + backward replay as one hipGraph (``graphed_step``); the gradient exchange between ranks
 (tgpose_amd.shard), ``clip_grad_norm_(net1, 5)`` (:223) and the optimizer step stay outside the graph.
 
-Not rebuilt (SURVEY section 8 scope): the epoch loop, logging, checkpointing, the Ranger optimizer / flat-and-anneal schedule
-(``tools/training_utils.build_optimizer`` exists only as bytecode in the reference; any ``torch.optim`` optimizer over
-``net1.parameters()`` is accepted) -- the data-parallel hot path is the step.
+The optimizer and its schedule are the reference's (:58-62 ``set_optimizer_scheduler``): Ranger (tgpose_amd.tools.torch_utils.solver.
+ranger2020: its step is one HIP launch over every parameter with a gradient) and flat_and_anneal (tgpose_amd.tools.torch_utils.solver.
+lr_scheduler), built by tgpose_amd.tools.training_utils from FLAGS; ``setup`` still accepts any ``torch.optim`` optimizer / scheduler.
+
+Not rebuilt (SURVEY section 8 scope): the epoch loop, logging, checkpointing -- the data-parallel hot path is the step.
 """
 import math
 import os
@@ -84,6 +86,13 @@ class RT_TDA_Trainer(object):
     def init_loss(self):
         self.loss_tda_net = TDA_loss()
         (self.name_fs_list, self.name_recon_list, self.name_geo_list, self.name_prop_list, self.name_TDA_list) = control_loss('TDA')
+
+    def set_optimizer_scheduler(self):
+        """trainer/RL_TDA.py:58-62: Ranger over build_params() and flat_and_anneal over train_steps * total_epoch // accumulate
+        iterations (finish_step steps both)"""
+        from ..tools.training_utils import build_optimizer, build_lr_rate
+        self.optimizer = build_optimizer(self.build_params())
+        self.scheduler = build_lr_rate(self.optimizer, total_iters=FLAGS.train_steps * FLAGS.total_epoch // FLAGS.accumulate)
 
     def build_params(self, training_stage_freeze=None):
         return [{"params": filter(lambda p: p.requires_grad, self.net1.parameters()), "lr": float(FLAGS.lr) * FLAGS.lr_pose}]
