@@ -896,6 +896,62 @@ typedef struct tgp_ranger_args {
 int tgp_ranger_plan(tgp_ranger_tensor *host_tensors, int n, int64_t *units);
 int tgp_ranger_step(const tgp_ranger_args *args, tgp_stream_t stream);
 
+/* ---- the training item's point-cloud augmentation (csrc/augment.hip; new symbols, ABI 8 unchanged) -------------------------------
+ * datasets/data_augmentation.py PC_BasicAugment (:19-63) and the second view of load_data.py:345-350 (one of PcJitter, PcRandomCutout,
+ * PcRandomCrop, PcRandomDropout), one workgroup per item.  The kernel draws nothing: every random number is an input, drawn by the
+ * host in the reference's order (datasets/data_augmentation.py of this package).
+ * Base augmentation (draws != NULL): pc (B, N, 3) -> pc_out (B, N, 3), R_out (B, 3, 3), t_out (B, 3), s_out (B, 3) (fsnet_scale
+ * residual), flags_out (B, 4) int32 {bb, rt, bc, pc} or NULL.  draws (B, 6) = prob_bb, prob_rt, prob_bc, ey_up, ey_down, prob_pc
+ * (torch.rand values); a stage is on when its prob < pro_*, bc also needs cat_id 1 (bowl) or 5 (mug).  defor (B, N, 3) = the
+ * torch.rand rows of the points (read only where the pc stage is on); model_point (B, n_model, 3) for bc's extents.  sym (B, 4) =
+ * sym_info.  pc_out may be pc.  Rounding as the reference's fp32 torch ops, the 3 x 3 products as (a0 b0 + a1 b1) + a2 b2.
+ * Second view (op != NULL; N <= tgp_augment_max_points()): on the base-augmented cloud (or pc when draws is NULL) ->
+ * view_out (B, N, 3): rows [0, M) the operator's cloud, rows [M, N) zero; count_out (B, 2) int32 = {M, accepted attempt or -1}.
+ * op (B) int32 TGP_AUG_* (TGP_AUG_NONE: the operator's p skipped it, the cloud is copied; other values act as TGP_AUG_NONE).
+ *   JITTER:  noise (B, N, 3) added (the clamped normal_ draw).
+ *   DROPOUT: a row whose drop_u (B, N) float64 is <= drop_ratio (B) float64 takes row 0.
+ *   CROP / CUTOUT: boxes (B, TGP_AUGMENT_MAX_TRY, 6) float64 = per attempt the unit-cube bounds {umin[3], umax[3]}; attempt t maps
+ *   them to coord_min + coord_diff * u in float64 (coord_* the cloud's fp32 min / max); a point is inside when strictly inside on
+ *   all three axes.  The first of attempts 0 .. *_max_try - 1 that is valid is taken (crop: crop_min_points <= inside < N, kept =
+ *   inside; cutout: N - inside >= cutout_min_points and inside > 0, kept = outside), points in their order; none valid: the cloud.
+ * pc_out / view_out rows are ld_out floats apart: 4 gives the padded rows tgp_gather_rows takes (C a multiple of 4).
+ * noise / drop_ratio / drop_u / boxes are read only for the items whose op needs them, but must be non-NULL.  view_out != pc. */
+#define TGP_AUGMENT_MAX_POINTS 2048
+#define TGP_AUGMENT_MAX_TRY 16
+#define TGP_AUG_NONE (-1)
+#define TGP_AUG_JITTER 0
+#define TGP_AUG_CUTOUT 1
+#define TGP_AUG_CROP 2
+#define TGP_AUG_DROPOUT 3
+typedef struct tgp_augment_args {
+    int B, N;
+    const float *pc;                       /* (B, N, 3) */
+    /* base augmentation */
+    const float *draws;                    /* (B, 6); NULL: no base augmentation */
+    const float *R, *t, *s, *mean_shape;   /* (B, 3, 3), (B, 3), (B, 3), (B, 3) */
+    const float *sym, *aug_bb, *aug_rt_t, *aug_rt_R;   /* (B, 4), (B, 3), (B, 3), (B, 3, 3) */
+    const float *cat_id, *nocs_scale;      /* (B), (B) */
+    const float *model_point;              /* (B, n_model, 3) */
+    int n_model;
+    const float *defor;                    /* (B, N, 3) */
+    float pro_bb, pro_rt, pro_bc, pro_pc, pc_r;
+    float *pc_out, *R_out, *t_out, *s_out;
+    int32_t *flags_out;
+    /* second view */
+    const int32_t *op;                     /* (B); NULL: no second view */
+    const float *noise;                    /* (B, N, 3) */
+    const double *drop_ratio;              /* (B) */
+    const double *drop_u;                  /* (B, N) */
+    const double *boxes;                   /* (B, TGP_AUGMENT_MAX_TRY, 6) */
+    int crop_max_try, cutout_max_try;      /* the operators' max_try_num (< TGP_AUGMENT_MAX_TRY) */
+    int crop_min_points, cutout_min_points;
+    float *view_out;                       /* (B, N, 3) */
+    int32_t *count_out;                    /* (B, 2) */
+    int ld_out;                            /* row stride of pc_out and view_out: 3 (or 0) packed, 4 padded (4th column 0) */
+} tgp_augment_args;
+int tgp_augment_max_points(void);
+int tgp_augment(const tgp_augment_args *args, tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,34 @@ class RangerArgs(ctypes.Structure):
 
 RANGER_GC, RANGER_ADAPTIVE, RANGER_LOOKAHEAD = 1, 2, 4
 
+
+class AugmentArgs(ctypes.Structure):
+    """struct tgp_augment_args (include/tgpose.h)"""
+    _fields_ = [
+        ("B", c_int), ("N", c_int),
+        ("pc", c_vp),
+        ("draws", c_vp),
+        ("R", c_vp), ("t", c_vp), ("s", c_vp), ("mean_shape", c_vp),
+        ("sym", c_vp), ("aug_bb", c_vp), ("aug_rt_t", c_vp), ("aug_rt_R", c_vp),
+        ("cat_id", c_vp), ("nocs_scale", c_vp),
+        ("model_point", c_vp), ("n_model", c_int),
+        ("defor", c_vp),
+        ("pro_bb", c_f32), ("pro_rt", c_f32), ("pro_bc", c_f32), ("pro_pc", c_f32), ("pc_r", c_f32),
+        ("pc_out", c_vp), ("R_out", c_vp), ("t_out", c_vp), ("s_out", c_vp),
+        ("flags_out", c_vp),
+        ("op", c_vp),
+        ("noise", c_vp),
+        ("drop_ratio", c_vp), ("drop_u", c_vp), ("boxes", c_vp),
+        ("crop_max_try", c_int), ("cutout_max_try", c_int), ("crop_min_points", c_int), ("cutout_min_points", c_int),
+        ("view_out", c_vp),
+        ("count_out", c_vp),
+        ("ld_out", c_int),
+    ]
+
+
+AUGMENT_MAX_POINTS, AUGMENT_MAX_TRY = 2048, 16
+AUG_NONE, AUG_JITTER, AUG_CUTOUT, AUG_CROP, AUG_DROPOUT = -1, 0, 1, 2, 3
+
 SIGNATURES = {
     "tgp_version": (c_int, []),
     "tgp_graph_node_counts": (c_int, [c_vp, c_vp]),
@@ -273,6 +301,8 @@ SIGNATURES = {
     "tgp_dec_l1": (c_int, [ctypes.POINTER(DecL1Args), c_vp]),
     "tgp_ranger_plan": (c_int, [ctypes.POINTER(RangerTensor), c_int, ctypes.POINTER(c_i64)]),
     "tgp_ranger_step": (c_int, [ctypes.POINTER(RangerArgs), c_vp]),
+    "tgp_augment_max_points": (c_int, []),
+    "tgp_augment": (c_int, [ctypes.POINTER(AugmentArgs), c_vp]),
     "tgp_sort_by_parent": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tgp_roi_cloud": (c_int, [c_vp] * 7 + [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "tgp_cloud_select": (c_int, [c_vp] * 5 + [c_int, c_int, c_int, c_vp, c_vp]),

@@ -44,6 +44,12 @@ _DEFAULTS = dict(
     warmup_method="linear",  # :130
     gamma=0.1,           # :131
     poly_power=0.9,      # :132
+    # the training loader's point-cloud augmentation (datasets/data_augmentation.py PC_BasicAugment)
+    aug_pc_pro=0.2,      # :28
+    aug_pc_r=0.2,        # :29
+    aug_rt_pro=0.3,      # :30
+    aug_bb_pro=0.3,      # :31
+    aug_bc_pro=0.3,      # :32
 )
 
 

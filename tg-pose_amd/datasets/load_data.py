@@ -15,10 +15,13 @@ What differs from the evaluation loader, and how the kernel takes it:
     walk once per item on the host, in double as OpenCV does, and the kernel looks source pixels up;
   * the cut keeps the points farther than 0.15 (not 0.25) of the diagonal -> ``cut_frac``.
 
-Out of scope, as in DESIGN.md section 8: reading files, the augmentations themselves (``aug_bbox_DZI``'s draw, ``defor_2D`` on the
-mask, ``PC_BasicAugment`` and the custom operators on the cloud -- all identity / caller-supplied here), ``compute_pd``
-(gudhi + persim).  With augmentation off the result is the reference's ``pcl_in`` bit for bit given the same ``np.random`` state
-(tests/test_gpu_parity.py::test_train_loader_vs_reference_getitem)."""
+``train_clouds`` returns the clouds with the cloud augmentation off: with it off the result is the reference's ``pcl_in`` bit for bit
+given the same ``np.random`` state (tests/test_gpu_parity.py::test_train_loader_vs_reference_getitem).  ``train_batch`` adds the
+reference's two cloud augmentations (:333-350): ``PC_BasicAugment`` and the second view ``aug_pcl_in``, one ``tgp_augment`` launch for
+the batch (datasets/data_augmentation.py of this package), with the draws made on the host in the reference's order.
+
+Out of scope, as in DESIGN.md section 8: reading files, ``aug_bbox_DZI``'s draw and ``defor_2D`` on the mask (the caller's: its
+OpenCV erode / dilate cannot be pinned here), ``compute_pd`` (gudhi + persim)."""
 import numpy as np
 import torch
 
@@ -102,6 +105,26 @@ def train_clouds(items, img_size=256, rng=np.random, device="cuda", min_points=5
     dev = torch.device(device)
     if not items:
         return []
+    rr, counts = _roi_records(items, img_size, dev)
+    D = len(items)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    sel2k, sel1k = np.zeros((D, 2048), dtype=np.int32), np.zeros((D, 1024), dtype=np.int32)
+    alive = []
+    for d in range(D):
+        total = _item_total(counts[d], min_points)
+        if total is None:
+            alive.append(False)
+            continue
+        sel2k[d] = _selection(total, 2048, rng)                # PC = _sample_points(PC, 2048)
+        sel1k[d] = sel2k[d][_selection(2048, 1024, rng)]       # pcl_in = _sample_points(PC, 1024): a selection of the selection
+        alive.append(True)
+    pc2k = ops.cloud_select(rr, up(sel2k))
+    pc1k = ops.cloud_select(rr, up(sel1k))
+    return [(pc2k[d], pc1k[d]) if alive[d] else None for d in range(D)]
+
+
+def _roi_records(items, img_size, dev):
+    """the items' ROI clouds as records (one tgp_roi_cloud_ex launch) and their counts (one 12-byte read-back per item)"""
     H, W = items[0]["depth"].shape
     tabs, camk, mval = [], [], []
     for it in items:
@@ -121,22 +144,103 @@ def train_clouds(items, img_size=256, rng=np.random, device="cuda", min_points=5
     rr = ops.roi_cloud(depth, masks, up(np.arange(D, dtype=np.int64) * (H * W)), up(np.ones(D, dtype=np.int32)),
                        up(np.arange(D, dtype=np.int32)), None, up(np.asarray(camk, dtype=np.float32)), roi_size=img_size,
                        tables=up(np.stack(tabs)), mask_val=up(np.asarray(mval, dtype=np.int32)), cut_frac=0.15)
-    counts = rr.counts.cpu().numpy()
-    sel2k, sel1k = np.zeros((D, 2048), dtype=np.int32), np.zeros((D, 1024), dtype=np.int32)
-    alive = []
-    for d in range(D):
-        n_depth, n_valid, total = (int(v) for v in counts[d])
-        if n_depth <= 1 or n_valid <= 1:                       # :262-265
-            alive.append(False)
+    return rr, rr.counts.cpu().numpy()
+
+
+def _item_total(counts, min_points):
+    """the cut cloud's point count, or None for an item the reference abandons"""
+    n_depth, n_valid, total = (int(v) for v in counts)
+    if n_depth <= 1 or n_valid <= 1:                           # :262-265
+        return None
+    if total < 0:
+        raise IndexError("index 25 is out of bounds for axis 0 with size %d" % n_valid)         # :281
+    if total < min_points:                                     # :288
+        return None
+    return total
+
+
+_IMAGE_KEYS = ("depth", "mask", "inst_id", "camK", "bbox_center", "scale", "bbox")
+_POSE_KEYS = ("rotation", "translation", "fsnet_scale")
+
+
+def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min_points=50, operators=None):
+    """``train_clouds`` plus the reference's two augmentations (load_data.py:333-350): the batch the trainer's step reads.
+
+    items: ``train_clouds``' dicts, each also carrying its labels 'rotation' (3,3), 'translation' (3,), 'fsnet_scale' (3,) (the
+    residual), 'mean_shape' (3,), 'sym_info' (4,), 'model_point' (n_model,3) (one n_model for the batch), 'nocs_scale' and 'cat_id'
+    (0-based).  Any other key (e.g. 'pdh1', 'points_category') is stacked and passed through.
+    Per item, in the reference's order: generate_aug_parameters (``rng``), PC_BasicAugment's torch draws (``gen``; None: torch's
+    default CPU generator, as the reference draws on the CPU), the two _sample_points permutations, the operator's randint(0, 4) and
+    its draws (``operators``: default_operators()), pc_sampler's shuffle.  One launch of tgp_augment for the batch (base augmentation
+    on the 2048 selected points, then the second view in LDS) and two tgp_gather_rows (pcl_in, aug_pcl_in).
+
+    Deviations from one reference __getitem__ after another (DESIGN.md section 8): crop and cutout draw all their attempts up front;
+    the shuffle of an item whose operator is crop or cutout needs its kept count M, so it is drawn after ONE read-back of the counts
+    for the batch, after every other item's draws; the draws before generate_aug_parameters (aug_bbox_DZI, defor_2D) stay with the
+    caller.  A batch without an applied crop or cutout draws exactly the reference's stream.
+    Items the reference abandons (train_clouds' None) are left out, without draws; 'item_index' lists the items kept.
+    -> dict of device tensors: pcl_in (B,1024,3), aug_pcl_in (B,1024,3), rotation (B,3,3), translation (B,3), fsnet_scale (B,3),
+    the labels passed through, aug_flags (B,4) int32 {bb, rt, bc, pc}, aug_counts (B,2) int32 (M, accepted attempt or -1),
+    item_index (B,) int64; and aug_name, a list of the operators' names."""
+    from . import data_augmentation as da
+    dev = torch.device(device)
+    ops_ = da.default_operators() if operators is None else list(operators)
+    if len(ops_) != 4:
+        raise ValueError("train_batch: the four operators of OPERATOR_NAMES are expected")
+    if not items:
+        raise ValueError("train_batch: no items")
+    rr, counts = _roi_records(items, img_size, dev)
+    keep, sel2k, p1k, shuf, recs, names, defer = [], [], [], [], [], [], []
+    params, draws, defor = [], [], []
+    for d, it in enumerate(items):
+        total = _item_total(counts[d], min_points)
+        if total is None:
             continue
-        if total < 0:
-            raise IndexError("index 25 is out of bounds for axis 0 with size %d" % n_valid)     # :281
-        if total < min_points:                                 # :288
-            alive.append(False)
-            continue
-        sel2k[d] = _selection(total, 2048, rng)                # PC = _sample_points(PC, 2048)
-        sel1k[d] = sel2k[d][_selection(2048, 1024, rng)]       # pcl_in = _sample_points(PC, 1024): a selection of the selection
-        alive.append(True)
-    pc2k = ops.cloud_select(rr, up(sel2k))
-    pc1k = ops.cloud_select(rr, up(sel1k))
-    return [(pc2k[d], pc1k[d]) if alive[d] else None for d in range(D)]
+        keep.append(d)
+        params.append(da.generate_aug_parameters(rng))                            # :318
+        dr, de = da.base_draws(1, total, "cpu", gen=gen, defor_gen=gen)           # :333 base_aug
+        draws.append(dr[0])
+        s2 = _selection(total, 2048, rng)                                         # :335
+        sel2k.append(s2)
+        defor.append(de[0][torch.from_numpy(s2.astype(np.int64))])                # the rows of the selected points only
+        p1k.append(_selection(2048, 1024, rng).astype(np.int32))                  # :336
+        k = int(rng.randint(0, len(ops_)))                                        # :346
+        rec = ops_[k].draw(2048, rng, gen)                                        # :347
+        recs.append(rec)
+        names.append(da.OPERATOR_NAMES[k])
+        if rec["op"] in (da._lib.AUG_CROP, da._lib.AUG_CUTOUT):
+            shuf.append(None)                                                     # M comes from the kernel
+            defer.append(len(keep) - 1)
+        else:
+            shuf.append(da.sampler_perm(2048, 1024, rng))                         # :348 pc_sampler
+    if not keep:
+        raise ValueError("train_batch: every item was abandoned")
+    B = len(keep)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    sel = np.zeros((len(items), 2048), dtype=np.int32)
+    sel[keep] = np.stack(sel2k)
+    pc2k = ops.cloud_select(rr, up(sel))
+    if B != len(items):
+        pc2k = pc2k[up(np.asarray(keep, dtype=np.int64))].contiguous()
+    lab = {k: [items[d][k] for d in keep] for k in items[0] if k not in _IMAGE_KEYS}
+    for k in _POSE_KEYS + ("mean_shape", "sym_info", "model_point", "nocs_scale", "cat_id"):
+        if k not in lab:
+            raise ValueError("train_batch: every item needs %r" % k)
+    f32 = lambda k: up(np.stack([np.asarray(v, dtype=np.float32) for v in lab[k]]))
+    stacked = {k: f32(k) for k in lab}
+    base = da._base_inputs(torch.stack(draws).to(dev), stacked["rotation"], stacked["translation"], stacked["fsnet_scale"],
+                           stacked["mean_shape"], stacked["sym_info"], up(np.stack([p[0] for p in params])),
+                           up(np.stack([p[1] for p in params])), up(np.stack([p[2] for p in params])), stacked["cat_id"],
+                           stacked["nocs_scale"], stacked["model_point"], torch.stack(defor).to(dev))
+    # padded (B, 2048, 4) outputs: tgp_gather_rows moves rows of a multiple of 4 floats
+    out = ops.augment(pc2k, base=base, view=da.view_inputs(recs, 2048, dev, ops_), ld_out=4)
+    if defer:                                                                     # the batch's one read-back of M
+        m = out["counts"][:, 0].cpu().numpy()
+        for i in defer:
+            shuf[i] = da.sampler_perm(int(m[i]), 1024, rng)
+    pcl_in = ops.gather_rows(out["pc"], up(np.stack(p1k)), torch.empty(B, 1024, 4, device=dev))[..., :3].contiguous()
+    aug = ops.gather_rows(out["view"], up(np.stack(shuf)), torch.empty(B, 1024, 4, device=dev))[..., :3].contiguous()
+    db = {k: v for k, v in stacked.items() if k not in _POSE_KEYS}
+    db.update(pcl_in=pcl_in, aug_pcl_in=aug, rotation=out["R"], translation=out["t"], fsnet_scale=out["s"], aug_flags=out["flags"],
+              aug_counts=out["counts"], item_index=up(np.asarray(keep, dtype=np.int64)), aug_name=names)
+    return db

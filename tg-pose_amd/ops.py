@@ -1714,3 +1714,58 @@ def ranger_step(table_dev, n, units):
     a = _lib.RangerArgs()
     a.tensors, a.n, a.units = _p(table_dev), int(n), int(units)
     check(_lib.lib().tgp_ranger_step(ctypes.byref(a), _stream(table_dev)), "tgp_ranger_step")
+
+
+# ------------------------------------------------------------------------------------------------ the training augmentation
+def _aug_arg(t, name, shape, dtype=torch.float32):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise TypeError("augment: %s must be a contiguous %s GPU tensor" % (name, dtype))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("augment: %s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    return t
+
+
+def augment(pc, base=None, view=None, pc_out=None, ld_out=3):
+    """The training item's cloud augmentation (tgp_augment, include/tgpose.h), one launch for the batch.
+
+    pc (B,N,3).  base: dict draws (B,6), R (B,3,3), t, s, mean_shape, aug_bb, aug_rt_t (B,3), sym (B,4), aug_rt_R (B,3,3), cat_id,
+    nocs_scale (B), model_point (B,n_model,3), defor (B,N,3), pro = (bb, rt, bc, pc) and pc_r floats.  view: dict op (B) int32,
+    noise (B,N,3) float32, drop_ratio (B), drop_u (B,N) and boxes (B,AUGMENT_MAX_TRY,6) float64, crop_max_try, cutout_max_try,
+    crop_min_points, cutout_min_points.  pc_out: the base-augmented cloud's buffer (may be pc; new when None).
+    -> dict: with base, pc / R / t / s / flags (B,4) int32; with view, view (B,N,3) and counts (B,2) int32 = (M, attempt)."""
+    if base is None and view is None:
+        raise ValueError("augment: nothing to do")
+    B, N = pc.shape[0], pc.shape[1]
+    _aug_arg(pc, "pc", (B, N, 3))
+    dev = pc.device
+    if ld_out not in (3, 4):
+        raise ValueError("augment: ld_out must be 3 or 4")
+    a = _lib.AugmentArgs()
+    a.B, a.N, a.pc, a.ld_out = B, N, _p(pc), ld_out
+    out = {}
+    if base is not None:
+        nm = base["model_point"].shape[1] if base["model_point"].dim() == 3 else -1
+        for k, shp in (("draws", (B, 6)), ("R", (B, 3, 3)), ("t", (B, 3)), ("s", (B, 3)), ("mean_shape", (B, 3)), ("sym", (B, 4)),
+                       ("aug_bb", (B, 3)), ("aug_rt_t", (B, 3)), ("aug_rt_R", (B, 3, 3)), ("cat_id", (B,)), ("nocs_scale", (B,)),
+                       ("model_point", (B, nm, 3)), ("defor", (B, N, 3))):
+            setattr(a, k, _p(_aug_arg(base[k], k, shp)))
+        a.n_model = nm
+        a.pro_bb, a.pro_rt, a.pro_bc, a.pro_pc = (float(v) for v in base["pro"])
+        a.pc_r = float(base["pc_r"])
+        pc_out = torch.empty(B, N, ld_out, device=dev) if pc_out is None else _aug_arg(pc_out, "pc_out", (B, N, ld_out))
+        out.update(pc=pc_out, R=torch.empty(B, 3, 3, device=dev), t=torch.empty(B, 3, device=dev), s=torch.empty(B, 3, device=dev),
+                   flags=torch.empty(B, 4, device=dev, dtype=torch.int32))
+        a.pc_out, a.R_out, a.t_out, a.s_out, a.flags_out = (_p(out[k]) for k in ("pc", "R", "t", "s", "flags"))
+    if view is not None:
+        _aug_arg(view["op"], "op", (B,), torch.int32)
+        _aug_arg(view["noise"], "noise", (B, N, 3))
+        _aug_arg(view["drop_ratio"], "drop_ratio", (B,), torch.float64)
+        _aug_arg(view["drop_u"], "drop_u", (B, N), torch.float64)
+        _aug_arg(view["boxes"], "boxes", (B, _lib.AUGMENT_MAX_TRY, 6), torch.float64)
+        a.op, a.noise, a.drop_ratio, a.drop_u, a.boxes = (_p(view[k]) for k in ("op", "noise", "drop_ratio", "drop_u", "boxes"))
+        for k in ("crop_max_try", "cutout_max_try", "crop_min_points", "cutout_min_points"):
+            setattr(a, k, int(view[k]))
+        out.update(view=torch.empty(B, N, ld_out, device=dev), counts=torch.empty(B, 2, device=dev, dtype=torch.int32))
+        a.view_out, a.count_out = _p(out["view"]), _p(out["counts"])
+    check(_lib.lib().tgp_augment(ctypes.byref(a), _stream(pc)), "tgp_augment")
+    return out
