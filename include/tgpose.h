@@ -952,6 +952,44 @@ typedef struct tgp_augment_args {
 int tgp_augment_max_points(void);
 int tgp_augment(const tgp_augment_args *args, tgp_stream_t stream);
 
+/* ---- ground-truth persistence images of the training clouds (csrc/persistence.hip; new symbols, ABI 8 unchanged) -----------
+ * datasets/compute_pd.py of the reference: per cloud pcl (B, N, 3) float32, N <= TGP_PD_MAX_POINTS, the alpha complex of the
+ * unique points (Delaunay triangulation, squared-radius values), its H1 / H2 persistence pairs with death > birth, and the legacy
+ * persim PersImage(spread=1e-2, pixels=[50, 50]) of each dimension, normalised to a maximum of 1.
+ * Outputs per cloud: h1 / h2 (B, TGP_PD_MAX_PAIRS, 2) float64 (birth, death) rows [0, counts), counts (B, 2) int32 {H1, H2},
+ * status (B) int32 (0 or TGP_PD_E*; a failed cloud has counts 0 and zero images), tets (B, TGP_PD_MAX_TETS, 4) int32 the finite
+ * tetrahedra as indices into the cloud's rows (first occurrence of a duplicated point) and ntet (B), or NULL; pdh1 / pdh2
+ * (B, 2500) float32 or both NULL (pairs only).  workspace: B * tgp_pd_workspace_bytes() bytes, 256-byte aligned.
+ * tet_cap: 0 for TGP_PD_MAX_TETS, a smaller value caps the triangulation (the overflow path, for tests).
+ * Two launches, no host synchronisation; a capacity overflow sets the cloud's status, it never writes out of bounds. */
+#define TGP_PD_MAX_POINTS 1024
+#define TGP_PD_MAX_TETS 8192
+#define TGP_PD_MAX_PAIRS 4096
+#define TGP_PD_PIXELS 2500
+#define TGP_PD_ETETS 1        /* tetrahedron / simplex storage */
+#define TGP_PD_ECAVITY 2      /* one insertion's cavity */
+#define TGP_PD_EWALK 3        /* point location did not end */
+#define TGP_PD_EPAIRS 4       /* more than TGP_PD_MAX_PAIRS pairs in one dimension */
+#define TGP_PD_ECOLUMNS 5     /* H1 column storage */
+#define TGP_PD_ERANGE 6       /* a coordinate is not finite, or too small against the cloud's extent for the exact grid */
+#define TGP_PD_EFLAT 7        /* fewer than 4 affinely independent points */
+#define TGP_PD_EINTERNAL 8    /* an inconsistency that a valid triangulation cannot produce */
+typedef struct tgp_pd_args {
+    int B, N;
+    const float *pcl;          /* (B, N, 3) */
+    void *workspace;
+    double *h1, *h2;           /* (B, TGP_PD_MAX_PAIRS, 2) */
+    int32_t *counts;           /* (B, 2) */
+    int32_t *status;           /* (B) */
+    int32_t *tets;             /* (B, TGP_PD_MAX_TETS, 4) or NULL */
+    int32_t *ntet;             /* (B); read when tets != NULL */
+    float *pdh1, *pdh2;        /* (B, TGP_PD_PIXELS) or NULL */
+    int tet_cap;
+} tgp_pd_args;
+int64_t tgp_pd_workspace_bytes(void);
+int tgp_pd_max_points(void);
+int tgp_persistence(const tgp_pd_args *args, tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

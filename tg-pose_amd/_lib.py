@@ -192,6 +192,26 @@ class AugmentArgs(ctypes.Structure):
 AUGMENT_MAX_POINTS, AUGMENT_MAX_TRY = 2048, 16
 AUG_NONE, AUG_JITTER, AUG_CUTOUT, AUG_CROP, AUG_DROPOUT = -1, 0, 1, 2, 3
 
+
+class PdArgs(ctypes.Structure):
+    """struct tgp_pd_args (include/tgpose.h)"""
+    _fields_ = [
+        ("B", c_int), ("N", c_int),
+        ("pcl", c_vp), ("workspace", c_vp),
+        ("h1", c_vp), ("h2", c_vp),
+        ("counts", c_vp), ("status", c_vp),
+        ("tets", c_vp), ("ntet", c_vp),
+        ("pdh1", c_vp), ("pdh2", c_vp),
+        ("tet_cap", c_int),
+    ]
+
+
+PD_MAX_POINTS, PD_MAX_TETS, PD_MAX_PAIRS, PD_PIXELS = 1024, 8192, 4096, 2500
+PD_STATUS = {1: "TGP_PD_ETETS (tetrahedron / simplex storage)", 2: "TGP_PD_ECAVITY (one insertion's cavity)",
+             3: "TGP_PD_EWALK (point location did not end)", 4: "TGP_PD_EPAIRS (more than PD_MAX_PAIRS pairs)",
+             5: "TGP_PD_ECOLUMNS (H1 column storage)", 6: "TGP_PD_ERANGE (coordinate not finite or below the exact grid)",
+             7: "TGP_PD_EFLAT (fewer than 4 affinely independent points)", 8: "TGP_PD_EINTERNAL"}
+
 SIGNATURES = {
     "tgp_version": (c_int, []),
     "tgp_graph_node_counts": (c_int, [c_vp, c_vp]),
@@ -303,6 +323,9 @@ SIGNATURES = {
     "tgp_ranger_step": (c_int, [ctypes.POINTER(RangerArgs), c_vp]),
     "tgp_augment_max_points": (c_int, []),
     "tgp_augment": (c_int, [ctypes.POINTER(AugmentArgs), c_vp]),
+    "tgp_pd_workspace_bytes": (c_i64, []),
+    "tgp_pd_max_points": (c_int, []),
+    "tgp_persistence": (c_int, [ctypes.POINTER(PdArgs), c_vp]),
     "tgp_sort_by_parent": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tgp_roi_cloud": (c_int, [c_vp] * 7 + [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "tgp_cloud_select": (c_int, [c_vp] * 5 + [c_int, c_int, c_int, c_vp, c_vp]),

@@ -163,7 +163,7 @@ _IMAGE_KEYS = ("depth", "mask", "inst_id", "camK", "bbox_center", "scale", "bbox
 _POSE_KEYS = ("rotation", "translation", "fsnet_scale")
 
 
-def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min_points=50, operators=None):
+def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min_points=50, operators=None, persistence=False):
     """``train_clouds`` plus the reference's two augmentations (load_data.py:333-350): the batch the trainer's step reads.
 
     items: ``train_clouds``' dicts, each also carrying its labels 'rotation' (3,3), 'translation' (3,), 'fsnet_scale' (3,) (the
@@ -181,8 +181,13 @@ def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min
     Items the reference abandons (train_clouds' None) are left out, without draws; 'item_index' lists the items kept.
     -> dict of device tensors: pcl_in (B,1024,3), aug_pcl_in (B,1024,3), rotation (B,3,3), translation (B,3), fsnet_scale (B,3),
     the labels passed through, aug_flags (B,4) int32 {bb, rt, bc, pc}, aug_counts (B,2) int32 (M, accepted attempt or -1),
-    item_index (B,) int64; and aug_name, a list of the operators' names."""
+    item_index (B,) int64; and aug_name, a list of the operators' names.
+    persistence=True also computes the reference's compute_pd targets from pcl_in (load_data.py:343): pdh1 and pdh2 (B, 2500)
+    float32, by ops.persistence_images (no random draws, so the draw order above is unchanged); items that carry 'pdh1' or 'pdh2'
+    themselves are refused."""
     from . import data_augmentation as da
+    if persistence and any("pdh1" in it or "pdh2" in it for it in items):
+        raise ValueError("train_batch: persistence=True computes pdh1 / pdh2; the items must not carry them")
     dev = torch.device(device)
     ops_ = da.default_operators() if operators is None else list(operators)
     if len(ops_) != 4:
@@ -243,4 +248,6 @@ def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min
     db = {k: v for k, v in stacked.items() if k not in _POSE_KEYS}
     db.update(pcl_in=pcl_in, aug_pcl_in=aug, rotation=out["R"], translation=out["t"], fsnet_scale=out["s"], aug_flags=out["flags"],
               aug_counts=out["counts"], item_index=up(np.asarray(keep, dtype=np.int64)), aug_name=names)
+    if persistence:
+        db["pdh1"], db["pdh2"] = ops.persistence_images(pcl_in)
     return db

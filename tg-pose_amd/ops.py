@@ -1769,3 +1769,64 @@ def augment(pc, base=None, view=None, pc_out=None, ld_out=3):
         a.view_out, a.count_out = _p(out["view"]), _p(out["counts"])
     check(_lib.lib().tgp_augment(ctypes.byref(a), _stream(pc)), "tgp_augment")
     return out
+
+
+def _pd_launch(pcl, images, tets=False, tet_cap=0):
+    if not isinstance(pcl, torch.Tensor) or pcl.dim() != 3 or pcl.shape[2] != 3:
+        raise ValueError("persistence: pcl must be a (B, N, 3) tensor")
+    if pcl.dtype != torch.float32 or pcl.device.type != "cuda":
+        raise ValueError("persistence: pcl must be float32 on the device")
+    B, N = pcl.shape[0], pcl.shape[1]
+    if B == 0 or N == 0 or N > _lib.PD_MAX_POINTS:
+        raise ValueError("persistence: 1 <= N <= %d points per cloud, B >= 1" % _lib.PD_MAX_POINTS)
+    pcl = pcl.contiguous()
+    dev = pcl.device
+    lib = _lib.lib()
+    ws = torch.empty(B * int(lib.tgp_pd_workspace_bytes()), dtype=torch.uint8, device=dev)
+    out = dict(h1=torch.empty(B, _lib.PD_MAX_PAIRS, 2, dtype=torch.float64, device=dev),
+               h2=torch.empty(B, _lib.PD_MAX_PAIRS, 2, dtype=torch.float64, device=dev),
+               counts=torch.empty(B, 2, dtype=torch.int32, device=dev), status=torch.empty(B, dtype=torch.int32, device=dev))
+    a = _lib.PdArgs()
+    a.B, a.N, a.pcl, a.workspace, a.tet_cap = B, N, _p(pcl), _p(ws), int(tet_cap)
+    a.h1, a.h2, a.counts, a.status = (_p(out[k]) for k in ("h1", "h2", "counts", "status"))
+    if tets:
+        out.update(tets=torch.empty(B, _lib.PD_MAX_TETS, 4, dtype=torch.int32, device=dev), ntet=torch.empty(B, dtype=torch.int32, device=dev))
+        a.tets, a.ntet = _p(out["tets"]), _p(out["ntet"])
+    if images:
+        out.update(pdh1=torch.empty(B, _lib.PD_PIXELS, device=dev), pdh2=torch.empty(B, _lib.PD_PIXELS, device=dev))
+        a.pdh1, a.pdh2 = _p(out["pdh1"]), _p(out["pdh2"])
+    check(lib.tgp_persistence(ctypes.byref(a), _stream(pcl)), "tgp_persistence")
+    out["_ws"] = ws           # kept alive until the launches have run
+    return out
+
+
+def pd_check_status(status):
+    """raise TgpError naming the clouds whose status word is not 0 (synchronises)"""
+    st = status.cpu().numpy()
+    bad = [(i, int(s)) for i, s in enumerate(st) if s != 0]
+    if bad:
+        raise _lib.TgpError("tgp_persistence failed for %d cloud(s): %s" % (len(bad), ", ".join(
+            "cloud %d: %s" % (i, _lib.PD_STATUS.get(s, "status %d" % s)) for i, s in bad[:8])))
+
+
+def persistence_images(pcl, check_status=True):
+    """The reference's compute_pd images for a batch of clouds (tgp_persistence, include/tgpose.h): two launches, no host sync.
+
+    pcl (B, N, 3) float32 on the device, N <= 1024.  -> (pdh1, pdh2), each (B, 2500) float32.  check_status=True synchronises
+    once and raises TgpError if a cloud failed (capacity, degenerate cloud); False returns (pdh1, pdh2, status) without a sync,
+    for graph capture (a failed cloud's images are zeros and its status word names the reason)."""
+    out = _pd_launch(pcl, images=True)
+    if check_status:
+        pd_check_status(out["status"])
+        return out["pdh1"], out["pdh2"]
+    return out["pdh1"], out["pdh2"], out["status"]
+
+
+def alpha_persistence(pcl, tet_cap=0):
+    """Diagnosis and tests: the padded pairs and the triangulation of each cloud, without images and without a sync.
+
+    -> dict h1 / h2 (B, 4096, 2) float64 (birth, death) rows [0, counts), counts (B, 2) int32 {H1, H2}, status (B) int32,
+    tets (B, 8192, 4) int32 rows [0, ntet) the finite Delaunay tetrahedra as row indices of pcl, ntet (B) int32.
+    tet_cap < 8192 caps the triangulation's storage (status TGP_PD_ETETS when it is exceeded)."""
+    out = _pd_launch(pcl, images=False, tets=True, tet_cap=tet_cap)
+    return out
