@@ -613,6 +613,27 @@ int tgp_roi_cloud(const uint16_t *depth, const uint8_t *masks, const int64_t *ma
 int tgp_roi_cloud_ex(const uint16_t *depth, const uint8_t *masks, const int64_t *mask_off, const int *mask_stride, const int *det_img,
                      const int *window, const float *camk, int D, int H, int W, int roi_size, uint32_t *recs, int *counts,
                      const int *tables, const int *mask_val, float cut_frac, tgp_stream_t stream);
+/* The training loader's mask deformation defor_2D (datasets/data_augmentation.py:319-342, applied at load_data.py:280), in two
+ * launches.  M = the warped mask as tgp_roi_cloud_ex tests it; a pixel is in the BAND when M differs from its up or left ROI
+ * neighbour (OpenCV's 2x2 ellipse [[0,1],[1,1]], anchor (1,1), one erode / dilate iteration, neighbours outside the ROI ignored).
+ *
+ * tgp_roi_band: band_counts (D,3) int32 = depth-valid ROI pixels, valid points with the UNDEFORMED mask (the reference's validity
+ * tests, :259-264), band size l.  Other arguments as tgp_roi_cloud_ex.
+ *
+ * tgp_roi_cloud_defor: tgp_roi_cloud_ex with, per detection, defor_on (D) int32 (0: records and counts bit-identical to
+ * tgp_roi_cloud_ex) and drop_bits (D, drop_words) uint32, bit r of row d set = the band pixel of row-major band rank r is dropped.
+ * An applied detection keeps a pixel when depth > 0 and (band ? !drop[rank] : M): band pixels not dropped become 1, including
+ * those where M was 0.  counts[1] stays the undeformed count; point 25, the cut and counts[2] follow the deformed mask; below 26
+ * deformed points counts[2] = -(1 + the deformed count) (tgp_roi_cloud_ex writes -1).
+ * cut_frac = -1: no cut, counts[2] = the deformed count (never -1).  drop_words in [0, 2048]; ranks past 32 x drop_words are
+ * kept. */
+int tgp_roi_band(const uint16_t *depth, const uint8_t *masks, const int64_t *mask_off, const int *mask_stride, const int *det_img,
+                 const int *window, int D, int H, int W, int roi_size, int *band_counts, const int *tables, const int *mask_val,
+                 tgp_stream_t stream);
+int tgp_roi_cloud_defor(const uint16_t *depth, const uint8_t *masks, const int64_t *mask_off, const int *mask_stride,
+                        const int *det_img, const int *window, const float *camk, int D, int H, int W, int roi_size, uint32_t *recs,
+                        int *counts, const int *tables, const int *mask_val, float cut_frac, const int *defor_on,
+                        const uint32_t *drop_bits, int drop_words, tgp_stream_t stream);
 /* tgp_cloud_select with the detections' source-pixel tables (NULL: the window's closed form). */
 int tgp_cloud_select_ex(const uint32_t *recs, const int32_t *sel, const int *det_img, const int *window, const float *camk, int D,
                         int roi_size, int n_pts, float *out, const int *tables, tgp_stream_t stream);

@@ -50,6 +50,13 @@ _DEFAULTS = dict(
     aug_rt_pro=0.3,      # :30
     aug_bb_pro=0.3,      # :31
     aug_bc_pro=0.3,      # :32
+    # the training loader's mask deformation and box augmentation (defor_2D, aug_bbox_DZI)
+    roi_mask_r=3,        # :26 (inert: the reference passes it as cv2.erode's dst)
+    roi_mask_pro=0.5,    # :27
+    DZI_PAD_SCALE=1.5,   # :17
+    DZI_TYPE="uniform",  # :18
+    DZI_SCALE_RATIO=0.25,  # :19
+    DZI_SHIFT_RATIO=0.25,  # :20
 )
 
 

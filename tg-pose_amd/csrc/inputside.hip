@@ -61,6 +61,43 @@ __device__ __forceinline__ void ordered_slots(const bool (&keep)[ROI_SUB], int (
     base += __builtin_amdgcn_readlane(incl, ROI_SUB * ROI_WAVES - 1);
 }
 
+// Two ordered compactions of different rounds behind ONE barrier (the deformed walk: the records of round c and the band ranks of
+// round c+1, see roi_cloud_kernel).  Same arithmetic as ordered_slots, once per table.
+template <int ROI_SUB>
+__device__ __forceinline__ void ordered_slots_pair(const bool (&keep)[ROI_SUB], int (*tot)[ROI_SUB][ROI_WAVES], int parity, int &base,
+                                                   int (&slot)[ROI_SUB], const bool (&keep2)[ROI_SUB], int (*tot2)[ROI_SUB][ROI_WAVES],
+                                                   int parity2, int &base2, int (&slot2)[ROI_SUB])
+{
+    const int lane = threadIdx.x & (TGP_WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / TGP_WAVE);
+    unsigned long long bal[ROI_SUB], bal2[ROI_SUB];
+#pragma unroll
+    for (int k = 0; k < ROI_SUB; ++k) {
+        bal[k] = __ballot(keep[k]);
+        bal2[k] = __ballot(keep2[k]);
+        if (lane == 0) tot[parity][k][wave] = __popcll(bal[k]), tot2[parity2][k][wave] = __popcll(bal2[k]);
+    }
+    __syncthreads();
+    const int own = lane < ROI_SUB * ROI_WAVES ? (&tot[parity][0][0])[lane] : 0;
+    const int own2 = lane < ROI_SUB * ROI_WAVES ? (&tot2[parity2][0][0])[lane] : 0;
+    int incl = own, incl2 = own2;
+#pragma unroll
+    for (int o = 1; o < ROI_SUB * ROI_WAVES; o <<= 1) {
+        const int up = __shfl_up(incl, o), up2 = __shfl_up(incl2, o);
+        incl += lane >= o ? up : 0;
+        incl2 += lane >= o ? up2 : 0;
+    }
+    const int excl = incl - own, excl2 = incl2 - own2;
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int k = 0; k < ROI_SUB; ++k) {
+        slot[k] = base + __builtin_amdgcn_readlane(excl, k * ROI_WAVES + wave) + __popcll(bal[k] & below);
+        slot2[k] = base2 + __builtin_amdgcn_readlane(excl2, k * ROI_WAVES + wave) + __popcll(bal2[k] & below);
+    }
+    base += __builtin_amdgcn_readlane(incl, ROI_SUB * ROI_WAVES - 1);
+    base2 += __builtin_amdgcn_readlane(incl2, ROI_SUB * ROI_WAVES - 1);
+}
+
 __device__ __forceinline__ float wave_min(float v)
 {
 #pragma unroll
@@ -125,17 +162,30 @@ struct RoiGeom {
     }
 };
 
-template <int ROI_SUB>
+// DEFOR: the training loader's mask deformation (defor_2D, datasets/data_augmentation.py:319-342) applied inside the walk.  M is the
+// warped mask; a pixel is in the BAND when M differs from its up or left ROI neighbour (the erode != dilate set of OpenCV's 2x2
+// ellipse [[0,1],[1,1]], anchor (1,1), one iteration, neighbours outside the ROI ignored).  An item with defor_on[j] set keeps
+//     deformed = band ? !drop[rank] : M,   rank = the pixel's row-major rank among the band pixels,
+// and drop = the host's np.random.choice draw as a bitmap over ranks.  The band ranks come from a second ordered scan that runs
+// one round AHEAD of the records' scan and shares its barrier (ordered_slots_pair): round c's keep needs round c's ranks.
+// counts[1] stays the undeformed n_valid (the reference tests it before defor_2D); point 25, the cut and counts[2] follow the
+// deformed mask; below 26 deformed points counts[2] = -(1 + that count).  cut_frac < 0 (DEFOR only): no cut, counts[2] = the
+// deformed count (the device defor_2D).
+template <int ROI_SUB, bool DEFOR = false>
 __global__ __launch_bounds__(ROI_THREADS) void roi_cloud_kernel(const uint16_t *__restrict__ depth, const uint8_t *__restrict__ masks,
                                                                 const int64_t *__restrict__ mask_off, const int *__restrict__ mask_stride,
                                                                 const int *__restrict__ det_img, const int *__restrict__ window,
                                                                 const float *__restrict__ camk, int H, int W, int roi_log2,
                                                                 uint32_t *recs, int *__restrict__ counts, const int *__restrict__ tables,
-                                                                const int *__restrict__ mask_val, float cut_frac)
+                                                                const int *__restrict__ mask_val, float cut_frac,
+                                                                const int *__restrict__ defor_on, const uint32_t *__restrict__ drop_bits,
+                                                                int drop_words)
 {
     __shared__ int tot[2][ROI_SUB][ROI_WAVES];
+    __shared__ int btot[DEFOR ? 2 : 1][ROI_SUB][ROI_WAVES];
     __shared__ float red[6][ROI_WAVES];
     __shared__ int n_depth_waves[ROI_WAVES];
+    __shared__ int n_valid_sum;         // DEFOR: the undeformed n_valid (an integer LDS sum: the per-wave table costs a spill)
     const int j = blockIdx.x, tid = threadIdx.x;
     const int roi = 1 << roi_log2;
     const int cap = roi * roi;
@@ -161,11 +211,20 @@ __global__ __launch_bounds__(ROI_THREADS) void roi_cloud_kernel(const uint16_t *
     const int colq = min(max(sx, 0), W - 1);
     const float xm = (float)sx - g.cx;
     const int row0 = __builtin_amdgcn_readfirstlane(tid >> roi_log2);      // this wave's row within a 1024-pixel sub-round
+    auto match = [&](int v) { return mval ? v == mval : v != 0; };
+    // DEFOR: the left neighbour's source column (x > 0 only) and the item's drop bitmap
+    const int sxl = DEFOR && x > 0 ? g.src_x(x - 1) : -1;
+    const bool inbxl = sxl >= 0 && sxl < W;
+    const int colql = min(max(sxl, 0), W - 1);
+    const bool def_on = DEFOR && defor_on[j] != 0;
+    const uint32_t *drop = DEFOR ? drop_bits + (size_t)j * drop_words : nullptr;
+    const int drop_cap = drop_words * 32;
+    if (DEFOR && tid == 0) n_valid_sum = 0;         // ordered before the sum by pass 1's barriers
     // The walk is a chain of dependent rounds (loads -> ballot -> barrier -> scan -> stores) on one CU, so what bounds it is
     // latency, not bandwidth or issue (SQ counters: waves wait 69 % of their cycles).  Round c+1's loads are therefore issued
     // before round c's barrier and stores: they do not depend on round c, and being older than the stores they can be waited
     // for without waiting for the stores (vmcnt retires in order).
-    int d_next[ROI_SUB], m_next[ROI_SUB];
+    int d_next[ROI_SUB], m_next[ROI_SUB], mu_next[ROI_SUB], ml_next[ROI_SUB];
     float ym_next[ROI_SUB];
     auto fetch = [&](int c) {
 #pragma unroll
@@ -178,23 +237,71 @@ __global__ __launch_bounds__(ROI_THREADS) void roi_cloud_kernel(const uint16_t *
             ym_next[k] = (float)sy - g.cy;
             d_next[k] = inb ? (int)dimg[q] : 0;
             m_next[k] = inb ? (int)mimg[q * mstride] : 0;
+            if constexpr (DEFOR) {          // the up and left ROI neighbours' mask bytes (L2-resident re-reads)
+                const int syu = y > 0 ? g.src_y(y - 1) : -1;
+                const bool inbu = inbx && syu >= 0 && syu < H, inbl = inbxl && sy >= 0 && sy < H;
+                mu_next[k] = inbu ? (int)mimg[(min(max(syu, 0), H - 1) * W + colq) * mstride] : 0;
+                ml_next[k] = inbl ? (int)mimg[(min(max(sy, 0), H - 1) * W + colql) * mstride] : 0;
+            }
         }
     };
+    // DEFOR: band flags of round c from its fetched bytes (m_next / mu_next / ml_next); m_next[k] becomes M | band << 1 (the mask
+    // byte is not needed past this point, and one packed word keeps the walk within 128 VGPRs)
+    auto band_of = [&](int c, bool (&b)[ROI_SUB]) {
+#pragma unroll
+        for (int k = 0; k < ROI_SUB; ++k) {
+            const int y = ((c * ROI_SUB + k) * ROI_THREADS >> roi_log2) + row0;
+            const bool M = match(m_next[k]);
+            b[k] = (y > 0 && match(mu_next[k]) != M) || (x > 0 && match(ml_next[k]) != M);
+            m_next[k] = (int)M | ((int)b[k] << 1);
+        }
+    };
+    int bbase = 0, n_und = 0;
+    int brank_next[ROI_SUB];
     fetch(0);
+    if constexpr (DEFOR) {          // the band ranks of round 0: the walk's one extra barrier
+        bool b[ROI_SUB];
+        band_of(0, b);
+        ordered_slots(b, btot, 0, bbase, brank_next);
+    }
     for (int c = 0; c < rounds; ++c) {
         int d[ROI_SUB], m[ROI_SUB];
         float ym[ROI_SUB];
         bool keep[ROI_SUB];
         int slot[ROI_SUB];
+        int brank[ROI_SUB];
 #pragma unroll
         for (int k = 0; k < ROI_SUB; ++k) d[k] = d_next[k], m[k] = m_next[k], ym[k] = ym_next[k];
+        if constexpr (DEFOR) {
+#pragma unroll
+            for (int k = 0; k < ROI_SUB; ++k) brank[k] = brank_next[k];
+        }
         if (c + 1 < rounds) fetch(c + 1);
 #pragma unroll
         for (int k = 0; k < ROI_SUB; ++k) {
             n_depth += d[k] > 0;
-            keep[k] = d[k] > 0 && (mval ? m[k] == mval : m[k] != 0);
+            if constexpr (DEFOR) {
+                const bool M = m[k] & 1, band = m[k] & 2;
+                n_und += d[k] > 0 && M;
+                const int r = brank[k];
+                const bool dropped = r < drop_cap && ((drop[r >> 5] >> (r & 31)) & 1u);
+                keep[k] = d[k] > 0 && (def_on && band ? !dropped : M);
+            } else {
+                keep[k] = d[k] > 0 && (mval ? m[k] == mval : m[k] != 0);
+            }
         }
-        ordered_slots(keep, tot, c & 1, base, slot);
+        if constexpr (DEFOR) {
+            bool bn[ROI_SUB];
+            if (c + 1 < rounds) {
+                band_of(c + 1, bn);
+            } else {
+#pragma unroll
+                for (int k = 0; k < ROI_SUB; ++k) bn[k] = false;
+            }
+            ordered_slots_pair(keep, tot, c & 1, base, slot, bn, btot, (c + 1) & 1, bbase, brank_next);
+        } else {
+            ordered_slots(keep, tot, c & 1, base, slot);
+        }
 #pragma unroll
         for (int k = 0; k < ROI_SUB; ++k)
             if (keep[k]) {
@@ -220,6 +327,12 @@ __global__ __launch_bounds__(ROI_THREADS) void roi_cloud_kernel(const uint16_t *
             red[3][wave] = hi0, red[4][wave] = hi1, red[5][wave] = hi2;
             n_depth_waves[wave] = nd;
         }
+        if constexpr (DEFOR) {
+            int nu = n_und;
+#pragma unroll
+            for (int o = TGP_WAVE / 2; o > 0; o >>= 1) nu += __shfl_xor(nu, o);
+            if (lane == 0) atomicAdd(&n_valid_sum, nu);
+        }
     }
     __syncthreads();        // also orders pass 1's global stores before pass 2's loads (same workgroup, same CU)
     int nd_all = 0;
@@ -229,9 +342,17 @@ __global__ __launch_bounds__(ROI_THREADS) void roi_cloud_kernel(const uint16_t *
         hi0 = fmaxf(hi0, red[3][w]), hi1 = fmaxf(hi1, red[4][w]), hi2 = fmaxf(hi2, red[5][w]);
         nd_all += n_depth_waves[w];
     }
-    if (tid == 0) counts[j * 3] = nd_all, counts[j * 3 + 1] = n_valid;
+    if constexpr (DEFOR) {
+        if (tid == 0) counts[j * 3] = nd_all, counts[j * 3 + 1] = n_valid_sum;
+        if (cut_frac < 0.f) {
+            if (tid == 0) counts[j * 3 + 2] = n_valid;
+            return;
+        }
+    } else {
+        if (tid == 0) counts[j * 3] = nd_all, counts[j * 3 + 1] = n_valid;
+    }
     if (n_valid < 26) {     // the reference indexes point 25 (:350) and raises; the host mirror raises for -1
-        if (tid == 0) counts[j * 3 + 2] = -1;
+        if (tid == 0) counts[j * 3 + 2] = DEFOR ? -1 - n_valid : -1;      // DEFOR: the deformed count too (0 points: np.min raises)
         return;
     }
 
@@ -310,7 +431,103 @@ extern "C" int tgp_roi_cloud_ex(const uint16_t *depth, const uint8_t *masks, con
     static const int sub = [] { const char *e = getenv("TGP_ROI_SUB"); return e ? atoi(e) : 4; }();     // development A/B
     auto kern = sub == 1 ? roi_cloud_kernel<1> : sub == 2 ? roi_cloud_kernel<2> : roi_cloud_kernel<4>;
     hipLaunchKernelGGL(kern, dim3(D), dim3(ROI_THREADS), 0, tgp_hs(stream), depth, masks, mask_off, mask_stride, det_img, window, camk, H, W,
-                       lg, recs, counts, tables, mask_val, cut_frac);
+                       lg, recs, counts, tables, mask_val, cut_frac, nullptr, nullptr, 0);
+    return TGP_LAUNCH_RESULT();
+}
+
+// The band launch of the deformed walk: per item n_depth, the undeformed n_valid (the reference's validity tests, :259-264) and the
+// band's size l (how many pixels defor_2D's draw chooses among).  Counts only, no order: every thread walks its column and the
+// block sums; the walk of roi_cloud_kernel (same source tables, same mask test) without its barriers.
+__global__ __launch_bounds__(ROI_THREADS) void roi_band_kernel(const uint16_t *__restrict__ depth, const uint8_t *__restrict__ masks,
+                                                               const int64_t *__restrict__ mask_off, const int *__restrict__ mask_stride,
+                                                               const int *__restrict__ det_img, const int *__restrict__ window, int H, int W,
+                                                               int roi_log2, const int *__restrict__ tables, const int *__restrict__ mask_val,
+                                                               int *__restrict__ band_counts)
+{
+    __shared__ int red[3][ROI_WAVES];
+    const int j = blockIdx.x, tid = threadIdx.x;
+    const int roi = 1 << roi_log2, cap = roi * roi, step = 1024 >> roi_log2;
+    const int img = det_img[j];
+    const int *tab = tables ? tables + ((size_t)j << (roi_log2 + 1)) : nullptr;
+    const int sumc = tab ? 0 : window[j * 3], sumr = tab ? 0 : window[j * 3 + 1], s = tab ? 0 : window[j * 3 + 2];
+    auto src_x = [&](int x) { return tab ? tab[x] : src_coord(sumc, s, x, step); };
+    auto src_y = [&](int y) { return tab ? tab[roi + y] : src_coord(sumr, s, y, step); };
+    const int mval = mask_val ? mask_val[j] : 0;
+    const uint16_t *dimg = depth + (size_t)img * H * W;
+    const uint8_t *mimg = masks + mask_off[j];
+    const int mstride = mask_stride[j];
+    // M at (sy, sx): 0 outside the frame (warpAffine's constant border).  Clamped address, no branch round the load, so an unrolled
+    // group of pixels has all its loads in flight (the walk is latency-bound: 64 pixels per thread, one CU per item)
+    auto mask_at = [&](int sy, int sx) {
+        const bool in = sx >= 0 && sx < W && sy >= 0 && sy < H;
+        const int v = mimg[(min(max(sy, 0), H - 1) * W + min(max(sx, 0), W - 1)) * mstride];
+        return in && (mval ? v == mval : v != 0);
+    };
+    const int x = tid & (roi - 1), row0 = tid >> roi_log2;
+    const int sx = src_x(x), sxl = x > 0 ? src_x(x - 1) : -1;
+    const int colq = min(max(sx, 0), W - 1);
+    const bool inbx = sx >= 0 && sx < W;
+    int nd = 0, nv = 0, nb = 0;
+    for (int i0 = 0; i0 < cap / ROI_THREADS; i0 += 4) {        // cap / 1024 is 4, 16 or 64
+        int sy[4], syu[4], dep[4];
+        bool M[4], Mu[4], Ml[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int y = ((i0 + k) * ROI_THREADS >> roi_log2) + row0;
+            sy[k] = src_y(y), syu[k] = y > 0 ? src_y(y - 1) : -1;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            dep[k] = dimg[min(max(sy[k], 0), H - 1) * W + colq];
+            M[k] = mask_at(sy[k], sx), Mu[k] = mask_at(syu[k], sx), Ml[k] = mask_at(sy[k], sxl);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int y = ((i0 + k) * ROI_THREADS >> roi_log2) + row0;
+            const bool dv = inbx && sy[k] >= 0 && sy[k] < H && dep[k] > 0;
+            const bool band = (y > 0 && Mu[k] != M[k]) || (x > 0 && Ml[k] != M[k]);
+            nd += dv, nv += dv && M[k], nb += band;
+        }
+    }
+    const int lane = tid & (TGP_WAVE - 1), wave = tid / TGP_WAVE;
+#pragma unroll
+    for (int o = TGP_WAVE / 2; o > 0; o >>= 1) nd += __shfl_xor(nd, o), nv += __shfl_xor(nv, o), nb += __shfl_xor(nb, o);
+    if (lane == 0) red[0][wave] = nd, red[1][wave] = nv, red[2][wave] = nb;
+    __syncthreads();
+    if (tid < 3) {
+        int t = 0;
+#pragma unroll
+        for (int w = 0; w < ROI_WAVES; ++w) t += red[tid][w];
+        band_counts[j * 3 + tid] = t;
+    }
+}
+
+extern "C" int tgp_roi_band(const uint16_t *depth, const uint8_t *masks, const int64_t *mask_off, const int *mask_stride, const int *det_img,
+                            const int *window, int D, int H, int W, int roi_size, int *band_counts, const int *tables, const int *mask_val,
+                            tgp_stream_t stream)
+{
+    TGP_REQUIRE(depth && masks && mask_off && mask_stride && det_img && (window || tables) && band_counts);
+    TGP_REQUIRE(D > 0 && H > 0 && W > 0 && H < 32768 && W < 32768 && (int64_t)H * W < (1ll << 24));
+    const int lg = roi_log2_of(roi_size);
+    if (lg < 0) return TGP_EUNSUPPORTED;
+    hipLaunchKernelGGL(roi_band_kernel, dim3(D), dim3(ROI_THREADS), 0, tgp_hs(stream), depth, masks, mask_off, mask_stride, det_img, window, H,
+                       W, lg, tables, mask_val, band_counts);
+    return TGP_LAUNCH_RESULT();
+}
+
+extern "C" int tgp_roi_cloud_defor(const uint16_t *depth, const uint8_t *masks, const int64_t *mask_off, const int *mask_stride,
+                                   const int *det_img, const int *window, const float *camk, int D, int H, int W, int roi_size,
+                                   uint32_t *recs, int *counts, const int *tables, const int *mask_val, float cut_frac, const int *defor_on,
+                                   const uint32_t *drop_bits, int drop_words, tgp_stream_t stream)
+{
+    TGP_REQUIRE(depth && masks && mask_off && mask_stride && det_img && (window || tables) && camk && recs && counts && defor_on);
+    TGP_REQUIRE((cut_frac >= 0.f && cut_frac <= 1.f) || cut_frac == -1.f);
+    TGP_REQUIRE(drop_words >= 0 && drop_words <= 2048 && (drop_words == 0 || drop_bits));      // 2048 words = 65536 ranks
+    TGP_REQUIRE(D > 0 && H > 0 && W > 0 && H < 32768 && W < 32768 && (int64_t)H * W < (1ll << 24));
+    const int lg = roi_log2_of(roi_size);
+    if (lg < 0) return TGP_EUNSUPPORTED;
+    hipLaunchKernelGGL((roi_cloud_kernel<2, true>), dim3(D), dim3(ROI_THREADS), 0, tgp_hs(stream), depth, masks, mask_off, mask_stride,
+                       det_img, window, camk, H, W, lg, recs, counts, tables, mask_val, cut_frac, defor_on, drop_bits, drop_words);
     return TGP_LAUNCH_RESULT();
 }
 

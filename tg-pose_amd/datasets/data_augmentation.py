@@ -231,3 +231,39 @@ def view_inputs(records, n, device, operators):
                 drop_ratio=up(np.array([r['drop_ratio'] for r in records], dtype=np.float64)), drop_u=up(drop_u), boxes=up(boxes),
                 crop_max_try=crop.max_try_num, cutout_max_try=cut.max_try_num, crop_min_points=crop.min_num_points,
                 cutout_min_points=cut.min_num_points)
+
+
+def defor_2D(roi_mask, rand_r=2, rand_pro=0.3, rng=np.random):
+    """The reference's mask deformation (data_augmentation.py:319-342) on a GPU (S,S) or (1,S,S) 0/1 float32 mask, S in {64, 128,
+    256} -> the deformed (S,S) mask (a new tensor).  Draws as the reference: rng.rand(), then, when it is not > rand_pro and the
+    band is not empty, rng.choice(l, l // 2, replace=False).  rand_r is inert, as in the reference (it reaches cv2.erode / dilate
+    as their dst: one iteration).  Runs the training loader's kernels with the mask as a frame, identity source tables and unit
+    depth (tgp_roi_band, tgp_roi_cloud_defor without the cut) and scatters the records back; one read-back (the band size)."""
+    from .load_data import defor_draws
+    if not (torch.is_tensor(roi_mask) and roi_mask.is_cuda and roi_mask.dtype == torch.float32):
+        raise TypeError("defor_2D: roi_mask must be a float32 GPU tensor")
+    S = roi_mask.shape[-1]
+    if not (roi_mask.dim() in (2, 3) and roi_mask.shape[-2] == S and roi_mask.numel() == S * S and S in (64, 128, 256)):
+        raise ValueError("defor_2D: roi_mask must be (S,S) or (1,S,S) with S in {64, 128, 256}")
+    m = roi_mask.reshape(S, S)
+    if not bool(((m == 0) | (m == 1)).all()):
+        raise ValueError("defor_2D: roi_mask must hold only 0 and 1")
+    dev = m.device
+    i32 = lambda a: torch.as_tensor(a, dtype=torch.int32, device=dev)
+    mask8 = m.to(torch.uint8).contiguous().reshape(-1)
+    depth = torch.ones(1, S, S, dtype=torch.int16, device=dev)
+    tabs = torch.arange(S, dtype=torch.int32, device=dev).repeat(1, 2, 1).contiguous()
+    args = (depth, mask8, torch.zeros(1, dtype=torch.int64, device=dev), i32([1]), i32([0]), None)
+    band = ops.roi_band(*args, roi_size=S, tables=tabs, mask_val=i32([1])).cpu().numpy()
+    band[0, :2] = 2                   # the draws of a mask, not of an item: no validity test
+    on, bits = defor_draws(band, float(rand_pro), rng)
+    if not on[0]:
+        return m.clone()
+    rr = ops.roi_cloud(*args, torch.tensor([[1.0, 1.0, 0.0, 0.0]], device=dev), roi_size=S, tables=tabs, mask_val=i32([1]),
+                       cut_frac=-1.0, defor=(i32(on), i32(bits)))
+    cap = S * S
+    pix = (rr.recs[0] >> 16) & 0xffff
+    live = torch.arange(cap, device=dev) < rr.counts[0, 2]
+    out = torch.zeros(cap + 1, dtype=torch.float32, device=dev)
+    out.scatter_(0, torch.where(live, pix, cap).long(), 1.0)
+    return out[:cap].reshape(S, S)

@@ -20,8 +20,11 @@ given the same ``np.random`` state (tests/test_gpu_parity.py::test_train_loader_
 reference's two cloud augmentations (:333-350): ``PC_BasicAugment`` and the second view ``aug_pcl_in``, one ``tgp_augment`` launch for
 the batch (datasets/data_augmentation.py of this package), with the draws made on the host in the reference's order.
 
-Out of scope, as in DESIGN.md section 8: reading files, ``aug_bbox_DZI``'s draw and ``defor_2D`` on the mask (the caller's: its
-OpenCV erode / dilate cannot be pinned here), ``compute_pd`` (gudhi + persim)."""
+``roi_mask_pro`` adds the reference's mask deformation ``defor_2D`` (:280, datasets/data_augmentation.py:319-342): a band launch
+(``tgp_roi_band``: per item n_depth, the undeformed n_valid, the band size l), ONE read-back, the host's draws, then the deformed
+compaction (``tgp_roi_cloud_defor``) in place of ``tgp_roi_cloud_ex``.  ``dzi=True`` draws ``aug_bbox_DZI``
+(tools/dataset_utils.py:24-61) from the same ``rng`` (``aug_bbox_dzi``).  Out of scope, as in DESIGN.md section 8: reading
+files."""
 import numpy as np
 import torch
 
@@ -86,6 +89,72 @@ def source_tables(bbox_center, scale, img_size=256):
     return np.clip(np.stack([sx, sy]), -32768, 32767).astype(np.int32)       # (OpenCV stores the map as shorts)
 
 
+def aug_bbox_dzi(bbox, im_H, im_W, rng=np.random, dzi_type=None, scale_ratio=None, shift_ratio=None, pad_scale=None):
+    """aug_bbox_DZI (tools/dataset_utils.py:24-61) on get_bbox's window of bbox (y1, x1, y2, x2), as load_data.py:233-238 calls
+    it, drawing from ``rng``; None takes FLAGS.DZI_*.  Every branch of the reference, its roi10d ``x2 = min(max(x1, 0), im_W)``
+    included.  -> (bbox_center (cx, cy) float64, scale)"""
+    from ..config import FLAGS
+    dzi_type = FLAGS.DZI_TYPE if dzi_type is None else dzi_type
+    scale_ratio = FLAGS.DZI_SCALE_RATIO if scale_ratio is None else scale_ratio
+    shift_ratio = FLAGS.DZI_SHIFT_RATIO if shift_ratio is None else shift_ratio
+    pad_scale = FLAGS.DZI_PAD_SCALE if pad_scale is None else pad_scale
+    rmin, rmax, cmin, cmax = get_bbox(bbox)
+    x1, y1, x2, y2 = np.array([cmin, rmin, cmax, rmax]).copy()
+    cx, cy = 0.5 * (x1 + x2), 0.5 * (y1 + y2)
+    bh, bw = y2 - y1, x2 - x1
+    kind = dzi_type.lower()
+    if kind == "uniform":
+        sr = 1 + scale_ratio * (2 * rng.random_sample() - 1)
+        sh = shift_ratio * (2 * rng.random_sample(2) - 1)
+        center = np.array([cx + bw * sh[0], cy + bh * sh[1]])
+        scale = max(y2 - y1, x2 - x1) * sr * pad_scale
+    elif kind == "roi10d":
+        a, b = -0.15, 0.15
+        x1 += bw * (rng.rand() * (b - a) + a)
+        x2 += bw * (rng.rand() * (b - a) + a)
+        y1 += bh * (rng.rand() * (b - a) + a)
+        y2 += bh * (rng.rand() * (b - a) + a)
+        x1 = min(max(x1, 0), im_W)
+        x2 = min(max(x1, 0), im_W)               # sic: the reference clamps x1 into x2
+        y1 = min(max(y1, 0), im_H)
+        y2 = min(max(y2, 0), im_H)
+        center = np.array([0.5 * (x1 + x2), 0.5 * (y1 + y2)])
+        scale = max(y2 - y1, x2 - x1) * pad_scale
+    elif kind == "truncnorm":
+        raise NotImplementedError("DZI truncnorm not implemented yet.")
+    else:
+        center = np.array([cx, cy])
+        scale = max(y2 - y1, x2 - x1)
+    return center, min(scale, max(im_H, im_W)) * 1.0
+
+
+def defor_draws(band_counts, roi_mask_pro, rng=np.random):
+    """defor_2D's draws (data_augmentation.py:327-336) for a batch, from the band launch's (D,3) counts (n_depth, undeformed n_valid,
+    band size l), item by item: none for an item the validity tests (:259-264) abandon; else rng.rand(), and when it is not
+    > roi_mask_pro and l >= 1, rng.choice(l, l // 2, replace=False) (the band ranks set to 0).
+    -> (defor_on (D,) int32, drop_bits (D, words) int32: bit r of row d = band rank r dropped)"""
+    D = len(band_counts)
+    on = np.zeros(D, np.int32)
+    chosen = [None] * D
+    for d in range(D):
+        n_depth, n_valid, l = (int(v) for v in band_counts[d])
+        if n_depth <= 1 or n_valid <= 1:
+            continue
+        if rng.rand() > roi_mask_pro:
+            continue
+        if l < 1:
+            continue
+        chosen[d] = np.asarray(rng.choice(l, l // 2, replace=False), dtype=np.int64)
+        on[d] = 1
+    words = max([(int(band_counts[d][2]) + 31) // 32 for d in range(D) if on[d]] or [0])
+    flags = np.zeros((D, words * 32), np.uint8)
+    for d in range(D):
+        if on[d]:
+            flags[d, chosen[d]] = 1
+    bits = np.packbits(flags, axis=1, bitorder="little").reshape(D, words * 4).view("<u4").view(np.int32)
+    return on, np.ascontiguousarray(bits)
+
+
 def _selection(total, n_pts, rng):
     """_sample_points (:366-380) as indices: tile when short, the prefix of one permutation when long"""
     if total < n_pts:
@@ -95,23 +164,28 @@ def _selection(total, n_pts, rng):
     return np.arange(n_pts)
 
 
-def train_clouds(items, img_size=256, rng=np.random, device="cuda", min_points=50):
+def train_clouds(items, img_size=256, rng=np.random, device="cuda", min_points=50, roi_mask_pro=None, roi_mask_r=3, dzi=False):
     """items: list of dicts -- 'depth' (H,W) uint16 (load_depth's output), 'mask' (H,W) uint8 instance-id image (the reference reads
     ``cv2.imread(mask_path)[:, :, 2]``), 'inst_id' int, 'camK' (3,3) float32, and the window: 'bbox_center' (cx, cy) + 'scale' (the
     caller's aug_bbox_DZI draw) or 'bbox' (y1, x1, y2, x2) for the un-augmented window.  All frames share (H, W).
     -> list over items of (PC (2048,3), pcl_in (1024,3)) float32 GPU tensors, or None for an item the reference's __getitem__
     abandons and retries (:262-265 too few valid pixels, :288 fewer than 50 points after the cut).  The two permutations per item
-    are drawn from ``rng`` in the reference's order (item by item, 2048 first).  One 12-byte read-back per item (the counts)."""
+    are drawn from ``rng`` in the reference's order (item by item, 2048 first).  One 12-byte read-back per item (the counts).
+    dzi=True: the window is drawn by aug_bbox_dzi from each item's 'bbox' (FLAGS.DZI_*), all items first.  roi_mask_pro (a float;
+    None: no deformation, no draw): defor_2D on each item's mask after one more read-back (defor_draws, after the DZI draws);
+    roi_mask_r is inert, as in the reference (it reaches cv2.erode / dilate as their dst).  For one item the stream is the
+    reference's from aug_bbox_DZI on; for a batch, every item's DZI and deformation draws precede the first permutation."""
     dev = torch.device(device)
     if not items:
         return []
-    rr, counts = _roi_records(items, img_size, dev)
+    rr, counts = _roi_records(items, img_size, dev, rng, roi_mask_pro, roi_mask_r, dzi)
+    deformed = roi_mask_pro is not None
     D = len(items)
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     sel2k, sel1k = np.zeros((D, 2048), dtype=np.int32), np.zeros((D, 1024), dtype=np.int32)
     alive = []
     for d in range(D):
-        total = _item_total(counts[d], min_points)
+        total = _item_total(counts[d], min_points, deformed)
         if total is None:
             alive.append(False)
             continue
@@ -123,16 +197,29 @@ def train_clouds(items, img_size=256, rng=np.random, device="cuda", min_points=5
     return [(pc2k[d], pc1k[d]) if alive[d] else None for d in range(D)]
 
 
-def _roi_records(items, img_size, dev):
-    """the items' ROI clouds as records (one tgp_roi_cloud_ex launch) and their counts (one 12-byte read-back per item)"""
+def _roi_records(items, img_size, dev, rng=np.random, roi_mask_pro=None, roi_mask_r=3, dzi=False):
+    """the items' ROI clouds as records (one tgp_roi_cloud_ex launch) and their counts (one 12-byte read-back per item); with
+    roi_mask_pro, the band launch, its read-back, the deformation draws and one tgp_roi_cloud_defor launch instead"""
+    if roi_mask_pro is not None and not (isinstance(roi_mask_pro, (float, int)) and 0.0 <= float(roi_mask_pro) <= 1.0):
+        raise ValueError("roi_mask_pro must be None or a probability in [0, 1]")
+    if not (isinstance(roi_mask_r, (int, np.integer)) and roi_mask_r >= 0):
+        raise ValueError("roi_mask_r must be a non-negative int (it is inert, as in the reference)")
+    if dzi and any("bbox" not in it for it in items):
+        raise ValueError("dzi=True draws the window from each item's 'bbox'")
     H, W = items[0]["depth"].shape
-    tabs, camk, mval = [], [], []
-    for it in items:
+    for it in items:            # every item is checked before the first draw: a refused batch leaves rng untouched
         if it["depth"].shape != (H, W) or it["mask"].shape != (H, W) or it["depth"].dtype != np.uint16 or it["mask"].dtype != np.uint8:
             raise ValueError("every item needs a uint16 depth image and a uint8 instance mask of one common (H,W)")
         if not 0 < int(it["inst_id"]) < 256:
             raise ValueError("inst_id must be a non-zero byte value")
-        center, scale = (it["bbox_center"], it["scale"]) if "bbox_center" in it else window_without_dzi(it["bbox"], H, W)
+    tabs, camk, mval = [], [], []
+    for it in items:
+        if dzi:
+            center, scale = aug_bbox_dzi(it["bbox"], H, W, rng)                 # load_data.py:238
+        elif "bbox_center" in it:
+            center, scale = it["bbox_center"], it["scale"]
+        else:
+            center, scale = window_without_dzi(it["bbox"], H, W)
         tabs.append(source_tables(center, scale, img_size))
         K = np.asarray(it["camK"], dtype=np.float32)
         camk.append([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
@@ -141,19 +228,30 @@ def _roi_records(items, img_size, dev):
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     depth = up(np.stack([it["depth"] for it in items]).view(np.int16))
     masks = up(np.stack([it["mask"] for it in items]).reshape(-1))
-    rr = ops.roi_cloud(depth, masks, up(np.arange(D, dtype=np.int64) * (H * W)), up(np.ones(D, dtype=np.int32)),
-                       up(np.arange(D, dtype=np.int32)), None, up(np.asarray(camk, dtype=np.float32)), roi_size=img_size,
-                       tables=up(np.stack(tabs)), mask_val=up(np.asarray(mval, dtype=np.int32)), cut_frac=0.15)
+    args = (depth, masks, up(np.arange(D, dtype=np.int64) * (H * W)), up(np.ones(D, dtype=np.int32)), up(np.arange(D, dtype=np.int32)),
+            None)
+    tabs, mval = up(np.stack(tabs)), up(np.asarray(mval, dtype=np.int32))
+    defor = None
+    if roi_mask_pro is not None:
+        band = ops.roi_band(*args, roi_size=img_size, tables=tabs, mask_val=mval).cpu().numpy()      # the extra read-back
+        on, bits = defor_draws(band, float(roi_mask_pro), rng)                                         # :280
+        defor = (up(on), up(bits))
+    rr = ops.roi_cloud(*args, up(np.asarray(camk, dtype=np.float32)), roi_size=img_size, tables=tabs, mask_val=mval, cut_frac=0.15,
+                       defor=defor)
     return rr, rr.counts.cpu().numpy()
 
 
-def _item_total(counts, min_points):
-    """the cut cloud's point count, or None for an item the reference abandons"""
+def _item_total(counts, min_points, deformed=False):
+    """the cut cloud's point count, or None for an item the reference abandons.  deformed: the counts of tgp_roi_cloud_defor, whose
+    third entry is -(1 + the deformed point count) below 26 points (tgp_roi_cloud_ex writes -1 and the count is n_valid)"""
     n_depth, n_valid, total = (int(v) for v in counts)
     if n_depth <= 1 or n_valid <= 1:                           # :262-265
         return None
     if total < 0:
-        raise IndexError("index 25 is out of bounds for axis 0 with size %d" % n_valid)         # :281
+        n = -1 - total if deformed else n_valid
+        if n == 0:                                             # :272, np.min over the empty deformed cloud
+            raise ValueError("zero-size array to reduction operation minimum which has no identity")
+        raise IndexError("index 25 is out of bounds for axis 0 with size %d" % n)                # :281
     if total < min_points:                                     # :288
         return None
     return total
@@ -163,7 +261,8 @@ _IMAGE_KEYS = ("depth", "mask", "inst_id", "camK", "bbox_center", "scale", "bbox
 _POSE_KEYS = ("rotation", "translation", "fsnet_scale")
 
 
-def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min_points=50, operators=None, persistence=False):
+def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min_points=50, operators=None, persistence=False,
+                roi_mask_pro=None, roi_mask_r=3, dzi=False):
     """``train_clouds`` plus the reference's two augmentations (load_data.py:333-350): the batch the trainer's step reads.
 
     items: ``train_clouds``' dicts, each also carrying its labels 'rotation' (3,3), 'translation' (3,), 'fsnet_scale' (3,) (the
@@ -176,8 +275,9 @@ def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min
 
     Deviations from one reference __getitem__ after another (DESIGN.md section 8): crop and cutout draw all their attempts up front;
     the shuffle of an item whose operator is crop or cutout needs its kept count M, so it is drawn after ONE read-back of the counts
-    for the batch, after every other item's draws; the draws before generate_aug_parameters (aug_bbox_DZI, defor_2D) stay with the
-    caller.  A batch without an applied crop or cutout draws exactly the reference's stream.
+    for the batch, after every other item's draws; dzi=True / roi_mask_pro (see train_clouds) draw aug_bbox_DZI and defor_2D for
+    every item of the batch before the first item's generate_aug_parameters (without them those draws stay with the caller).  A
+    batch of one item without an applied crop or cutout draws exactly the reference's stream from aug_bbox_DZI through pc_sampler.
     Items the reference abandons (train_clouds' None) are left out, without draws; 'item_index' lists the items kept.
     -> dict of device tensors: pcl_in (B,1024,3), aug_pcl_in (B,1024,3), rotation (B,3,3), translation (B,3), fsnet_scale (B,3),
     the labels passed through, aug_flags (B,4) int32 {bb, rt, bc, pc}, aug_counts (B,2) int32 (M, accepted attempt or -1),
@@ -194,11 +294,12 @@ def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min
         raise ValueError("train_batch: the four operators of OPERATOR_NAMES are expected")
     if not items:
         raise ValueError("train_batch: no items")
-    rr, counts = _roi_records(items, img_size, dev)
+    rr, counts = _roi_records(items, img_size, dev, rng, roi_mask_pro, roi_mask_r, dzi)
+    deformed = roi_mask_pro is not None
     keep, sel2k, p1k, shuf, recs, names, defer = [], [], [], [], [], [], []
     params, draws, defor = [], [], []
     for d, it in enumerate(items):
-        total = _item_total(counts[d], min_points)
+        total = _item_total(counts[d], min_points, deformed)
         if total is None:
             continue
         keep.append(d)

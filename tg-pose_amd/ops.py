@@ -1632,11 +1632,8 @@ class RoiRecords:
         self.tables = tables
 
 
-def roi_cloud(depth, masks, mask_off, mask_stride, det_img, window, camk, roi_size=256, tables=None, mask_val=None, cut_frac=0.25):
-    """tgp_roi_cloud / tgp_roi_cloud_ex.  depth (I,H,W) int16-viewed uint16, masks flat uint8, mask_off (D,) int64, mask_stride /
-    det_img (D,) int32, window (D,3) int32 (None with tables), camk (I,4) float32 -- all on the GPU.  tables (D,2,roi_size) int32:
-    host-evaluated source pixels (the training loader's augmented windows); mask_val (D,) int32: mask byte to match (ground-truth
-    instance masks); cut_frac: the outlier cut's share of the diagonal (0.25 evaluation, 0.15 training).  -> RoiRecords"""
+def _roi_args(depth, masks, mask_off, mask_stride, det_img, window, camk, roi_size, tables, mask_val, who):
+    """the checks roi_cloud and roi_band share -> (I, H, W, D)"""
     if not (depth.is_cuda and depth.dtype in (torch.int16, torch.uint16) and depth.dim() == 3 and depth.is_contiguous()):
         raise TypeError("depth must be a contiguous (I,H,W) 16-bit GPU tensor")
     if not (masks.is_cuda and masks.dtype in (torch.uint8, torch.bool) and masks.is_contiguous()):
@@ -1644,22 +1641,56 @@ def roi_cloud(depth, masks, mask_off, mask_stride, det_img, window, camk, roi_si
     if not (mask_off.is_cuda and mask_off.dtype == torch.int64 and mask_off.is_contiguous()):
         raise TypeError("mask_off must be a contiguous int64 GPU tensor")
     _i32(mask_stride, "mask_stride"), _i32(det_img, "det_img")
-    _f32(camk, "camk", 2)
     I, H, W = depth.shape
     D = det_img.numel()
     if window is None and tables is None:
-        raise ValueError("roi_cloud: a window or source tables are needed")
+        raise ValueError("%s: a window or source tables are needed" % who)
     if window is not None and _i32(window, "window").shape != (D, 3):
-        raise ValueError("roi_cloud: window must be (D,3)")
+        raise ValueError("%s: window must be (D,3)" % who)
     if tables is not None and _i32(tables, "tables").shape != (D, 2, roi_size):
-        raise ValueError("roi_cloud: tables must be (D,2,roi_size)")
+        raise ValueError("%s: tables must be (D,2,roi_size)" % who)
     if mask_val is not None and _i32(mask_val, "mask_val").numel() != D:
-        raise ValueError("roi_cloud: mask_val must be (D,)")
-    if mask_off.numel() != D or mask_stride.numel() != D or camk.shape != (I, 4) or not camk.is_contiguous():
-        raise ValueError("roi_cloud: inconsistent shapes")
+        raise ValueError("%s: mask_val must be (D,)" % who)
+    if mask_off.numel() != D or mask_stride.numel() != D or (camk is not None and (camk.shape != (I, 4) or not camk.is_contiguous())):
+        raise ValueError("%s: inconsistent shapes" % who)
+    return I, H, W, D
+
+
+def roi_band(depth, masks, mask_off, mask_stride, det_img, window, roi_size=256, tables=None, mask_val=None):
+    """tgp_roi_band: the band launch of the mask deformation (defor_2D).  Arguments as roi_cloud.  -> (D,3) int32 GPU tensor:
+    depth-valid ROI pixels, valid points with the undeformed mask, band size l (pixels whose mask differs from the up or left
+    ROI neighbour's)"""
+    _, H, W, D = _roi_args(depth, masks, mask_off, mask_stride, det_img, window, None, roi_size, tables, mask_val, "roi_band")
+    out = torch.empty(D, 3, device=depth.device, dtype=torch.int32)
+    check(_lib.lib().tgp_roi_band(_p(depth), _p(masks), _p(mask_off), _p(mask_stride), _p(det_img), _p(window), D, H, W, roi_size,
+                                  _p(out), _p(tables), _p(mask_val), _stream(depth)), "tgp_roi_band")
+    return out
+
+
+def roi_cloud(depth, masks, mask_off, mask_stride, det_img, window, camk, roi_size=256, tables=None, mask_val=None, cut_frac=0.25,
+              defor=None):
+    """tgp_roi_cloud / tgp_roi_cloud_ex.  depth (I,H,W) int16-viewed uint16, masks flat uint8, mask_off (D,) int64, mask_stride /
+    det_img (D,) int32, window (D,3) int32 (None with tables), camk (I,4) float32 -- all on the GPU.  tables (D,2,roi_size) int32:
+    host-evaluated source pixels (the training loader's augmented windows); mask_val (D,) int32: mask byte to match (ground-truth
+    instance masks); cut_frac: the outlier cut's share of the diagonal (0.25 evaluation, 0.15 training).
+    defor = (defor_on (D,) int32, drop_bits (D, words) int32 viewed as uint32 bitmaps over band ranks): the mask deformation
+    (tgp_roi_cloud_defor); cut_frac may then be -1 (no cut).  -> RoiRecords"""
+    _f32(camk, "camk", 2)
+    I, H, W, D = _roi_args(depth, masks, mask_off, mask_stride, det_img, window, camk, roi_size, tables, mask_val, "roi_cloud")
+    if defor is not None:
+        on, bits = defor
+        _i32(on, "defor_on"), _i32(bits, "drop_bits")
+        if on.numel() != D or bits.dim() != 2 or bits.shape[0] != D or bits.shape[1] > 2048:
+            raise ValueError("roi_cloud: defor must be (defor_on (D,), drop_bits (D, words <= 2048))")
+        if not (0.0 <= cut_frac <= 1.0 or cut_frac == -1.0):
+            raise ValueError("roi_cloud: cut_frac must be in [0, 1] or -1 (no cut)")
     recs = torch.empty(D, roi_size * roi_size, device=depth.device, dtype=torch.int32)
     counts = torch.empty(D, 3, device=depth.device, dtype=torch.int32)
-    if tables is None and mask_val is None and cut_frac == 0.25:
+    if defor is not None:
+        check(_lib.lib().tgp_roi_cloud_defor(_p(depth), _p(masks), _p(mask_off), _p(mask_stride), _p(det_img), _p(window), _p(camk), D,
+                                             H, W, roi_size, _p(recs), _p(counts), _p(tables), _p(mask_val), float(cut_frac), _p(on),
+                                             _p(bits), bits.shape[1], _stream(depth)), "tgp_roi_cloud_defor")
+    elif tables is None and mask_val is None and cut_frac == 0.25:
         check(_lib.lib().tgp_roi_cloud(_p(depth), _p(masks), _p(mask_off), _p(mask_stride), _p(det_img), _p(window), _p(camk), D, H, W,
                                        roi_size, _p(recs), _p(counts), _stream(depth)), "tgp_roi_cloud")
     else:
