@@ -57,6 +57,14 @@ _DEFAULTS = dict(
     DZI_TYPE="uniform",  # :18
     DZI_SCALE_RATIO=0.25,  # :19
     DZI_SHIFT_RATIO=0.25,  # :20
+    # the training loop (trainer/RL_TDA.py RL_TDA_train / train, the checkpoint file it writes)
+    batch_size=24,       # :59
+    save_every=1,        # :136 (epochs between checkpoints; the last epoch is always saved)
+    log_every=100,       # :137 (batches between log lines)
+    model_save="output/models/distr",  # :138 (the checkpoints' directory)
+    resume=0,            # :140
+    resume_model="",     # :141
+    RL_model_path="",    # :143
 )
 
 

@@ -352,3 +352,211 @@ def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min
     if persistence:
         db["pdh1"], db["pdh2"] = ops.persistence_images(pcl_in)
     return db
+
+
+# ------------------------------------------------------------------------------------------------- the training loop's batches
+CATEGORY_KEYS = ("points_category", "pdh1_category", "pdh2_category")
+
+
+def epoch_batches(n, batch_size, gen=None, shuffle=True, drop_last=False, rank=0, world_size=1):
+    """One epoch's item indices in batches, as DataLoader(shuffle=True, generator=gen) orders them: the loader's iterator draws its
+    base seed from ``gen`` (None: torch's default CPU generator), then RandomSampler permutes with ``gen`` -- or, without one, with a
+    generator seeded by one more draw.  Data parallel, as DistributedSampler splits: the
+    order is padded with its own head to a multiple of world_size and rank r takes every world_size-th index from r, so every rank
+    has the same number of batches (the ranks' ``gen`` must be seeded alike)."""
+    if n <= 0 or batch_size <= 0:
+        raise ValueError("epoch_batches: no items or a batch size below 1")
+    if shuffle:
+        torch.empty((), dtype=torch.int64).random_(generator=gen)                # the iterator's base seed
+        if gen is None:
+            seed = int(torch.empty((), dtype=torch.int64).random_().item())
+            order = torch.randperm(n, generator=torch.Generator().manual_seed(seed)).tolist()
+        else:
+            order = torch.randperm(n, generator=gen).tolist()
+    else:
+        order = list(range(n))
+    if world_size > 1:
+        total = -(-n // world_size) * world_size
+        order = (order + order[: total - n])[rank::world_size]
+    out = [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+    if drop_last and out and len(out[-1]) < batch_size:
+        out.pop()
+    return out
+
+
+def fill_batch(indices, n, build):
+    """The reference's refill (load_data.py:262-265, 288): an item its __getitem__ abandons is replaced by the item at the next index,
+    (index + 1) % n, and so on, so the batch keeps its size.  build(list of item indices) -> (kept positions within that list, part)
+    or None when every item was abandoned.  Rounds: every position still open is built again at its next index, after the round
+    before it.  -> (parts [(batch positions, part)], the item index each position ended with)"""
+    at = list(indices)
+    open_ = list(range(len(at)))
+    parts, rounds = [], 0
+    while open_:
+        if rounds > n:
+            raise ValueError("fill_batch: every item was abandoned")
+        got = build([at[p] for p in open_])
+        kept = [] if got is None else [int(k) for k in got[0]]
+        if kept:
+            parts.append(([open_[k] for k in kept], got[1]))
+        keep = set(kept)
+        open_ = [p for k, p in enumerate(open_) if k not in keep]
+        for p in open_:
+            at[p] = (at[p] + 1) % n
+        rounds += 1
+    return parts, at
+
+
+def _merge(parts, B):
+    """the parts of fill_batch as one batch in position order"""
+    if len(parts) == 1:
+        return parts[0][1]
+    pos = [p for ps, _ in parts for p in ps]
+    order = np.argsort(np.asarray(pos))
+    dbs = [db for _, db in parts]
+    out = {}
+    for k, v in dbs[0].items():
+        if torch.is_tensor(v):
+            cat = torch.cat([db[k] for db in dbs])
+            out[k] = cat[torch.from_numpy(order).to(cat.device)].contiguous()
+        elif isinstance(v, list):
+            cat = [x for db in dbs for x in db[k]]
+            out[k] = [cat[j] for j in order]
+        else:
+            out[k] = v
+    assert len(pos) == B
+    return out
+
+
+class TrainBatches(object):
+    """The training loop's batch source (the reference's DataLoader over PoseDataset, shuffle=True): ``items`` are host item dicts in
+    train_batch's format (reading the files stays with the caller); each epoch draws an order (epoch_batches) and yields
+    train_batch's device batches of ``batch_size`` items.
+
+    * An item train_batch abandons is replaced by the next index's item (fill_batch), so a batch keeps batch_size items; the
+      replacements' draws follow the batch's other draws.  'item_index' lists the item each row came from.
+    * category_tables = (points (6,P,3), pdh1 (6,2500), pdh2 (6,2500)) -- the reference's obj_model/*.npy -- adds the batch's
+      points_category / pdh1_category / pdh2_category, gathered by cat_id on the device.
+    * persistence=True computes pdh1 / pdh2 with ops.persistence_images: the loop is then bounded by that kernel (about 440 ms per
+      32-item batch on an MI355X against a ~16 ms step).
+    * prefetch=True (a CUDA device): the iterator's ``prefetch()`` -- RL_TDA_train calls it after enqueuing a step -- makes the next
+      batch's draws on the host and enqueues its kernels on a side stream, so they overlap the step; the next ``next()`` orders the
+      current stream after them.  The draws happen in the same order as without prefetch (every draw of batch i+1 after every draw
+      of step i), so the two loops are bit-identical.
+
+    * dzi=True passes on train_batch's refusals: source_tables raises ValueError for a drawn window whose warp is not separable
+      (rare; the affine map's rounding noise moves a tie), which ends the loop.
+    * The epoch order comes from a generator of its own, seeded with ``seed + epoch`` (as DistributedSampler does): no augmentation
+      draw, refill or subsample draw can move it, so under data parallel every rank computes the same order in every epoch and
+      rank / world_size (default: torch.distributed's) give each rank its own slice of it.  seed=None draws the seed once, at
+      construction, from ``gen`` (before any augmentation draw; ranks with alike-seeded generators agree); pass one seed to all
+      ranks otherwise.  The epoch counts up at every iteration; set_epoch(e) sets it (a resumed run).
+    rng (NumPy) and gen (torch CPU generator; None: torch's default) feed train_batch."""
+
+    def __init__(self, items, batch_size, rng=np.random, gen=None, device="cuda", prefetch=True, shuffle=True, drop_last=False,
+                 persistence=False, dzi=False, roi_mask_pro=None, roi_mask_r=3, category_tables=None, min_points=50, operators=None,
+                 img_size=256, rank=None, world_size=None, seed=None):
+        import torch.distributed as dist
+        if not items:
+            raise ValueError("TrainBatches: no items")
+        self.items, self.batch_size = list(items), int(batch_size)
+        self.rng, self.gen, self.device = rng, gen, torch.device(device)
+        self.prefetch = bool(prefetch) and self.device.type == "cuda"
+        self.shuffle, self.drop_last = shuffle, drop_last
+        self.kw = dict(img_size=img_size, device=self.device, min_points=min_points, operators=operators, persistence=persistence,
+                       roi_mask_pro=roi_mask_pro, roi_mask_r=roi_mask_r, dzi=dzi)
+        on = dist.is_available() and dist.is_initialized()
+        self.world_size = int(world_size if world_size is not None else (dist.get_world_size() if on else 1))
+        self.rank = int(rank if rank is not None else (dist.get_rank() if on else 0))
+        self.tables = None
+        if category_tables is not None:
+            tabs = [torch.as_tensor(np.asarray(t, dtype=np.float32)) for t in category_tables]
+            if len(tabs) != 3 or any(t.shape[0] != tabs[0].shape[0] for t in tabs):
+                raise ValueError("category_tables: (points, pdh1, pdh2), one row per category")
+            self.tables = [t.to(self.device) for t in tabs]
+            if self.device.type == "cuda":
+                torch.cuda.current_stream(self.device).synchronize()     # the side stream reads them from now on
+        self._side = None
+        if seed is None:
+            seed = int(torch.empty((), dtype=torch.int64).random_(generator=gen).item())
+        self.seed, self.epoch = int(seed), 0
+
+    def __len__(self):
+        n = -(-len(self.items) // self.world_size)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def build(self, indices):
+        """one batch of the items at ``indices``, refilled, on the current stream"""
+        n = len(self.items)
+
+        def one(idx):
+            try:
+                db = train_batch([self.items[i] for i in idx], rng=self.rng, gen=self.gen, **self.kw)
+            except ValueError as e:
+                if "every item was abandoned" in str(e):
+                    return None
+                raise
+            return db["item_index"].cpu().numpy(), db
+
+        parts, at = fill_batch(indices, n, one)
+        db = _merge(parts, len(indices))
+        db["item_index"] = torch.as_tensor(np.asarray(at, dtype=np.int64)).to(self.device)
+        if self.tables is not None:
+            cid = db["cat_id"].reshape(-1).long()
+            for k, t in zip(CATEGORY_KEYS, self.tables):
+                db[k] = t.index_select(0, cid)
+        return db
+
+    def side_stream(self):
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.device)
+        return self._side
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def order(self, epoch):
+        """epoch ``epoch``'s batches of item indices for this rank (no draw from rng or gen)"""
+        g = torch.Generator().manual_seed(self.seed + int(epoch))
+        return epoch_batches(len(self.items), self.batch_size, g, self.shuffle, self.drop_last, self.rank, self.world_size)
+
+    def __iter__(self):
+        batches = self.order(self.epoch)
+        self.epoch += 1
+        return _EpochBatches(self, batches)
+
+
+class _EpochBatches(object):
+    def __init__(self, src, batches):
+        self.src, self.batches, self.at, self.ready = src, batches, 0, None
+
+    def __iter__(self):
+        return self
+
+    def prefetch(self):
+        """build the next batch on the side stream now (a no-op without prefetch, at the epoch's end, or when one is ready)"""
+        if not self.src.prefetch or self.ready is not None or self.at >= len(self.batches):
+            return
+        side = self.src.side_stream()
+        with torch.cuda.stream(side):
+            db = self.src.build(self.batches[self.at])
+            done = torch.cuda.Event()
+            done.record(side)
+        self.at += 1
+        self.ready = (db, done)
+
+    def __next__(self):
+        if self.ready is not None:
+            db, done = self.ready
+            self.ready = None
+            cur = torch.cuda.current_stream(self.src.device)
+            cur.wait_event(done)
+            for v in db.values():
+                if torch.is_tensor(v):
+                    v.record_stream(cur)            # allocated on the side stream, used and freed on this one
+            return db
+        if self.at >= len(self.batches):
+            raise StopIteration
+        db = self.src.build(self.batches[self.at])
+        self.at += 1
+        return db

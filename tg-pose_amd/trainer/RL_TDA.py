@@ -1,5 +1,5 @@
-"""Drop-in for the step of ``trainer/RL_TDA.py``: ``RT_TDA_Trainer.RL_TDA_train_step`` (:110-200) and the loop body around it
-(:205-226) on the HIP path.
+"""Drop-in for ``trainer/RL_TDA.py``: ``RT_TDA_Trainer.RL_TDA_train_step`` (:110-200), the loop ``RL_TDA_train`` (:202-263) and
+``train`` (:265-267), and the checkpoint methods ``load_old_model_params`` (:88-97) / ``init_RL_TDA_model`` (:64-86), on the HIP path.
 
 One step is: net1 = PoseNet9D() on the cloud with gradients (tgpose_amd.autograd: HIP forward and backward), net2 =
 PoseNet9D(only_encoder=True) on the augmented cloud under ``no_grad`` (the fused training-mode forward of tgpose_amd.engine:
@@ -13,10 +13,15 @@ The optimizer and its schedule are the reference's (:58-62 ``set_optimizer_sched
 ranger2020: its step is one HIP launch over every parameter with a gradient) and flat_and_anneal (tgpose_amd.tools.torch_utils.solver.
 lr_scheduler), built by tgpose_amd.tools.training_utils from FLAGS; ``setup`` still accepts any ``torch.optim`` optimizer / scheduler.
 
-Not rebuilt (SURVEY section 8 scope): the epoch loop, logging, checkpointing -- the data-parallel hot path is the step.
+``RL_TDA_train`` replays the captured step (one capture per batch shape; a batch of another shape -- an epoch's smaller last batch
+-- runs the eager ``train_iteration``), applies the loop's NaN skip after the replay through ``finish_step(total=...)``, and, when
+the batch source can prefetch (datasets.load_data.TrainBatches), enqueues the next batch's preparation before it reads the step's
+NaN flag.  It logs the reference's line every FLAGS.log_every batches and writes the reference's checkpoint file
+(``rl_tda_model_{e:02d}.pth``, tensors on the CPU) on rank 0 only.
 """
 import math
 import os
+import time
 
 import torch
 
@@ -62,6 +67,79 @@ def total_loss(loss_dict):
     return (terms * _TOTAL_W[key]).sum()
 
 
+
+# ----------------------------------------------------------------------------------------------------------- the loop's files
+CHECKPOINT_KEYS = ('epoch', 'net1_state_dict', 'net2_state_dict', 'optimizer_state_dict', 'scheduler_state_dict')   # (:258-262)
+
+
+def checkpoint_path(epoch):
+    """the loop's checkpoint file (:263): ``rl_tda_model_{epoch:02d}.pth`` in FLAGS.model_save"""
+    return os.path.join(str(FLAGS.model_save), 'rl_tda_model_{:02d}.pth'.format(epoch))
+
+
+def saves_checkpoint(epoch, total_epoch):
+    """(:257) a checkpoint after every FLAGS.save_every-th epoch (0-based ``epoch``) and after the last one"""
+    return (epoch + 1) % FLAGS.save_every == 0 or (epoch + 1) == total_epoch
+
+
+# the log line of :229-248 as data: (text in front of the value, value) -- the values are read back in one copy
+_LOG_FIELDS = (('L:', 'total'), (', con_l:', 'RL_loss'), (',recon_1:', 'recon_1_loss'), (',recon_consist:', 'recon_consistency_loss'),
+               (', TDA_l:', 'TDA'), (', rot_l:', 'Rot1+Rot2'), (', size_l:', 'Size'), (', trans_l:', 'Tran'), (', h1_l:', 'TDA_h1'),
+               (', h2_l:', 'TDA_h2'), (', h1_l_cate:', 'TDA_h1_cate'), (', h2_l_cate:', 'TDA_h2_cate'),
+               (',R_DCD_cate_pred:', 'R_DCD_cate_pred'), (',Prop_sym:', 'Prop_sym'))
+
+
+def log_values(total, loss_dict):
+    """the fourteen numbers of the log line, in its order, with one device-to-host copy"""
+    tda = loss_dict['TDA_loss']
+    names = list(tda)
+    dev = [total.reshape(-1)[:1]] + [loss_dict[k].reshape(-1)[:1] for k in ('RL_loss', 'recon_1_loss', 'recon_consistency_loss')]
+    dev += [tda[k].reshape(-1)[:1] for k in names]
+    host = torch.cat([v.detach().float().to(dev[0].device) for v in dev]).cpu().tolist()
+    t = dict(zip(names, host[4:]))
+    val = {'total': host[0], 'RL_loss': host[1], 'recon_1_loss': host[2], 'recon_consistency_loss': host[3],
+           'TDA': sum(host[4:]), 'Rot1+Rot2': t['Rot1'] + t['Rot2']}
+    return [val[k] if k in val else t[k] for _, k in _LOG_FIELDS]
+
+
+def log_line(epoch, batch, values):
+    """the reference's log line (:229-248) for stage 2: the same labels, separators, order and four decimals"""
+    return 'Stage {} Epoch {} Batch {} '.format(2, epoch, batch) + ''.join('{}{:.4f}'.format(label, v) for (label, _), v in zip(_LOG_FIELDS, values))
+
+
+def rl_stage_renamed(rl_net1_state, own_keys):
+    """init_RL_TDA_model's rule (:76-84): every key of an RL-stage net1 that names ``face_enc`` (and not ``ph_pred``) is taken
+    as the same key with ``face_all`` -- if this net1 has that key; every other key is dropped.  -> {new key: tensor}"""
+    own = set(own_keys)
+    out = {}
+    for k, v in rl_net1_state.items():
+        if 'face_enc' in k and 'ph_pred' not in k:
+            nk = k.replace('face_enc', 'face_all')
+            if nk in own:
+                out[nk] = v
+    return out
+
+
+def _to_cpu(obj):
+    """a state dict with every tensor copied to the host (a view is copied alone, not the flat buffer behind it)"""
+    if torch.is_tensor(obj):
+        return obj.detach().cpu().clone() if obj.device.type == 'cpu' else obj.detach().cpu()
+    if isinstance(obj, dict):
+        return type(obj)((k, _to_cpu(v)) for k, v in obj.items())
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_to_cpu(v) for v in obj)
+    return obj
+
+
+def _rank0():
+    import torch.distributed as dist
+    return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+
+
+def _signature(db):
+    return tuple(sorted((k, tuple(v.shape), v.dtype) for k, v in db.items() if torch.is_tensor(v)))
+
+
 class RT_TDA_Trainer(object):
     def __init__(self, logger=None, device=None):
         self.logger = logger
@@ -73,6 +151,8 @@ class RT_TDA_Trainer(object):
         self._graphed = None          # the last GraphedStep captured over net1 (its static .grad buffers must stay in place)
         self._buckets = None          # shard.GradBuckets of a graphed_step(overlap=True): p.grad are views into its flat buffers
         self._exchanged = False       # set by a replay whose gradient exchange has already run, cleared by finish_step
+        self._loop = None             # (batch signature, step) of the capture RL_TDA_train replays
+        self._skipped = False         # whether the last train_iteration skipped its step (NaN total)
 
     def setup(self, mode, optimizer=None, scheduler=None):
         self.init_network(mode)
@@ -214,7 +294,8 @@ class RT_TDA_Trainer(object):
             self.optimizer.zero_grad(set_to_none=self._graphed is None and self._buckets is None)
         _, loss_dict = self.RL_TDA_train_step(db)
         total = total_loss(loss_dict)
-        if self.loss_is_nan(total):
+        self._skipped = self.loss_is_nan(total)
+        if self._skipped:
             print('Found nan in total loss')
             return total.detach(), loss_dict
         total.backward()
@@ -240,9 +321,14 @@ class RT_TDA_Trainer(object):
         N = static['pcl_in'].shape[1]
         cut = EncoderCut() if (overlap and "nocut" not in _debug) else None
         pending = []
+        terms = {}
 
         def step_fn(samples):
             _, loss_dict = self.RL_TDA_train_step(static, sample_idx=samples, cut=cut)
+            # the loss terms of the captured run stay allocated: every replay rewrites them (the loop's log line reads them)
+            terms.clear()
+            terms.update({k: (v.detach() if torch.is_tensor(v) else {kk: vv.detach() for kk, vv in v.items()})
+                          for k, v in loss_dict.items()})
             return total_loss(loss_dict)
 
         between = after = None
@@ -273,4 +359,117 @@ class RT_TDA_Trainer(object):
                         static[k].copy_(v.reshape(static[k].shape), non_blocking=True)
             return g(sample_idx)
         step.graph = g
+        step.loss_dict = terms
         return step
+
+    # ------------------------------------------------------------------------------------------------------------ the loop
+    def _loop_step(self, db, overlap):
+        """the captured step RL_TDA_train replays for batches of db's shapes; None for a batch of another shape (it runs eagerly).
+        The capture's warm-up runs both forwards twice and draws subsamples: the BatchNorm buffers and torch's CPU generator are put
+        back as they were, so the loop's state equals the eager loop's."""
+        sig = _signature(db)
+        if self._loop is None:
+            rng = torch.get_rng_state()
+            keep = [{k: v.detach().clone() for k, v in net.state_dict().items()} for net in (self.net1, self.net2)]
+            step = self.graphed_step(db, overlap=overlap)
+            for net, sd in zip((self.net1, self.net2), keep):
+                net.load_state_dict(sd)
+            torch.set_rng_state(rng)
+            self._loop = (sig, step)
+        return self._loop[1] if self._loop[0] == sig else None
+
+    def RL_TDA_train(self, train_dataloader, total_epoch, graph=True, overlap=None):
+        """trainer/RL_TDA.py:202-263.  train_dataloader: any iterable of batch dicts (datasets.load_data.TrainBatches, a
+        DataLoader, a list).  Per batch: the step, then -- unless its total is NaN -- clip_grad_norm_(net1, 5), the optimizer, the
+        scheduler.  Every FLAGS.log_every batches (1-based) the reference's log line goes to self.logger; after the epochs that
+        saves_checkpoint names, checkpoint_path(e) gets the reference's five keys with every tensor on the CPU.  Rank 0 alone logs
+        and writes; the ranks skip a NaN step together (loss_is_nan).
+
+        graph=True replays the step captured at the first batch (graphed_step; overlap: its data-parallel form, by default when
+        more than one rank runs) and applies the NaN skip in finish_step(total=...); a batch of another shape runs the eager
+        train_iteration.  graph=False runs train_iteration for every batch.  When the iterator has ``prefetch()``, it is called
+        after the step is enqueued and before its NaN flag is read: the next batch is prepared while the step runs."""
+        import torch.distributed as dist
+        rank0 = _rank0()
+        if overlap is None:
+            overlap = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        for e in range(total_epoch):
+            epoch_s_time = time.time()
+            batches = iter(train_dataloader)
+            prefetch = getattr(batches, 'prefetch', None)
+            for i, data in enumerate(batches, 1):
+                iter_s_time = time.time()
+                step = self._loop_step(data, overlap) if graph else None
+                if step is not None:
+                    total = step(data)
+                    if prefetch is not None:
+                        prefetch()
+                    stepped = self.finish_step(total=total)
+                    loss_dict = step.loss_dict
+                else:
+                    total, loss_dict = self.train_iteration(data)
+                    if prefetch is not None:
+                        prefetch()
+                    stepped = not self._skipped
+                if stepped and i % FLAGS.log_every == 0 and rank0 and self.logger is not None:
+                    self.logger.info(log_line(e, i, log_values(total, loss_dict)))
+                    self.logger.info('The average running time of every {} is {:.4f} sec'.format(FLAGS.log_every, time.time() - iter_s_time))
+                del total, loss_dict, data          # an eager step's autograd graph must not outlive it
+            if rank0 and self.logger is not None:
+                self.logger.info('>>>>>>>>----------Epoch {:02d} train finish,time is {:02f} sec---------<<<<<<<<'.format(
+                    e, time.time() - epoch_s_time))
+            if rank0 and saves_checkpoint(e, total_epoch):
+                self.save_checkpoint(e)
+
+    def train(self, train_dataloader, mode):
+        """(:265-267) the reference hard-codes 150 epochs, FLAGS.total_epoch's default"""
+        if mode == 'RL_TDA':
+            self.RL_TDA_train(train_dataloader, FLAGS.total_epoch)
+
+    def checkpoint(self, epoch):
+        """the reference's checkpoint dict (:258-262) with every tensor copied to the host"""
+        return _to_cpu({'epoch': epoch, 'net1_state_dict': self.net1.state_dict(), 'net2_state_dict': self.net2.state_dict(),
+                        'optimizer_state_dict': self.optimizer.state_dict(), 'scheduler_state_dict': self.scheduler.state_dict()})
+
+    def save_checkpoint(self, epoch, path=None):
+        path = checkpoint_path(epoch) if path is None else path
+        d = os.path.dirname(path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        torch.save(self.checkpoint(epoch), path)
+        return path
+
+    def load_old_model_params(self, path, mode):
+        """(:88-97) net1, net2, the optimizer and -- when the file has it -- the scheduler from a checkpoint of RL_TDA_train (this
+        package's or the reference's; tensors saved on any device are read on the host first).  Everything is copied into the
+        existing tensors: parameters, BatchNorm buffers and the static .grad buffers keep their storage, and Ranger flattens the
+        loaded state again at its next step (its buffer is outside the graph).  net2's captured forward, however, reads the
+        kernel-ready copy of its weights packed when the step was captured (PoseNet9D.packed), which a load cannot reach: the loop's
+        capture is dropped and RL_TDA_train captures again at its next batch (a step the caller captured with graphed_step must be
+        captured again as well)."""
+        checkpoint = torch.load(path, map_location='cpu')
+        self._loop = None
+        if mode == 'RL_TDA':
+            if self.net1 is not None:
+                self.net1.load_state_dict(checkpoint['net1_state_dict'])
+            if self.net2 is not None:
+                self.net2.load_state_dict(checkpoint['net2_state_dict'])
+            self.optimizer.load_state_dict(checkpoint['optimizer_state_dict'])
+            if 'scheduler_state_dict' in checkpoint:
+                self.scheduler.load_state_dict(checkpoint['scheduler_state_dict'])
+        return checkpoint.get('epoch')
+
+    def init_RL_TDA_model(self, model_path):
+        """(:64-86) net1 from an RL-stage checkpoint: its ``face_enc`` weights become this net1's ``face_all`` ones
+        (rl_stage_renamed); the rest of net1 keeps its values"""
+        if self.logger is not None:
+            self.logger.info('[RT_TDA] loading model from {} '.format(model_path))
+        checkpoint = torch.load(model_path, map_location='cpu')
+        self._loop = None                   # (as in load_old_model_params)
+        own = self.net1.state_dict()
+        upd = rl_stage_renamed(checkpoint['net1_state_dict'], own.keys())
+        for k in upd:
+            print('update {} to {}'.format(k.replace('face_all', 'face_enc'), k))
+        own.update(upd)
+        self.net1.load_state_dict(own)
+        return sorted(upd)
