@@ -1011,6 +1011,36 @@ int64_t tgp_pd_workspace_bytes(void);
 int tgp_pd_max_points(void);
 int tgp_persistence(const tgp_pd_args *args, tgp_stream_t stream);
 
+/* ---- gradients with respect to the point coordinates (csrc/xyz_bwd.hip): no float atomics, bit-repeatable ----
+ * tgp_gconv_dirgrad: d(unit neighbour direction) ddir (B, n, k, 3) of HSlayer_surface.graph_conv (proj == NULL) or HS_layer.graph_conv
+ * (proj (B, n, 8C) rows = [centre | support], slots = tgp_gconv_hs_fwd_slots' record or NULL: recomputed) from d g (B, n, C) rows:
+ * for every (support s, channel c) whose first maximum over the neighbours j has theta > 0, d g[c] / 7 (x the winner's support value)
+ * * sdn[:, s*C + c] lands on that j.  S == 7, k <= 64, 7 * C * 5 bytes of LDS <= 60 KB: TGP_EUNSUPPORTED otherwise. */
+int tgp_gconv_dirgrad(const float *xyz, const int32_t *idx, const float *proj, int ldp, const float *sdn, const float *dg, int ldg,
+                      const uint8_t *slots, int B, int n, int k, int S, int C, float *ddir, tgp_stream_t stream);
+/* tgp_neighbor_dirs: get_neighbor_direction_norm's forward: unit (B, n, k, 3) = F.normalize(x[idx] - x), unnormed (same, or NULL) the
+ * difference itself; idx (B, n, k) ids in [0, n). */
+int tgp_neighbor_dirs(const float *xyz, const int32_t *idx, int B, int n, int k, float *unit, float *unnormed, tgp_stream_t stream);
+/* tgp_dirs_to_xyz: backward of get_neighbor_direction_norm (gcn3d.py:48-58): ddir (B, n, k, 3) = d F.normalize(x[idx] - x), dun (same
+ * shape, or NULL) = d of the unnormalised difference -> dxyz (B, n, 3) (accumulate != 0: added to its contents).  Reverse lists of idx:
+ * rev_global == 0: tgp_reverse_graph's (rptr (B*n + 1), rent = (i << 6) | j); rev_global == 1: tgp_child_lists' over idx viewed as
+ * (B, n*k) with R = n (rent = global entry (b*n + i) * k + j). */
+int tgp_dirs_to_xyz(const float *xyz, const int32_t *idx, const int32_t *rptr, const int32_t *rent, int rev_global, const float *ddir,
+                    const float *dun, int B, int n, int k, float *dxyz, int accumulate, tgp_stream_t stream);
+/* tgp_center_bwd: backward of tgp_center: dpoints (B, n, 3) = dxyz + (dmean - sum_i dxyz_i) / n; dmean (B, 3) or NULL. */
+int tgp_center_bwd(const float *dxyz, const float *dmean, int B, int n, float *dpoints, tgp_stream_t stream);
+/* tgp_bn_eval_bwd: backward of y = act((x - mean) / sqrt(var + eps) * gamma + beta) with FIXED mean / var (eval-mode BatchNorm on the
+ * running statistics; the forward is tgp_bn_apply): dx, dgamma, dbeta (C).  workspace: tgp_bn_eval_workspace_floats(C) floats. */
+int64_t tgp_bn_eval_workspace_floats(int C);
+int tgp_bn_eval_bwd(const float *dy, int lddy, const float *x, int ld, int64_t rows, int C, const float *mean, const float *var, float eps,
+                    const float *gamma, const float *beta, int act, float slope, float *dx, int lddx, float *dgamma, float *dbeta,
+                    float *workspace, tgp_stream_t stream);
+/* tgp_bn_eval_bwd_pooled: the same for max over each object's points (tgp_colmax_arg with the running statistics): dpool (objects, C),
+ * argrow (objects, C) global winning rows -> dense dx (objects*rows_per_obj, C), dgamma, dbeta.  workspace: objects * C floats. */
+int tgp_bn_eval_bwd_pooled(const float *dpool, int ldp, const int32_t *argrow, int lda, const float *x, int ld, int objects, int rows_per_obj,
+                           int C, const float *mean, const float *var, float eps, const float *gamma, const float *beta, int act, float slope,
+                           float *dx, int lddx, float *dgamma, float *dbeta, float *workspace, tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

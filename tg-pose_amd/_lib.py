@@ -350,6 +350,15 @@ SIGNATURES = {
     "tgp_roi_band": (c_int, [c_vp] * 6 + [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "tgp_roi_cloud_defor": (c_int, [c_vp] * 7 + [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_int, c_vp]),
     "tgp_cloud_sample": (c_int, [c_vp] * 5 + [c_int, c_int, c_int, ctypes.c_uint64, c_vp, c_vp]),
+    "tgp_gconv_dirgrad": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "tgp_dirs_to_xyz": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp]),
+    "tgp_neighbor_dirs": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "tgp_center_bwd": (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
+    "tgp_bn_eval_workspace_floats": (c_i64, [c_int]),
+    "tgp_bn_eval_bwd": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_f32, c_vp, c_vp, c_int, c_f32, c_vp, c_int, c_vp, c_vp,
+                                c_vp, c_vp]),
+    "tgp_bn_eval_bwd_pooled": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_f32, c_vp, c_vp, c_int,
+                                       c_f32, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
 }
 
 ABI_VERSION = 8

@@ -234,6 +234,7 @@ class _FeatConsumersFactored(Function):
         (ptr1, idx1), (ptr2, idx2) = lists1, lists2
         ctx.save_for_backward(fine, fm23, fm4, ptr1, idx1, ptr2, idx2, Wb, Wc, *Was)
         ctx.tails, ctx.has_bias, ctx.nfeat = tails, [b is not None for b in bs], fm01.shape[2]
+        ctx.tail_shape = tuple(tail.shape)
         return tuple(outs)
 
     @staticmethod
@@ -261,6 +262,20 @@ class _FeatConsumersFactored(Function):
                 dfine = dx if dx is not None else dfine
                 part.append((dWa, db))
             off += n
+        dtail = None
+        if need[3]:
+            # the tail's differentiable columns: the centred xyz that Pose_Ts reads (PoseNet9D.py:63) after the one-hot; one small GEMM
+            # per layer that reads them, d xyz = g_i Wa_i[:, xyz columns], added in layer order
+            B, N, lt = ctx.tail_shape
+            n_cls = min(kt for kt in ctx.tails)
+            dtail = torch.zeros(B, N, lt, device=fine.device, dtype=torch.float32)
+            for g, Wa, kt in zip(gs, Was, ctx.tails):
+                if g is None or kt <= n_cls:
+                    continue
+                c0 = ctx.nfeat + n_cls
+                Wx = _pad4(Wa[:, c0:c0 + kt - n_cls]).t().contiguous()          # (4, n): the xyz columns' weights and a zero row
+                dx = ops.linear_rows(g.reshape(M, -1).contiguous(), Wx)
+                dtail[:, :, n_cls:kt] += dx.view(B, N, -1)[:, :, : kt - n_cls]
         dfm23, dWb, _ = _linear_backward(fm23, Wb, dP1, need[1], need_w, False)
         dfm4, dWc, _ = _linear_backward(fm4, Wc, dP2, need[2], need_w, False)
         grads, off = [], 0
@@ -271,7 +286,7 @@ class _FeatConsumersFactored(Function):
                 dW = torch.cat([dWa[:, :256], dWb[off:off + n], dWc[off:off + n], dWa[:, 256:256 + kt]], 1)
             grads += [dW, db]
             off += n
-        return (dfine, dfm23, dfm4, None, None, None, None, None) + tuple(grads)
+        return (dfine, dfm23, dfm4, dtail, None, None, None, None) + tuple(grads)
 
 
 FACTORED = os.environ.get("TGP_TRAIN_FACTORED", "1") != "0"     # the layers over the concat buffer factored over the up-sampling
@@ -344,6 +359,48 @@ class _BNActPool(Function):
         return dx.view(B, n, C), dg, db, None, None, None
 
 
+class _BNActEval(Function):
+    """act(BatchNorm1d_eval(x)) over rows: the running statistics, no buffer moves (tgp_bn_apply forward, tgp_bn_eval_bwd backward)"""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, rm, rv, act, slope, eps):
+        x = x.contiguous()
+        ctx.save_for_backward(x, rm, rv, gamma, beta)
+        ctx.act, ctx.slope, ctx.eps = act, slope, eps
+        return ops.bn_apply(x, rm, rv, gamma, beta, eps, act, slope)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, rm, rv, gamma, beta = ctx.saved_tensors
+        dx, dg, db = ops.bn_eval_bwd(dy.contiguous(), x, rm, rv, gamma, beta, ctx.eps, ctx.act, ctx.slope)
+        return dx, dg, db, None, None, None, None, None
+
+
+class _BNActPoolEval(Function):
+    """max over each object's points of act(BatchNorm1d_eval(x)): x (B, n, C) -> (B, C)"""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, rm, rv, act, slope, eps):
+        x = x.contiguous()
+        B, n, C = x.shape
+        pooled, arg = ops.colmax_arg(x, B, n, bn=(rm, rv, gamma, beta), act=act, slope=slope, eps=eps)
+        ctx.save_for_backward(x, rm, rv, gamma, beta, arg)
+        ctx.act, ctx.slope, ctx.eps = act, slope, eps
+        return pooled
+
+    @staticmethod
+    def backward(ctx, dpool):
+        x, rm, rv, gamma, beta, arg = ctx.saved_tensors
+        B, n, C = x.shape
+        dx, dg, db = ops.bn_eval_bwd_pooled(dpool.contiguous(), arg, x, n, rm, rv, gamma, beta, ctx.eps, ctx.act, ctx.slope)
+        return dx.view(B, n, C), dg, db, None, None, None, None, None
+
+
+def _eval_bn(bn):
+    """does this BatchNorm normalise with its running statistics (eval mode)?"""
+    return bn is not None and not bn.training and bn.track_running_stats and bn.running_mean is not None
+
+
 def _running(bn):
     """the module's buffers for ops.bn_train(running=...): moved by the statistics kernel (was: four torch launches per module).
     momentum=None (torch's cumulative moving average, 1 / num_batches_tracked) is not implemented by that kernel and is refused
@@ -374,6 +431,8 @@ def _tap_seq(kind, value):
 
 
 def bn_act(x, bn, act=1, slope=0.0):
+    if _eval_bn(bn):
+        return _BNActEval.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, act, slope, bn.eps)
     y = _BNAct.apply(x, bn.weight, bn.bias, bn, act, slope)
     if TAPS is not None:
         _tap_seq("act", y.detach().cpu())
@@ -381,21 +440,31 @@ def bn_act(x, bn, act=1, slope=0.0):
 
 
 def bn_act_pool(x, bn, act=1, slope=0.0):
+    if _eval_bn(bn):
+        return _BNActPoolEval.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, act, slope, bn.eps)
     return _BNActPool.apply(x, bn.weight, bn.bias, bn, act, slope)
 
 
 class _GConvSurface(Function):
+    """rev: reverse lists of idx for the points' gradient (computed in the backward when None)"""
+
     @staticmethod
-    def forward(ctx, xyz, idx, sdn, C):
+    def forward(ctx, xyz, idx, sdn, C, rev=None):
+        xyz = xyz.contiguous()
         g = ops.gconv_surface(xyz, idx, sdn.contiguous(), S, C)
         ctx.save_for_backward(xyz, idx, sdn)
-        ctx.C = C
+        ctx.C, ctx.rev = C, rev
         return g
 
     @staticmethod
     def backward(ctx, dg):
         xyz, idx, sdn = ctx.saved_tensors
-        return None, None, ops.gconv_surface_bwd(xyz, idx, sdn.contiguous(), dg.contiguous(), S, ctx.C), None
+        dg = dg.contiguous()
+        dxyz = None
+        if ctx.needs_input_grad[0]:     # the receptive field's unit directions (gcn3d.py:48-58, :96) -> d xyz
+            dxyz = ops.dirs_to_xyz(xyz, idx, ops.gconv_dirgrad(xyz, idx, sdn.contiguous(), dg, S, ctx.C), rev=ctx.rev)
+        dsdn = ops.gconv_surface_bwd(xyz, idx, sdn.contiguous(), dg, S, ctx.C) if ctx.needs_input_grad[2] else None
+        return dxyz, None, dsdn, None, None
 
 
 # The backward of the graph layers without float atomics (csrc/graph_bwd.hip): reverse neighbour lists + two dense passes.  0: the
@@ -410,6 +479,7 @@ class _GConvHS(Function):
     def forward(ctx, xyz, idx, proj, sdn, C, rev=None):
         proj = proj.contiguous()
         sdn_c = sdn.contiguous()
+        xyz = xyz.contiguous()
         ctx.slots = None
         if rev is not None and ops.gconv_gather_ok(C, idx.shape[2], proj, sdn_c):
             # the forward kernel that also records every maximum's slot: the backward then starts from them (no second walk over
@@ -425,12 +495,17 @@ class _GConvHS(Function):
     def backward(ctx, dg):
         xyz, idx, proj, sdn = ctx.saved_tensors
         dg = dg.contiguous()
+        dxyz = None
+        if ctx.needs_input_grad[0]:
+            # the receptive field's unit directions -> d xyz; from the forward's slots, read before the gather pass below consumes them
+            ddir = ops.gconv_dirgrad(xyz, idx, sdn.contiguous(), dg, S, ctx.C, proj=proj, slots=ctx.slots)
+            dxyz = ops.dirs_to_xyz(xyz, idx, ddir, rev=ctx.rev)
         if ctx.rev is not None and ops.gconv_gather_ok(ctx.C, idx.shape[2], proj, dg):
             slots, ctx.slots = ctx.slots, None            # (a second backward over the same graph recomputes them)
             dproj, dsdn = ops.gconv_hs_bwd_gather(xyz, idx, ctx.rev, proj, sdn.contiguous(), dg, S, ctx.C, slots=slots)
         else:
             dproj, dsdn = ops.gconv_hs_bwd(xyz, idx, proj, sdn.contiguous(), dg.contiguous(), S, ctx.C)
-        return None, None, dproj, dsdn, None, None
+        return dxyz, None, dproj, dsdn, None, None
 
 
 class _NbrMaxMean(Function):
@@ -460,18 +535,29 @@ class _PoolMax(Function):
         fm = fm.contiguous()
         v, f = ops.pool(xyz, fm, idx, sample, kpool=kpool)
         idx_s = idx[:, sample.long(), :kpool].contiguous()
-        ctx.save_for_backward(fm, idx_s)
+        ctx.save_for_backward(fm, idx_s, sample)
         ctx.rev = ops.reverse_graph(idx_s, fm.shape[1]) if SCATTER_FREE and fm.requires_grad else None
-        ctx.mark_non_differentiable(v)
+        ctx.n = xyz.shape[1]
+        if not ctx.needs_input_grad[0]:
+            ctx.mark_non_differentiable(v)       # vertices_pool = vertices[:, sample_idx] (gcn3d.py:243): differentiable with xyz
         return v, f
 
     @staticmethod
-    def backward(ctx, _dv, df):
-        fm, idx_s = ctx.saved_tensors
-        df = df.contiguous()
-        if ctx.rev is not None and ops.nbrmax_gather_ok(fm.shape[2], fm, df):
-            return None, ops.nbrmax_bwd_gather(fm, idx_s, ctx.rev, df), None, None, None
-        return None, ops.nbrmax_bwd(fm, idx_s, df), None, None, None
+    def backward(ctx, dv, df):
+        fm, idx_s, sample = ctx.saved_tensors
+        dxyz = dfm = None
+        if ctx.needs_input_grad[0] and dv is not None:
+            # the sampled rows are distinct (a randperm prefix): one term per element of d xyz
+            B = dv.shape[0]
+            rows = sample.to(torch.int32).view(1, -1).expand(B, -1).contiguous()
+            dxyz = ops.gather_rows_bwd(dv.contiguous(), rows, ctx.n)
+        if ctx.needs_input_grad[1]:
+            df = df.contiguous()
+            if ctx.rev is not None and ops.nbrmax_gather_ok(fm.shape[2], fm, df):
+                dfm = ops.nbrmax_bwd_gather(fm, idx_s, ctx.rev, df)
+            else:
+                dfm = ops.nbrmax_bwd(fm, idx_s, df)
+        return dxyz, dfm, None, None, None
 
 
 class _GatherRows(Function):
@@ -532,7 +618,36 @@ class _HeadPost(Function):
     def backward(ctx, *grads):
         green, red = ctx.saved_tensors
         dg, dr, dt = ops.head_post_bwd(green, red, grads)
-        return dg, dr, dt, None
+        dmean = grads[4] if ctx.needs_input_grad[3] else None       # Pred_T = T + mean (PoseNet9D.py:65)
+        return dg, dr, dt, dmean
+
+
+class _Center(Function):
+    """points - points.mean(1) and the mean (PoseNet9D.py:37,48): tgp_center forward, tgp_center_bwd backward"""
+
+    @staticmethod
+    def forward(ctx, points):
+        return ops.center(points.contiguous())
+
+    @staticmethod
+    def backward(ctx, dxyz, dmean):
+        return ops.center_bwd(dxyz.contiguous(), dmean)
+
+
+class _NeighborDirs(Function):
+    """get_neighbor_direction_norm (gcn3d.py:48-58): unit directions to the neighbours and the unnormalised differences"""
+
+    @staticmethod
+    def forward(ctx, xyz, idx):
+        xyz = xyz.contiguous()
+        unit, raw = ops.neighbor_dirs(xyz, idx, unnormed=True)
+        ctx.save_for_backward(xyz, idx)
+        return unit, raw
+
+    @staticmethod
+    def backward(ctx, dunit, draw):
+        xyz, idx = ctx.saved_tensors
+        return ops.dirs_to_xyz(xyz, idx, dunit.contiguous(), dun=draw.contiguous()), None
 
 
 class _NormalizeDirs(Function):
@@ -612,7 +727,9 @@ def _surface(layer, xyz, graphs, kmax):
     C = layer.kernel_num
     sdn = _NormalizeDirs.apply(layer.directions)
     pre = getattr(getattr(graphs, "g", None), "prefix", "")
-    g = _tap(pre + "conv_0.g", _GConvSurface.apply(xyz, graphs("conv_0.rf", 0, xyz, kmax), sdn, C))
+    idx_rf = graphs("conv_0.rf", 0, xyz, kmax)
+    rev_rf = _reverse(graphs, idx_rf, xyz.shape[1]) if xyz.requires_grad else None
+    g = _tap(pre + "conv_0.g", _GConvSurface.apply(xyz, idx_rf, sdn, C, rev_rf))
     idx_orl = graphs("conv_0.orl_xyz", 0, xyz, kmax)
     out = _orl(layer, g, idx_orl, _reverse(graphs, idx_orl, xyz.shape[1]))
     return _tap(pre + "conv_0.out", _LinearEpi.apply(_pad4(xyz), _pad4(_w2(layer.STE_layer)), None, None, out, False))   # STE(xyz) + out
@@ -684,12 +801,14 @@ def encoder(enc, xyz, obj_id, sample_idx, graphs, kmax=20, n_cls=6):
         near1 = graphs.g.get("up_1", lambda: ops.nn1(xyz, v1)).view(B, N)
         near2 = graphs.g.get("up_2", lambda: ops.nn1(xyz, v2)).view(B, N)
         one_hot = torch.zeros(B, n_cls, device=dev).scatter_(1, obj_id.view(-1, 1).long(), 1)
-        tail = torch.cat([one_hot.unsqueeze(1).expand(B, N, n_cls), xyz, torch.zeros(B, N, FEAT_LD - FEAT_C - 3, device=dev)], 2)
+        pad = torch.zeros(B, N, FEAT_LD - FEAT_C - 3, device=dev)
         base = torch.arange(B, device=dev, dtype=torch.int32).view(B, 1)
         near1g, near2g = near1 + base * v1.shape[1], near2 + base * v2.shape[1]
         # children of every coarse point: the backward of the up-sampling (here and in the factored layers) is a segment sum
         lists1 = ops.child_lists(near1, v1.shape[1]) if SCATTER_FREE or FACTORED else None
         lists2 = ops.child_lists(near2, v2.shape[1]) if SCATTER_FREE or FACTORED else None
+    # (outside no_grad: Pose_Ts reads the xyz columns, PoseNet9D.py:63 -- differentiable when the points are)
+    tail = torch.cat([one_hot.unsqueeze(1).expand(B, N, n_cls), xyz, pad], 2)
     up1, up2 = (lists1, lists2) if SCATTER_FREE else (None, None)
     ups = [_GatherRows.apply(fm2, near1, up1), _GatherRows.apply(fm3, near1, up1), _GatherRows.apply(fm4, near2, up2)]
     if not FACTORED:
@@ -761,18 +880,24 @@ def proj_global(enc, feat):
 
 def posenet_forward(net, points, obj_id, train_keys, sample_idx=None, inject=None, record=None, kmax=20, n_cls=6, cut=None,
                     enable_proj=False):
-    """PoseNet9D.forward (PoseNet9D.py:33-91) with autograd; net is the drop-in module (training mode).
+    """PoseNet9D.forward (PoseNet9D.py:33-91) with autograd; net is the drop-in module.  Training mode: batch-statistics BatchNorm.
+    Eval mode (points that require grad): BatchNorm on the running statistics, dropout the identity, no buffer moves; without
+    train_keys the PH predictor and the decoder, which reach none of the six eval outputs, are not run.  Points that require grad
+    are centred with autograd and receive d points from every layer that reads them.
     cut: an EncoderCut to split the backward at the encoder's output `feat` (GraphedStep's two-segment form: everything after
     `feat` is differentiated first, the encoder afterwards, so that the late layers' gradients can travel meanwhile)."""
     B, N, _ = points.shape
-    if B < 2:
+    if B < 2 and net.training:
         raise ValueError("Expected more than 1 value per channel when training, got input size [%d, 256]" % B)
     if sample_idx is None:
         sample_idx = engine.draw_sample_idx(N)
     points = points.contiguous().float()
-    with torch.no_grad():                      # the clouds are data: no gradient flows to them
-        xyz, mean = ops.center(points)         # bit-identical to the reference's centring (kNN indices depend on it)
-        mean = mean.unsqueeze(1)
+    if points.requires_grad and torch.is_grad_enabled():
+        xyz, mean = _Center.apply(points)      # tgp_center's bits forward; d points = d xyz - mean(d xyz) + d mean / N
+    else:
+        with torch.no_grad():                  # a cloud that is data: exactly the former path
+            xyz, mean = ops.center(points)     # bit-identical to the reference's centring (kNN indices depend on it)
+    mean = mean.unsqueeze(1)
     if net.only_encoder:
         face = net.face_enc
         graphs = _GraphSource(points.device, inject, record, "face_enc.encoder.")
@@ -781,6 +906,8 @@ def posenet_forward(net, points, obj_id, train_keys, sample_idx=None, inject=Non
         xd = feat_consumers_factored(parts, [(_w2(dec0), dec0.bias)])[0] if parts is not None else None
         fo = feat[:, :, :FEAT_C] if parts is None else feat
         return dict(feat_global=proj_global(face.encoder, fo) if enable_proj else colmax(fo), recon=decoder(face.decoder, feat, None, xd))
+    # the PH predictor and the decoder reach the outputs only with train_keys; training mode runs them anyway (their BatchNorms move)
+    full = train_keys or net.training
     face = net.face_all
     graphs = _GraphSource(points.device, inject, record, "face_all.encoder.")
     feat, parts = encoder(face.encoder, xyz, obj_id.to(points.device), sample_idx, graphs, kmax, n_cls)
@@ -794,17 +921,21 @@ def posenet_forward(net, points, obj_id, train_keys, sample_idx=None, inject=Non
     # buffer with d feat accumulated inside their dx GEMMs (_FeatConsumers)
     w1 = _w2
     dec0 = face.decoder.conv1d_block[0]
-    layers = [(w1(face.ph_pred.conv_5[0]), None), (w1(dec0), dec0.bias), (w1(net.rot_green.conv1), net.rot_green.conv1.bias),
-              (w1(net.rot_red.conv1), net.rot_red.conv1.bias), (w1(net.ts.conv1), net.ts.conv1.bias)]
-    x5, xd, xg, xr, xt = feat_consumers(feat, layers) if parts is None else feat_consumers_factored(parts, layers)
-    back, h1, h2 = ph_predictor(face.ph_pred, feat, x5)
-    recon = decoder(face.decoder, feat, back, xd)
+    layers = [(w1(face.ph_pred.conv_5[0]), None), (w1(dec0), dec0.bias)] if full else []
+    layers += [(w1(net.rot_green.conv1), net.rot_green.conv1.bias), (w1(net.rot_red.conv1), net.rot_red.conv1.bias),
+               (w1(net.ts.conv1), net.ts.conv1.bias)]
+    xs = feat_consumers(feat, layers) if parts is None else feat_consumers_factored(parts, layers)
+    xg, xr, xt = xs[-3:]
+    if full:
+        back, h1, h2 = ph_predictor(face.ph_pred, feat, xs[0])
+        recon = decoder(face.decoder, feat, back, xs[1])
     green = point_head(net.rot_green, feat, xg)
     red = point_head(net.rot_red, feat, xr)
     ts = point_head(net.ts, feat, xt)
     out = dict()
     if train_keys:
-        out["recon"] = recon + mean
+        # (a mean that requires grad: its gradient is the sum over each object's points, tgp_colsum_objects)
+        out["recon"] = add_row_bias(recon, mean[:, 0]) if mean.requires_grad else recon + mean
     (out["p_green_R"], out["p_red_R"], out["f_green_R"], out["f_red_R"], out["Pred_T"], out["Pred_s"]) = _HeadPost.apply(
         green, red, ts, mean[:, 0].contiguous())
     if train_keys:

@@ -15,6 +15,13 @@ from . import gcn3d
 from .gcn3d import _Packable, _xyz
 
 
+def _refuse_points_grad(vertices, who):
+    """the eval-mode sub-modules run the fused no-autograd kernels: a cloud that requires grad is refused rather than silently detached"""
+    if vertices.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("%s in eval mode does not differentiate with respect to the points; call PoseNet9D (either mode) "
+                                  "or this module in training mode, or detach the points" % who)
+
+
 def _pad_rows(x, C):
     """(B, N, C) rows -> (B, N, FEAT_LD) zero padded (the row stride every layer over the concat buffer reads)"""
     return torch.nn.functional.pad(x.float(), (0, engine.FEAT_LD - C))
@@ -78,6 +85,7 @@ class Face_Enc(_WithBuffers):
                                                 tgp_autograd._GraphSource(dev, None, None, ""), self.neighbor_num, FLAGS.obj_c)
             feat = feat[:, :, : engine.FEAT_C]
             return feat, (self.project(feat) if enable_proj else feat.permute(0, 2, 1))
+        _refuse_points_grad(vertices, "Face_Enc")
         conv = self._packed(lambda: engine.pack_encoder(engine._dev_sd(self.state_dict(), dev), "", dev))
         pk = type("EncPack", (), dict(conv=conv))
         xyz = vertices.detach().float().contiguous()
@@ -175,6 +183,7 @@ class FaceNet(_WithBuffers):
             recon = tgp_autograd.decoder(self.decoder, featp, back, xd)
             f = featp[:, :, : engine.FEAT_C]
             return recon, f, (self.encoder.project(f) if enable_proj else f.permute(0, 2, 1)), h1, h2
+        _refuse_points_grad(vertices, "FaceNet")
         pk = self._packed(lambda: engine.Packed(self.state_dict(), dev, face="", with_heads=False))
         xyz = vertices.detach().float().contiguous()
         N = xyz.shape[1]

@@ -6,7 +6,8 @@ names (face_all / face_enc, rot_green, rot_red, ts) and therefore state-dict key
 ``load_state_dict(checkpoint['net1_state_dict'])`` (evaluater/RT_TDA_Evaluater.py:39) works
 unchanged.  The forward is the fused HIP pipeline of ``tgpose_amd.engine`` in eval mode and in training
 mode under ``no_grad`` (batch-statistics BatchNorm, dropout: the trainer's net2), and the differentiable
-one of ``tgpose_amd.autograd`` in training mode with gradients recorded (net1); extra keyword-only
+one of ``tgpose_amd.autograd`` in training mode with gradients recorded (net1) and, in either mode, for a cloud
+``points`` that requires grad (the gradients with respect to the points, as the reference's autograd gives them); extra keyword-only
 arguments let tests pin the random subsample and inject / record neighbour graphs.
 """
 import torch
@@ -58,8 +59,10 @@ class PoseNet9D(_WithBuffers):
                 eval_outputs_only=None):
         if not points.is_cuda:
             raise RuntimeError("tgpose_amd.PoseNet9D runs on the GPU only (no CPU fallback); move inputs to cuda")
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            # differentiable path: the same kernels composed as torch.autograd.Functions (tgpose_amd/autograd.py)
+        grad_pts = torch.is_grad_enabled() and points.requires_grad
+        if grad_pts or (self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
+            # differentiable path: the same kernels composed as torch.autograd.Functions (tgpose_amd/autograd.py); a cloud that requires
+            # grad takes it in eval mode too (BatchNorm on the running statistics), and receives d points
             from ... import autograd as tgp_autograd
             return tgp_autograd.posenet_forward(self, points, obj_id, bool(FLAGS.train), sample_idx, inject, record,
                                                 FLAGS.gcn_n_num, FLAGS.obj_c, cut=cut, enable_proj=bool(enable_proj))

@@ -7,11 +7,12 @@ being recorded and a feature input or a layer parameter requires them, the call 
 ``torch.autograd.Function``s of ``tgpose_amd.autograd`` (HIP forward AND HIP backward) and returns a
 graph-attached tensor; otherwise the fused no-autograd kernels of ``tgpose_amd.engine`` run.  The
 layers hold no BatchNorm / dropout, so ``.train()`` / ``.eval()`` make no difference to them.
-Gradients with respect to the point coordinates (``vertices``) are not produced -- the trainer's
-clouds are data (trainer/RL_TDA.py:111-116) -- and a ``vertices`` that requires grad is refused.
+A ``vertices`` that requires grad (with grad mode on) is differentiated as in the reference: through the
+receptive fields' unit directions (get_neighbor_direction_norm), HSlayer_surface's STE convolution of the
+points and Pool_layer's ``vertices[:, sample_idx]``; the kNN selections carry no gradient, as ``topk``'s.
 
-Reference: get_neighbor_index :14, get_nearest_index :26, indexing_neighbor_new :38,
-HSlayer_surface :60, HS_layer :115, get_ORL_global :210, Pool_layer :219.
+Reference: get_neighbor_index :14, get_nearest_index :26, indexing_neighbor_new :38, get_neighbor_direction_norm :48,
+HSlayer_surface :60, HS_layer :115, get_receptive_fields :188, get_ORL_global :210, Pool_layer :219.
 """
 import math
 
@@ -27,8 +28,9 @@ def _tracked(*tensors):
 
 
 def _xyz(vertices):
+    """the points as the kernels read them: on the autograd graph when they require grad, else detached"""
     if vertices.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError("gradients with respect to the point coordinates are not implemented (the clouds are data)")
+        return vertices.float().contiguous()
     return vertices.detach().float().contiguous()
 
 
@@ -62,21 +64,58 @@ def get_nearest_index(target, source):
 
 
 def indexing_neighbor_new(tensor, index):
-    """(bs, v, C), (bs, m, k) -> (bs, m, k, C): row gather (C a multiple of 4); differentiable in `tensor`."""
+    """(bs, v, C), (bs, m, k) -> (bs, m, k, C): row gather; differentiable in `tensor`.  C not a multiple of 4 (the points, C = 3): the
+    rows are gathered zero-padded to the next multiple and the padding is cut off."""
     bs, v, C = tensor.shape
     _, m, k = index.shape
     flat = index.reshape(bs, m * k).to(torch.int32).contiguous()
+    C4 = (C + 3) // 4 * 4
     if _tracked(tensor):
         from ... import autograd as tgp_autograd
-        return tgp_autograd._GatherRows.apply(tensor.float(), flat).view(bs, m, k, C)
-    out = torch.empty(bs, m * k, C, device=tensor.device, dtype=torch.float32)
-    ops.gather_rows(tensor.detach().float().contiguous(), flat, out)
-    return out.view(bs, m, k, C)
+        src = tensor.float()
+        if C4 != C:
+            src = torch.nn.functional.pad(src, (0, C4 - C))
+        return tgp_autograd._GatherRows.apply(src, flat).view(bs, m, k, C4)[..., :C]
+    src = tensor.detach().float().contiguous()
+    if C4 != C:
+        src = torch.nn.functional.pad(src, (0, C4 - C)).contiguous()
+    out = torch.empty(bs, m * k, C4, device=tensor.device, dtype=torch.float32)
+    ops.gather_rows(src, flat, out)
+    out = out.view(bs, m, k, C4)
+    return out if C4 == C else out[..., :C]
+
+
+def get_neighbor_direction_norm(vertices, neighbor_index, return_unnormed=False):
+    """(bs, v, 3), (bs, v, k) -> unit directions F.normalize(vertices[idx] - vertices) (bs, v, k, 3) [, the unnormalised differences];
+    differentiable in `vertices` (tgp_neighbor_dirs forward, tgp_dirs_to_xyz backward)"""
+    bs, v, _ = vertices.shape
+    idx = neighbor_index.to(torch.int32).contiguous()
+    if idx.dim() != 3 or idx.shape[0] != bs or idx.shape[1] != v:
+        raise ValueError("get_neighbor_direction_norm: neighbor_index must be (bs, %d, k)" % v)
+    if _tracked(vertices):
+        from ... import autograd as tgp_autograd
+        unit, raw = tgp_autograd._NeighborDirs.apply(vertices.float(), idx)
+        return (unit, raw) if return_unnormed else unit
+    out = ops.neighbor_dirs(vertices.detach().float().contiguous(), idx, unnormed=return_unnormed)
+    return out
+
+
+def get_receptive_fields(neighbor_num, vertices, feature_map=None, mode="RF-F"):
+    """-> (unit directions (bs, v, k, 3), neighbour index (bs, v, k) int64): the neighbours by feature distance ('RF-F') or by point
+    distance ('RF-P'), as gcn3d.py:188-207"""
+    assert mode in ["RF-F", "RF-P"]
+    if mode == "RF-F":
+        assert feature_map is not None, "The feature_map should be provided if 'RF-F' is used"
+        feat = feature_map
+    else:
+        feat = vertices
+    neighbor_index = get_neighbor_index(feat, neighbor_num)
+    return get_neighbor_direction_norm(vertices, neighbor_index), neighbor_index
 
 
 def get_ORL_global(feature, vertices, neighbor_num):
     """(bs, v, C), (bs, v, 3) -> (bs, v, C): neighbour max, mean over points, repeated per point; differentiable in `feature`."""
-    idx = ops.knn_xyz(_xyz(vertices), neighbor_num)
+    idx = ops.knn_xyz(vertices.detach().float().contiguous(), neighbor_num)
     if _tracked(feature):
         from ... import autograd as tgp_autograd
         g = tgp_autograd._NbrMaxMean.apply(feature.float(), idx)
@@ -118,7 +157,7 @@ class HSlayer_surface(_Packable):
 
     def forward(self, vertices, neighbor_num):
         xyz = _xyz(vertices)
-        if _tracked(*self.parameters()):
+        if _tracked(xyz, *self.parameters()):
             from ... import autograd as tgp_autograd
             return tgp_autograd._surface(self, xyz, _SeamGraphs(), neighbor_num)
         idx = ops.knn_xyz(xyz, neighbor_num)
@@ -150,7 +189,7 @@ class HS_layer(_Packable):
 
     def forward(self, vertices, feature_map, neighbor_num):
         xyz = _xyz(vertices)
-        if _tracked(feature_map, *self.parameters()):
+        if _tracked(xyz, feature_map, *self.parameters()):
             from ... import autograd as tgp_autograd
             return tgp_autograd._hs(self, "conv", xyz, feature_map.float(), _SeamGraphs(), 0, neighbor_num)
         fmap = feature_map.detach().float().contiguous()
@@ -170,7 +209,7 @@ class Pool_layer(nn.Module):
         idx = ops.knn_xyz(xyz, self.neighbor_num)
         sample = torch.randperm(n)[: int(n / self.pooling_rate)]      # global CPU generator, as gcn3d.py:242
         sample = sample.to(device=xyz.device, dtype=torch.int32)
-        if _tracked(feature_map):
+        if _tracked(xyz, feature_map):
             from ... import autograd as tgp_autograd
             return tgp_autograd._PoolMax.apply(xyz, feature_map.float(), idx, sample, self.neighbor_num)
         return ops.pool(xyz, feature_map.detach().float().contiguous(), idx, sample, kpool=self.neighbor_num)

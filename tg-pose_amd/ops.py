@@ -1861,3 +1861,129 @@ def alpha_persistence(pcl, tet_cap=0):
     tet_cap < 8192 caps the triangulation's storage (status TGP_PD_ETETS when it is exceeded)."""
     out = _pd_launch(pcl, images=False, tets=True, tet_cap=tet_cap)
     return out
+
+
+# ------------------------------------------------------------------------------------------------- gradients to the points
+@_timed("graph")
+def gconv_dirgrad(xyz, idx, sdn, dg, S, C, proj=None, slots=None):
+    """d(unit neighbour direction) (B, n, k, 3) of HSlayer_surface.graph_conv (proj None) or HS_layer.graph_conv (proj (B, n, 8C) rows;
+    slots: gconv_hs_slots' record, read before gconv_hs_bwd_gather consumes it, or None: the winners are recomputed) from dg (B, n, C)"""
+    _f32(xyz, "xyz", 3), _i32(idx, "idx"), _f32(sdn, "sdn", 2)
+    if not xyz.is_contiguous() or not sdn.is_contiguous():
+        raise ValueError("gconv_dirgrad: xyz and sdn must be contiguous")
+    dg, ldg = _rows(dg, "dg")
+    B, n, k = idx.shape
+    ldp = 0
+    if proj is not None:
+        proj, ldp = _rows(proj, "proj")
+    if slots is not None and (slots.dtype != torch.uint8 or slots.numel() != B * n * S * C or not slots.is_contiguous()):
+        raise ValueError("gconv_dirgrad: slots must be a contiguous uint8 tensor of B*n*S*C entries")
+    ddir = torch.empty(B, n, k, 3, device=xyz.device, dtype=torch.float32)
+    check(_lib.lib().tgp_gconv_dirgrad(_p(xyz), _p(idx), _p(proj), ldp, _p(sdn), _p(dg), ldg, _p(slots), B, n, k, S, C, _p(ddir),
+                                       _stream(xyz)), "tgp_gconv_dirgrad")
+    return ddir
+
+
+@_timed("graph")
+def neighbor_dirs(xyz, idx, unnormed=False):
+    """xyz (B, n, 3), idx (B, n, k) int32 -> unit directions (B, n, k, 3) [, the unnormalised differences]"""
+    _f32(xyz, "xyz", 3), _i32(idx, "idx")
+    B, n, k = idx.shape
+    if not xyz.is_contiguous() or tuple(xyz.shape) != (B, n, 3):
+        raise ValueError("neighbor_dirs: xyz must be contiguous (B, n, 3) with idx's B and n")
+    unit = torch.empty(B, n, k, 3, device=xyz.device, dtype=torch.float32)
+    raw = torch.empty_like(unit) if unnormed else None
+    check(_lib.lib().tgp_neighbor_dirs(_p(xyz), _p(idx), B, n, k, _p(unit), _p(raw), _stream(xyz)), "tgp_neighbor_dirs")
+    return (unit, raw) if unnormed else unit
+
+
+def xyz_reverse_lists(idx, n_src):
+    """reverse lists of a (B, n, k) xyz / feature graph for dirs_to_xyz: (rptr, rent, rev_global) -- tgp_reverse_graph's where it sorts
+    the shape, else tgp_child_lists' over the flattened entries"""
+    rev = reverse_graph(idx, n_src)
+    if rev is not None:
+        return rev[0], rev[1], 0
+    B, n, k = idx.shape
+    ptr, ent = child_lists(idx.contiguous().view(B, n * k), n_src)
+    return ptr, ent, 1
+
+
+@_timed("graph")
+def dirs_to_xyz(xyz, idx, ddir, rev=None, dun=None, out=None, accumulate=False):
+    """backward of get_neighbor_direction_norm: ddir (B, n, k, 3) d unit direction, dun (same) d unnormalised difference or None ->
+    dxyz (B, n, 3); rev = xyz_reverse_lists(idx, n) or reverse_graph's pair (computed when None); accumulate: added to out"""
+    _f32(xyz, "xyz", 3), _i32(idx, "idx"), _f32(ddir, "ddir", 4)
+    B, n, k = idx.shape
+    if not xyz.is_contiguous() or tuple(xyz.shape) != (B, n, 3):
+        raise ValueError("dirs_to_xyz: xyz must be contiguous (B, n, 3) with idx's B and n")
+    if tuple(ddir.shape) != (B, n, k, 3) or not ddir.is_contiguous():
+        raise ValueError("dirs_to_xyz: ddir must be contiguous (B, n, k, 3)")
+    if dun is not None:
+        _f32(dun, "dun", 4)
+        if tuple(dun.shape) != (B, n, k, 3) or not dun.is_contiguous():
+            raise ValueError("dirs_to_xyz: dun must be contiguous (B, n, k, 3)")
+    if rev is None:
+        rev = xyz_reverse_lists(idx, n)
+    elif len(rev) == 2:
+        rev = (rev[0], rev[1], 0)
+    if out is None:
+        if accumulate:
+            raise ValueError("dirs_to_xyz: accumulate needs out")
+        out = torch.empty(B, n, 3, device=xyz.device, dtype=torch.float32)
+    elif not (out.is_contiguous() and tuple(out.shape) == (B, n, 3) and out.dtype == torch.float32):
+        raise ValueError("dirs_to_xyz: out must be contiguous float32 (B, n, 3)")
+    check(_lib.lib().tgp_dirs_to_xyz(_p(xyz), _p(idx), _p(rev[0]), _p(rev[1]), int(rev[2]), _p(ddir), _p(dun), B, n, k, _p(out),
+                                     int(accumulate), _stream(xyz)), "tgp_dirs_to_xyz")
+    return out
+
+
+def center_bwd(dxyz, dmean=None):
+    """backward of center(): dxyz (B, n, 3), dmean (B, 3) or None -> d points (B, n, 3)"""
+    _f32(dxyz, "dxyz", 3)
+    dxyz = dxyz.contiguous()
+    B, n, _ = dxyz.shape
+    if dmean is not None:
+        dmean = _f32(dmean, "dmean").reshape(B, 3).contiguous()
+    out = torch.empty_like(dxyz)
+    check(_lib.lib().tgp_center_bwd(_p(dxyz), _p(dmean), B, n, _p(out), _stream(dxyz)), "tgp_center_bwd")
+    return out
+
+
+def bn_apply(x, mean, var, gamma, beta, eps=1e-5, act=0, slope=0.0):
+    """act((x - mean) / sqrt(var + eps) * gamma + beta) over rows with fixed statistics (eval-mode BatchNorm on the running ones)"""
+    x, ld = _rows(x, "x")
+    C = x.shape[-1]
+    rows = math.prod(x.shape[:-1])
+    out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    check(_lib.lib().tgp_bn_apply(_p(x), ld, rows, C, _p(mean), _p(var), _p(gamma), _p(beta), float(eps), act, float(slope), None,
+                                  _p(out), C, None, 0, 0, 0, _stream(x)), "tgp_bn_apply")
+    return out
+
+
+def bn_eval_bwd(dy, x, mean, var, gamma, beta, eps=1e-5, act=0, slope=0.0):
+    """backward of bn_apply: -> (dx, dgamma, dbeta)"""
+    dy, lddy = _rows(dy, "dy")
+    x, ld = _rows(x, "x")
+    rows, C = math.prod(x.shape[:-1]), x.shape[-1]
+    dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    dg = torch.empty(C, device=x.device, dtype=torch.float32)
+    db = torch.empty(C, device=x.device, dtype=torch.float32)
+    ws = _ws(_lib.lib().tgp_bn_eval_workspace_floats(C), x.device)
+    check(_lib.lib().tgp_bn_eval_bwd(_p(dy), lddy, _p(x), ld, rows, C, _p(mean), _p(var), float(eps), _p(gamma), _p(beta), act, float(slope),
+                                     _p(dx), C, _p(dg), _p(db), _p(ws), _stream(x)), "tgp_bn_eval_bwd")
+    return dx, dg, db
+
+
+def bn_eval_bwd_pooled(dpool, argrow, x, rows_per_obj, mean, var, gamma, beta, eps=1e-5, act=0, slope=0.0):
+    """backward of colmax_arg(x, bn=(running mean, running var, gamma, beta)): -> (dense dx (objects * n, C), dgamma, dbeta)"""
+    x, ld = _rows(x, "x")
+    objects, C = dpool.shape
+    dpool = dpool.contiguous()
+    dx = torch.empty(objects * rows_per_obj, C, device=x.device, dtype=torch.float32)
+    dg = torch.empty(C, device=x.device, dtype=torch.float32)
+    db = torch.empty(C, device=x.device, dtype=torch.float32)
+    ws = _ws(objects * C, x.device)
+    check(_lib.lib().tgp_bn_eval_bwd_pooled(_p(dpool), dpool.stride(0), _p(argrow), argrow.stride(0), _p(x), ld, objects, rows_per_obj, C,
+                                            _p(mean), _p(var), float(eps), _p(gamma), _p(beta), act, float(slope), _p(dx), C, _p(dg), _p(db),
+                                            _p(ws), _stream(x)), "tgp_bn_eval_bwd_pooled")
+    return dx, dg, db
