@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests.util import golden, knn_rows_equivalent, rows_without_ties, synth_points
+from tests.util import (checked_objects, fused_kernels_fp64, golden, knn_rows_equivalent, objects_for_tiles, rows_without_ties,
+                        run_fused_kernels, synth_points)
 
 pytestmark = pytest.mark.gpu
 
@@ -61,7 +62,7 @@ def test_center_bit_exact(ops, B, n):
 
 # ----------------------------------------------------------------------------------------- kNN
 @pytest.mark.parametrize("B,n,k", [(4, 1028, 20), (2, 1024, 20), (3, 257, 20), (3, 257, 4), (5, 64, 8), (2, 300, 20),
-                                   (1, 2048, 20), (2, 130, 16)])
+                                   (1, 2048, 20), (2, 130, 16), (32, 1028, 20)])
 def test_knn_xyz_bit_exact_vs_oracle(ops, B, n, k):
     _clib, _, _ = _oracle()
     pts, _ = synth_points(B, n, seed=7 * n + k)
@@ -126,7 +127,9 @@ def test_knn_xyz_vs_reference_golden(ops, key, k):
                                         # the fused kernel's tail-row cases: 8 tail rows riding along, 9 in their own block, a tail longer
                                         # than the number of full blocks, two tail rows on two blocks, the widest cloud it serves
                                         (2, 264, 128, 20, 128), (2, 265, 128, 20, 128), (2, 40, 256, 8, 256), (2, 66, 128, 8, 128),
-                                        (1, 1152, 128, 20, 128)])
+                                        (1, 1152, 128, 20, 128),
+                                        # the benchmark's batch: conv_1 on the concat buffer's row stride, a layer at 257 points
+                                        (32, 1028, 128, 20, 1292), (32, 257, 256, 20, 256)])
 def test_knn_feat_bit_exact_vs_oracle(ops, B, n, d, k, ld):
     _clib, _, _ = _oracle()
     gen = torch.Generator().manual_seed(n + d)
@@ -974,9 +977,10 @@ def test_enable_proj_vs_reference_golden(ops):
     assert torch.allclose(got["feat_global"].cpu(), want["feat_global"], atol=1e-4, rtol=0)
 
 
-@pytest.mark.parametrize("B,N,seed,tol", [(4, 1028, 21, 1e-4), (3, 512, 22, 1e-4), (2, 512, 22, 2e-3)])
+@pytest.mark.parametrize("B,N,seed,tol", [(4, 1028, 21, 1e-4), (3, 512, 22, 1e-4), (2, 512, 22, 2e-3), (32, 1028, 24, 1e-4)])
 def test_training_forward_vs_oracle(ops, B, N, seed, tol):
-    """Teacher-forced on the oracle's graphs, 1e-4.  B = 2 is the ill-conditioned corner of the reference's own maths:
+    """Teacher-forced on the oracle's graphs, 1e-4; B = 32 is the benchmark's batch (BatchNorm over 32 896 rows, every category
+    present).  B = 2 is the ill-conditioned corner of the reference's own maths:
     bn5 / bn3 normalise two pooled rows, so each channel becomes +-gamma * d / sqrt(d^2 + eps) with d = (x1 - x2) / 2 and
     a 1e-6 difference in x is amplified by up to 1/sqrt(eps) = 316; checked at 2e-3 only to catch gross errors."""
     from tgpose_amd import FLAGS, seeded_state_dict
@@ -2351,7 +2355,8 @@ def test_fused_kernels_vs_fp64(ops, B, N):
     """tgp_heads_fused and tgp_conv_max_fused at the operator level: random operands, fp64 torch restatement of
     max_points relu(bn2(conv2(relu(bn1(W_fine . fine + P1[idx1] + P2[idx2] + bias))))) resp. max_points lrelu(bn(conv ...)).
     Objects of N rows with N % 32 != 0 (waves straddle objects), M % 128 != 0 (a partial last tile), K = 268 of 272 columns
-    with garbage in the padding.  Accuracy bar: that of the split GEMM (3e-6 of the output scale per layer; two layers)."""
+    with garbage in the padding.  Accuracy bar: that of the split GEMM (3e-6 of the output scale per layer; two layers).
+    (The same restatement at the tile counts of the kernels' round rules: test_fused_kernels_vs_fp64_at_the_round_boundaries.)"""
     gen = torch.Generator().manual_seed(B * 1000 + N)
     M, K, heads = B * N, 268, 3
     fine = torch.randn(M, 272, generator=gen)
@@ -2366,24 +2371,13 @@ def test_fused_kernels_vs_fp64(ops, B, N):
     bias, scale, shift = (torch.randn(4096, generator=gen) * 0.1, torch.rand(4096, generator=gen) + 0.5, torch.randn(4096, generator=gen) * 0.1)
     W2 = torch.randn(heads, 256, 1024, generator=gen) / 32.0
     b2, sc2, sh2 = (torch.randn(heads, 256, generator=gen) * 0.1, torch.rand(heads, 256, generator=gen) + 0.5, torch.randn(heads, 256, generator=gen) * 0.1)
-    d = lambda t: g(t.contiguous())
-    was = ops.split_f16(d(Wa))
-    keys2, over = ops.heads_fused(d(fine), K, ops.heads_planes_w(d(Wa)[1024:]), d(P1)[:, 1024:], d(idx1), d(P2)[:, 1024:], d(idx2),
-                                  ops.heads_pack_w2(d(W2), d(bias)[1024:], d(scale)[1024:], d(shift)[1024:]), d(b2), d(sc2), d(sh2), B, N)
-    keys5, over5 = ops.conv_max_fused(d(fine), K, ops.heads_planes_w(d(Wa)[:1024]), d(P1), d(idx1), d(P2), d(idx2), d(bias)[:1024], d(scale)[:1024], d(shift)[:1024],
-                                      0.2, B, N)
-    assert int(over.item()) == 0 and int(over5.item()) == 0
-    got2 = ops.colmax_decode(keys2.view(heads * B, 256)).view(heads, B, 256).cpu().double()
-    got5 = ops.colmax_decode(keys5).cpu().double()
-    f64 = fine[:, :K].double()
-    pre = f64 @ Wa[:, :K].double().t() + bias.double() + P1.double()[idx1.long()] + P2.double()[idx2.long()]
-    pre = pre * scale.double() + shift.double()
-    c5 = torch.nn.functional.leaky_relu(pre[:, :1024], 0.2).view(B, N, 1024).max(1)[0]
+    operands = [fine, K, Wa, P1, idx1, P2, idx2, bias, scale, shift, W2, b2, sc2, sh2]
+    got5, got2, over5, over = run_fused_kernels(ops, *[g(t.contiguous()) if torch.is_tensor(t) else t for t in operands], B, N)
+    assert over == 0 and over5 == 0
+    c5, y = fused_kernels_fp64(*operands, N, range(B))
     assert (got5 - c5).abs().max().item() <= 3e-6 * c5.abs().max().item()
-    H = torch.relu(pre[:, 1024:]).view(M, heads, 1024)
     for hd in range(heads):
-        y = torch.relu((H[:, hd] @ W2[hd].double().t() + b2[hd].double()) * sc2[hd].double() + sh2[hd].double()).view(B, N, 256).max(1)[0]
-        assert (got2[hd] - y).abs().max().item() <= 6e-6 * y.abs().max().item(), hd
+        assert (got2[hd] - y[hd]).abs().max().item() <= 6e-6 * y[hd].abs().max().item(), hd
 
 
 def test_fused_kernels_flag_tiny_inputs(ops):
@@ -3072,15 +3066,18 @@ def _step_db(cat_ids, N, seed, golden_name="category_clouds.npz"):
                           torch.from_numpy(gc["pdh2_category"]), sym, cat_ids, N, seed)
 
 
-def test_train_step_vs_oracle_full_cloud_size(ops):
-    """The same step at N = 1028 (the benchmark's cloud size), B = 8 with every category, against the CPU oracle's composition
-    (oracle/train_step_ref.py, itself pinned to the reference's trainer by tests/test_oracle_golden.py) on the oracle's graphs."""
+@pytest.mark.parametrize("B", [8, 32])
+def test_train_step_vs_oracle_full_cloud_size(ops, B):
+    """The same step at N = 1028 (the benchmark's cloud size), B = 8 and the benchmark's B = 32 with every category, against the CPU
+    oracle's composition (oracle/train_step_ref.py, itself pinned to the reference's trainer by tests/test_oracle_golden.py) on the
+    oracle's graphs.  B = 32 is the size bench.py --workload train_step times: the K-split plans of the weight-gradient GEMMs
+    (ops._ksplit_plan) and the BatchNorm reductions over 32 896 rows."""
     from oracle import train_step_ref as TS
     from tgpose_amd import FLAGS, seeded_state_dict
     from tgpose_amd.trainer.RL_TDA import total_loss
     from tests.test_oracle_golden import leaves
-    B, N, wseed = 8, 1028, 9
-    db = _step_db([0, 1, 2, 3, 4, 5, 3, 0], N, 19)
+    N, wseed = 1028, 9
+    db = _step_db([0, 1, 2, 3, 4, 5, 3, 0] if B == 8 else [i % 6 for i in range(B)], N, 19)
     torch.manual_seed(5)
     samples = []
     for _ in range(2):
@@ -4275,8 +4272,16 @@ def test_repair_buffer_of_the_fused_heads_is_chunked(ops):
         assert torch.isfinite(outs[0][k]).all() and torch.equal(outs[0][k], outs[1][k]), k
 
 
+# At the benchmark's B = 32 the GPU's conv_0.directions gradient is 2.6e-3 (relative L2) from the fp64 oracle on the same recorded
+# branch, in both GEMM modes; the fp32 oracle is 4.4e-4 from the fp64 one, every other parameter of the GPU run within 1.8e-3 of it.
+_FORCED_B32 = pytest.mark.xfail(strict=True, raises=AssertionError, reason=(
+    "conv_0.directions 2.6e-3 from the fp64 oracle at B = 32 (bar 2e-3; fp32 oracle 4.4e-4): cause open -- the surface conv's backward "
+    "(csrc/gconv_bwd.hip) re-derives its max over neighbours, which the forcing does not pin, and sums 32 896 x 20 terms"))
+
+
+@pytest.mark.parametrize("B", [4, pytest.param(32, marks=_FORCED_B32)])
 @pytest.mark.parametrize("gemm_mode", ["split16", "fp32"], indirect=True)
-def test_backward_full_network_with_forced_decisions(ops, gemm_mode):
+def test_backward_full_network_with_forced_decisions(ops, gemm_mode, B):
     """The whole network's gradient at the benchmark's cloud size in the DEFAULT arithmetic, with the decisions taken out of the
     comparison (round-2 and round-3 verdicts).  The gradient of this network is piecewise: every ReLU mask, every max over neighbours
     / points picks a branch, and two fp32 evaluations 1e-6 apart pick a handful of different ones -- which is why the free-running
@@ -4286,10 +4291,13 @@ def test_backward_full_network_with_forced_decisions(ops, gemm_mode):
     mask, each recorded winner the max over points (oracle.posenet_ref.posenet_forward(force=...), itself checked on the CPU by
     tests/test_oracle_golden.py::test_oracle_forced_decisions_reproduce_a_free_run).  What is left between the two gradients is
     rounding: every parameter within 2e-3 relative L2 (B = 4, N = 1028, fp16-split GEMMs and exact-fp32 GEMMs; median ~3e-5), and
-    the count of visible ReLU decisions that differ in the free-running oracle is printed beside it."""
+    the count of visible ReLU decisions that differ in the free-running oracle is printed beside it.  At the benchmark's B = 32 the
+    oracle differentiates the branch in float64 (its fp32 sums over 32 896 rows are themselves up to 4e-4 off); that case is an expected
+    failure for now (_FORCED_B32)."""
     from tgpose_amd import FLAGS, seeded_state_dict, autograd
     _, _, PR = _oracle()
-    B, N, seed = 4, 1028, 44
+    N, seed = 1028, 44
+    dt = torch.float64 if B == 32 else torch.float32
     sd = seeded_state_dict(seed)
     pts, obj = synth_points(B, N, seed)
     torch.manual_seed(seed)
@@ -4313,19 +4321,20 @@ def test_backward_full_network_with_forced_decisions(ops, gemm_mode):
     loss.backward()
     got = {k: p.grad for k, p in net.named_parameters()}
     # the oracle on the recorded branch
-    P = {k: (v.clone().requires_grad_(True) if v.dtype.is_floating_point and "running_" not in k else v.clone()) for k, v in sd.items()}
-    forced = PR.posenet_forward(P, pts, obj, sample_idx=sample, train_keys=True, mode="exact", bn_train=True, inject=inter["indices"],
-                                force=taps)
+    P = {k: (v.to(dt, copy=True).requires_grad_(True) if v.dtype.is_floating_point and "running_" not in k else
+             v.to(dt, copy=True) if v.dtype.is_floating_point else v.clone()) for k, v in sd.items()}
+    forced = PR.posenet_forward(P, pts.to(dt), obj.to(dt), sample_idx=sample, train_keys=True, mode="exact", bn_train=True,
+                                inject=inter["indices"], force=taps)
     forced.pop("_bn_new")
-    sum((forced[k] * weights[k]).sum() for k in weights).backward()
-    want = {k: v.grad for k, v in P.items() if torch.is_tensor(v) and v.requires_grad and v.grad is not None}
+    sum((forced[k] * weights[k].to(dt)).sum() for k in weights).backward()
+    want = {k: v.grad.float() for k, v in P.items() if torch.is_tensor(v) and v.requires_grad and v.grad is not None}
     for k, v in forced.items():
-        assert torch.allclose(out[k].detach().cpu(), v.detach(), atol=1e-4, rtol=0), k
+        assert torch.allclose(out[k].detach().cpu(), v.detach().float(), atol=1e-4, rtol=0), k
     relu_cols = out["feat"].detach().cpu()[:, :, :768], free["feat"][:, :, :768]
     flipped = int(((relu_cols[0] == 0) != (relu_cols[1] == 0)).sum())
     rel = {k: (got[k].cpu() - w).norm().item() / (w.norm().item() + GRAD_ATOL) for k, w in want.items()}
-    print("forced-decision backward %s: worst |dg|/|g| %.2e (%s), median %.2e; free-running oracle differs in %d of %d visible ReLU decisions"
-          % (gemm_mode, max(rel.values()), max(rel, key=rel.get), sorted(rel.values())[len(rel) // 2], flipped, relu_cols[0].numel()))
+    print("forced-decision backward %s B=%d: worst |dg|/|g| %.2e (%s), median %.2e; free-running oracle differs in %d of %d visible ReLU decisions"
+          % (gemm_mode, B, max(rel.values()), max(rel, key=rel.get), sorted(rel.values())[len(rel) // 2], flipped, relu_cols[0].numel()))
     for k in sorted(rel, key=rel.get, reverse=True)[:6]:
         print("|dg|_2 / (|g|_2 + %.0e)  %-46s %.2e   (|g|_2 %.3e)" % (GRAD_ATOL, k, rel[k], want[k].norm().item()))
     # conv biases in front of a BatchNorm (and what only reaches the loss through such a pair at B = 4) have a gradient that is zero in
@@ -4391,3 +4400,293 @@ def test_submodules_stand_alone_in_eval_and_training_mode(ops):
                                                #  few ReLU / max decisions differ -- test_backward_full_network_with_forced_decisions)
     finally:
         FLAGS.train = 0
+
+
+# ------------------------------------------------------------------ the benchmark's sizes and the fused kernels' round rules
+# conv_max_fused and dec_l1 cut the few tiles that lie just past a whole round of workgroups into single 32-channel blocks, one
+# workgroup per block.  Only large batches reach that path (B = 32 objects of 1028 points: 257 tiles; B = 256: 2056).  The two rules
+# as their launchers state them: the tests assert on which side of them their shapes fall, so that a change of a rule fails here
+# instead of silently leaving the cut path uncovered.
+def _conv_max_cut(tiles, C=1024):
+    """tiles tgp_conv_max_fused (csrc/heads_fused.hip) cuts: 1-8 past a whole round of 512 / chunks tiles (2 chunks below 512 tiles)"""
+    rnd = 512 // (2 if C // 32 >= 2 and tiles < 512 else 1)
+    return tiles % rnd if tiles > rnd and 0 < tiles % rnd <= 8 else 0
+
+
+def _dec_l1_cut(tiles, cus):
+    """tiles tgp_dec_l1 (csrc/dec_fused.hip) cuts: 1-8 past a whole round of one tile per CU"""
+    return tiles % cus if tiles > cus and 0 < tiles % cus <= 8 else 0
+
+
+def _cus():
+    return torch.cuda.get_device_properties(DEV).multi_processor_count
+
+
+EVAL_KEYS = ("p_green_R", "p_red_R", "f_green_R", "f_red_R", "Pred_T", "Pred_s")
+
+
+@pytest.mark.parametrize("tiles,cut", [(256, 0), (257, 1), (264, 8), (265, 0), (520, 8), (521, 0), (2056, 8)])
+def test_fused_kernels_vs_fp64_at_the_round_boundaries(ops, tiles, cut):
+    """tgp_conv_max_fused and tgp_heads_fused against test_fused_kernels_vs_fp64's fp64 restatement and bars (3e-6 / 6e-6 of the output's
+    scale) at tile counts on both sides of conv_max_fused's round rule: 256 (one round of two chunks per tile), 257 and 264 (1 and 8 tiles
+    past it: cut into single channel blocks), 265 (9 past: not cut), 520 (one chunk per tile from 512 tiles on: 8 cut), 521, and 2056 =
+    B = 256 objects of 1028 points (the last 8 tiles: rows 4-1027 of object 255).  The heads kernel has no cut; here it runs grids of
+    several rounds.  Operands are drawn on the device (P1 alone is 1 GB at 2056 tiles); the fp64 side takes the first object, one in the
+    middle, the last one and every object with a row in a cut tile -- objects of N % 32 != 0 points whose boundaries fall inside the cut
+    tiles."""
+    B, N = (256, 1028) if tiles == 2056 else objects_for_tiles(tiles, cut)
+    M, K, heads = B * N, 268, 3
+    assert -(-M // 128) == tiles and _conv_max_cut(tiles) == cut
+    gen = torch.Generator(device=DEV).manual_seed(tiles)
+    rn = lambda *s: torch.randn(*s, generator=gen, device=DEV)
+    ru = lambda *s: torch.rand(*s, generator=gen, device=DEV)
+    fine = rn(M, 272)
+    fine[:, K:] = float("nan")                                     # the padding columns are not the caller's to define
+    fine[:, :K][:, ::9] *= 30.0
+    Wa = rn(4096, 272) / K ** 0.5
+    Wa[:, K:] = 0
+    n1, n2 = M // 4, M // 16
+    P1, P2 = rn(n1, 4096), rn(n2, 4096)
+    idx1 = torch.randint(0, n1, (M,), generator=gen, device=DEV, dtype=torch.int32)
+    idx2 = torch.randint(0, n2, (M,), generator=gen, device=DEV, dtype=torch.int32)
+    bias, scale, shift = rn(4096) * 0.1, ru(4096) + 0.5, rn(4096) * 0.1
+    W2 = rn(heads, 256, 1024) / 32.0
+    b2, sc2, sh2 = rn(heads, 256) * 0.1, ru(heads, 256) + 0.5, rn(heads, 256) * 0.1
+    operands = [fine, K, Wa, P1, idx1, P2, idx2, bias, scale, shift, W2, b2, sc2, sh2]
+    got5, got2, over5, over = run_fused_kernels(ops, *operands, B, N)
+    assert over == 0 and over5 == 0
+    objs = checked_objects(B, N, (tiles - cut) * 128)
+    c5, y = fused_kernels_fp64(*operands, N, objs)
+    got5, got2 = got5[objs], got2[:, objs]
+    print("conv_max_fused / heads_fused: %d tiles (B = %d, N = %d), %d cut into channel blocks; objects %s; |err| / scale conv_5 %.2e, "
+          "heads %.2e" % (tiles, B, N, cut, objs, (got5 - c5).abs().max().item() / c5.abs().max().item(),
+                          max((got2[hd] - y[hd]).abs().max().item() / y[hd].abs().max().item() for hd in range(heads))))
+    assert (got5 - c5).abs().max().item() <= 3e-6 * c5.abs().max().item()
+    for hd in range(heads):
+        assert (got2[hd] - y[hd]).abs().max().item() <= 6e-6 * y[hd].abs().max().item(), hd
+
+
+@pytest.mark.parametrize("rounds,extra,cut", [(1, -1, 0), (1, 1, 1), (1, 8, 8), (1, 9, 0), (2, 8, 8)])
+def test_dec_l1_and_dec_fused_vs_fp64_at_the_round_boundaries(ops, rounds, extra, cut):
+    """The decoder as the engine runs it by default (engine.decoder_forward_factored: tgp_dec_l1, then tgp_dec_fused on
+    dec_pack(h1_permuted=True)) against an fp64 restatement of the whole decoder: relu(bn(fine . Wa + P1[idx1] + P2[idx2] + bias +
+    rowbias[object])), three relu(bn(conv)) layers, the last conv, rows leaving through a permutation per object.  At rounds x CUs +
+    extra tiles, the CU count read from the device (dec_l1's round is one tile per CU, so the cut is exercised on a partitioned device
+    too): CUs - 1, CUs + 1, CUs + 8 (1 and 8 tiles cut into single channel blocks), CUs + 9, 2 CUs + 8.  Objects of N % 32 != 0 points,
+    coarse products and per-object biases as views into wider rows.  Bar: test_dec_fused_vs_fp64_and_partial_tiles's 1e-5 of the
+    output's scale; the range flag stays 0."""
+    cus = _cus()
+    tiles = rounds * cus + extra
+    B, N = objects_for_tiles(tiles, cut)
+    M, K = B * N, 268
+    assert -(-M // 128) == tiles and _dec_l1_cut(tiles, cus) == cut
+    gen = torch.Generator(device=DEV).manual_seed(tiles + 1)
+    rn = lambda *s: torch.randn(*s, generator=gen, device=DEV)
+    ru = lambda *s: torch.rand(*s, generator=gen, device=DEV)
+    fine = rn(M, 272)
+    fine[:, K:] = float("nan")
+    Wa = rn(512, 272) / K ** 0.5
+    Wa[:, K:] = 0
+    n1, n2 = M // 4, M // 16
+    P1, P2 = rn(n1, 640)[:, 128:], rn(n2, 640)[:, 128:]            # as the engine's P1[:, 4096:]: a row stride wider than 512
+    idx1 = torch.randint(0, n1, (M,), generator=gen, device=DEV, dtype=torch.int32)
+    idx2 = torch.randint(0, n2, (M,), generator=gen, device=DEV, dtype=torch.int32)
+    rowbias = (rn(B, 516) * 0.3)[:, :512]
+    bias, scale, shift = rn(512) * 0.1, ru(512) + 0.5, rn(512) * 0.1
+    Ws = [rn(n, k) / k ** 0.5 for n, k in ((512, 512), (256, 512), (128, 256))]
+    vecs = [(rn(n) * 0.1, ru(n) + 0.5, rn(n) * 0.1) for n in (512, 256, 128)]
+    w5, b5 = rn(3, 128) / 11.0, rn(3)
+    order = torch.argsort(ru(B, N), dim=1)
+    flag = torch.zeros(1, device=DEV, dtype=torch.int32)
+    h1 = ops.Planes(M, 512, DEV)
+    ops.dec_l1(ops.planes_split(fine, K=K), ops.heads_planes_w(Wa), P1, idx1, P2, idx2, bias, scale, shift, rowbias, N, h1, flag)
+    out = ops.dec_fused(h1, ops.dec_pack(*Ws, h1_permuted=True), vecs, w5, b5, order, N, flag).view(B, N, 3)
+    assert int(flag.item()) == 0
+    objs = checked_objects(B, N, (tiles - cut) * 128)
+    h = lambda t: t.cpu().double()
+    rows = torch.cat([torch.arange(b * N, (b + 1) * N) for b in objs]).to(DEV)
+    x = h(fine[rows, :K]) @ h(Wa[:, :K]).t() + h(bias) + h(P1[idx1[rows].long()]) + h(P2[idx2[rows].long()]) + h(rowbias[rows // N])
+    x = torch.relu(x * h(scale) + h(shift))
+    for W, (b, sc, sh) in zip(Ws, vecs):
+        x = torch.relu((x @ h(W).t() + h(b)) * h(sc) + h(sh))
+    y = (x @ h(w5).t() + h(b5)).view(len(objs), N, 3)
+    ref = torch.empty_like(y).scatter_(1, order[objs].cpu().unsqueeze(-1).expand(-1, -1, 3), y)
+    err = (h(out[objs]) - ref).abs().max().item()
+    print("dec_l1 -> dec_fused: %d tiles on %d CUs (B = %d, N = %d), %d cut into channel blocks; objects %s; |err| / scale %.2e"
+          % (tiles, cus, B, N, cut, objs, err / ref.abs().max().item()))
+    assert err <= 1e-5 * ref.abs().max().item()
+
+
+BENCH_B, BENCH_N, BENCH_SEED = 32, 1028, 26
+
+
+@pytest.fixture(scope="module")
+def bench_case():
+    """bench.py's batch -- B = 32 objects of N = 1028 points, every category present -- on seeded weights, and the oracle's eval forward on
+    it with the training keys (for recon / h1 / h2) and its graphs: computed once for the tests that share it"""
+    from tgpose_amd import seeded_state_dict
+    _, _, PR = _oracle()
+    pts, obj = synth_points(BENCH_B, BENCH_N, BENCH_SEED)
+    assert sorted(set(obj.view(-1).int().tolist())) == list(range(6))
+    torch.manual_seed(BENCH_SEED)
+    i1 = torch.randperm(BENCH_N)[: BENCH_N // 4]
+    sample = (i1, torch.randperm(i1.numel())[: i1.numel() // 4])
+    with torch.no_grad():
+        want, inter = PR.posenet_forward(seeded_state_dict(BENCH_SEED), pts, obj, sample_idx=sample, train_keys=True, mode="exact",
+                                         want_intermediates=True)
+    return pts, obj, sample, want, inter["indices"]
+
+
+def _default_engine_flags():
+    """the arithmetic and kernels bench.py runs: fp16-split GEMMs on planes, the projection kernel, the factored layers, the fused heads
+    kernel, the decoder on planes only through dec_l1 and dec_fused"""
+    from tgpose_amd import engine, ops as _ops
+    return bool(_ops.PLANES and _ops.GEMM_MODE == "split16" and engine.PROJ_KERNEL and engine.FACTORED and engine.HEADS_FUSED
+                and engine.DEC_PLANES_ONLY and engine.DEC_L1 and engine.DEC_FUSED)
+
+
+def _count_launches(ops, monkeypatch):
+    """record the row count of every ops.dec_l1 call and count the ops.conv_max_fused calls of a forward: the fused kernels with a cut
+    path did run (their use also depends on the weights' fp16 range and on row-routing rules, not only on the engine's switches)"""
+    calls = {"dec_l1": [], "conv_max_fused": []}
+    dec_l1, conv_max = ops.dec_l1, ops.conv_max_fused
+
+    def dec_l1_rec(fine_planes, *a, **kw):
+        calls["dec_l1"].append(fine_planes.rows)
+        return dec_l1(fine_planes, *a, **kw)
+
+    def conv_max_rec(*a, **kw):
+        calls["conv_max_fused"].append(1)
+        return conv_max(*a, **kw)
+    monkeypatch.setattr(ops, "dec_l1", dec_l1_rec)
+    monkeypatch.setattr(ops, "conv_max_fused", conv_max_rec)
+    return calls
+
+
+def test_benchmark_batch_eval_forward_vs_oracle(ops, bench_case, monkeypatch):
+    """bench.py's line -- B = 32 objects of N = 1028 points in eval mode with the default engine flags (planes, the projection kernel,
+    the fused heads kernel, DEC_L1, DEC_FUSED) -- on the oracle's graphs: all 32 objects x the six eval keys within 1e-4, and recon /
+    h1 / h2 (engine.posenet_forward's probe) within 1e-4 of the oracle's training-key output.  The 32 896 rows are 257 tiles of 128:
+    conv_max_fused (conv_5, whose maxima feed the PH branch, and through it h1 / h2 and the decoder's per-object bias) and dec_l1 (the
+    decoder's first conv) cut the 257th tile, rows 900-1027 of object 31, into single channel blocks: object 31's recon rows 900-1027
+    are the ones dec_l1 computes on its cut path."""
+    from tgpose_amd import FLAGS, engine
+    assert _default_engine_flags()
+    assert _conv_max_cut(257) == 1 and _dec_l1_cut(257, _cus()) == 1
+    pts, obj, sample, want, idx = bench_case
+    net = _net(BENCH_SEED)
+    FLAGS.train = 0
+    probe = {}
+    calls = _count_launches(ops, monkeypatch)
+    with torch.no_grad():
+        got = engine.posenet_forward(net.packed(DEV), g(pts), g(obj), False, sample_idx=sample, inject=idx, probe=probe)
+    assert calls["dec_l1"] == [BENCH_B * BENCH_N] and len(calls["conv_max_fused"]) == 1
+    assert sorted(got) == sorted(EVAL_KEYS)
+    for k in EVAL_KEYS:
+        assert torch.allclose(got[k].cpu(), want[k], atol=1e-4, rtol=0), k
+    for k in ("recon", "h1", "h2"):
+        assert torch.allclose(probe[k].cpu(), want[k], atol=1e-4, rtol=0), k
+    print("B = 32 eval forward on the oracle's graphs: |err| six keys %.2e, recon %.2e (object 31, rows 900-1027: %.2e), h1 / h2 %.2e"
+          % (max((got[k].cpu() - want[k]).abs().max().item() for k in EVAL_KEYS), (probe["recon"].cpu() - want["recon"]).abs().max().item(),
+             (probe["recon"][31, 900:].cpu() - want["recon"][31, 900:]).abs().max().item(),
+             max((probe[k].cpu() - want[k]).abs().max().item() for k in ("h1", "h2"))))
+
+
+def test_benchmark_batch_free_running_forward_and_its_replay_vs_oracle(ops, bench_case):
+    """The same inputs free-running, in the execution form bench.py times: branch-free (engine.BRANCH_STREAMS off while the forward runs
+    and while it is captured), eager and as a GraphedForward(pk, 32, 1028, train_keys=False) replay.
+      * the xyz graphs are bit-identical to the oracle's; the feature graphs meet test_forward_vs_oracle's same-set bars (conv_1 >= 99 %,
+        later layers >= 93 % of the rows keep the oracle's neighbour set);
+      * the six eval keys and recon / h1 / h2 (probe) are within 1e-4 of the oracle run on the graphs this run built (measured <= 5e-7);
+      * against the oracle's own free run they drift further -- a near-tied neighbour that swaps moves an object's outputs: measured
+        p_green_R 5.9e-4 on object 21 (the next object 1.7e-4), p_red_R 2.5e-4, recon 2.1e-4, the others <= 6.1e-5.  Every key stays
+        within 1e-3 on every object and within test_forward_vs_oracle's 5e-4 on all objects but one;
+      * the replay returns the eager run's results bit for bit."""
+    from tgpose_amd import FLAGS, engine, seeded_state_dict
+    _, _, PR = _oracle()
+    assert _default_engine_flags()
+    pts, obj, sample, want, idx = bench_case
+    net = _net(BENCH_SEED)
+    FLAGS.train = 0
+    old = engine.BRANCH_STREAMS
+    engine.BRANCH_STREAMS = False
+    try:
+        rec, probe = {}, {}
+        with torch.no_grad():
+            free = {k: v.clone() for k, v in engine.posenet_forward(net.packed(DEV), g(pts), g(obj), False, sample_idx=sample, record=rec,
+                                                                    probe=probe).items()}
+        aux = {k: probe[k].cpu() for k in ("recon", "h1", "h2")}
+        gf = engine.GraphedForward(net.packed(DEV), BENCH_B, BENCH_N, torch.device(DEV), train_keys=False)
+        replay = {k: v.clone() for k, v in gf(g(pts), g(obj), sample).items()}
+        torch.cuda.synchronize()
+        del gf
+    finally:
+        engine.BRANCH_STREAMS = old
+    own = {}
+    for name, ref in idx.items():
+        got = rec[name].cpu().long()
+        got = own[name] = (got.unsqueeze(-1) if got.dim() == 2 else got)[..., : ref.shape[-1]]   # k=4 list = prefix of the k=20 list
+        if name.endswith(".rf") and "conv_0" not in name:
+            same_set = (got.sort(-1)[0] == ref.sort(-1)[0]).all(dim=-1).float().mean().item()
+            assert same_set >= (0.99 if "conv_1" in name else 0.93), (name, same_set)
+        else:
+            assert torch.equal(got, ref), name
+    with torch.no_grad():
+        on_own = PR.posenet_forward(seeded_state_dict(BENCH_SEED), pts, obj, sample_idx=sample, train_keys=True, mode="exact", inject=own)
+    got = dict({k: free[k].cpu() for k in EVAL_KEYS}, **aux)
+    for k, v in got.items():
+        assert torch.allclose(v, on_own[k], atol=1e-4, rtol=0), k
+    drift = {k: (v - want[k]).abs().reshape(BENCH_B, -1).max(1)[0] for k, v in got.items()}
+    print("B = 32 free run: |err| vs the oracle on the run's own graphs %.2e; vs the oracle's free run %s"
+          % (max((v - on_own[k]).abs().max().item() for k, v in got.items()),
+             ", ".join("%s %.1e (object %d)" % (k, d.max().item(), d.argmax().item()) for k, d in drift.items())))
+    for k, d in drift.items():
+        assert d.max().item() <= 1e-3 and d.sort()[0][-2].item() <= 5e-4, (k, d.max().item(), d.argmax().item())
+    assert sorted(replay) == sorted(free)
+    for k in free:
+        assert torch.equal(replay[k], free[k]), k
+
+
+def test_forward_large_batch_every_object_vs_oracle(ops, monkeypatch):
+    """B = 256 objects of 1028 points (BASELINE config 3) in eval mode on the oracle's graphs: every object x the six eval keys within
+    1e-4, and recon / h1 / h2 (probe) within 1e-4 of the oracle's training-key output.  The oracle runs in 8 chunks of 32 objects --
+    eval-mode objects are independent (running BatchNorm statistics) -- and the chunks' neighbour lists, local to each object,
+    are concatenated along the batch.  The 263 168 rows are 2056 tiles: conv_max_fused and dec_l1 cut the last 8 into single channel
+    blocks -- rows 4-1027 of object 255, which test_forward_large_batch_runs checks only for being finite."""
+    from tgpose_amd import FLAGS, engine, seeded_state_dict
+    _, _, PR = _oracle()
+    assert _default_engine_flags()
+    assert _conv_max_cut(2056) == 8 and _dec_l1_cut(2056, _cus()) == 8
+    B, N, C, seed = 256, 1028, 32, 27
+    sd = seeded_state_dict(seed)
+    pts, obj = synth_points(B, N, seed)
+    torch.manual_seed(seed)
+    i1 = torch.randperm(N)[: N // 4]
+    sample = (i1, torch.randperm(i1.numel())[: i1.numel() // 4])
+    keys = EVAL_KEYS + ("recon", "h1", "h2")
+    want, idx = {k: [] for k in keys}, {}
+    with torch.no_grad():
+        for c in range(0, B, C):
+            out, inter = PR.posenet_forward(sd, pts[c:c + C], obj[c:c + C], sample_idx=sample, train_keys=True, mode="exact",
+                                            want_intermediates=True)
+            for k in keys:
+                want[k].append(out[k])
+            for k, v in inter["indices"].items():
+                idx.setdefault(k, []).append(v)
+            del out, inter
+    want = {k: torch.cat(v) for k, v in want.items()}
+    idx = {k: torch.cat(v) for k, v in idx.items()}
+    net = _net(seed)
+    FLAGS.train = 0
+    probe = {}
+    calls = _count_launches(ops, monkeypatch)
+    with torch.no_grad():
+        got = engine.posenet_forward(net.packed(DEV), g(pts), g(obj), False, sample_idx=sample, inject=idx, probe=probe)
+    assert calls["dec_l1"] == [B * N] and len(calls["conv_max_fused"]) == 1
+    got.update({k: probe[k] for k in ("recon", "h1", "h2")})
+    for k in keys:
+        err = (got[k].cpu() - want[k]).abs().reshape(B, -1).max(1)[0]
+        assert err.shape[0] == B and err.max().item() <= 1e-4, (k, err.argmax().item(), err.max().item())
+    print("B = 256 eval forward on the oracle's graphs: |err| %s; object 255: %.2e"
+          % (", ".join("%s %.1e" % (k, (got[k].cpu() - want[k]).abs().max().item()) for k in keys),
+             max((got[k][255].cpu() - want[k][255]).abs().max().item() for k in keys)))

@@ -44,6 +44,56 @@ def rows_without_ties(D, k):
     return (np.diff(s, axis=1) > 0).all(axis=1)
 
 
+def run_fused_kernels(ops, fine, K, Wa, P1, idx1, P2, idx2, bias, scale, shift, W2, b2, sc2, sh2, B, N, slope=0.2):
+    """tgp_conv_max_fused over Wa's first 1024 rows (conv_5, LeakyReLU(slope)) and tgp_heads_fused over the rest (the heads), operands
+    on the device: -> conv_5's maxima (B, 1024) and the heads' (heads, B, 256) as fp64 on the host, conv_5's and the heads' range flags"""
+    heads = W2.shape[0]
+    keys2, over = ops.heads_fused(fine, K, ops.heads_planes_w(Wa[1024:]), P1[:, 1024:], idx1, P2[:, 1024:], idx2,
+                                  ops.heads_pack_w2(W2, bias[1024:], scale[1024:], shift[1024:]), b2, sc2, sh2, B, N)
+    keys5, over5 = ops.conv_max_fused(fine, K, ops.heads_planes_w(Wa[:1024]), P1, idx1, P2, idx2, bias[:1024], scale[:1024], shift[:1024],
+                                      slope, B, N)
+    got2 = ops.colmax_decode(keys2.view(heads * B, 256)).view(heads, B, 256).cpu().double()
+    got5 = ops.colmax_decode(keys5).cpu().double()
+    return got5, got2, int(over5.item()), int(over.item())
+
+
+def fused_kernels_fp64(fine, K, Wa, P1, idx1, P2, idx2, bias, scale, shift, W2, b2, sc2, sh2, N, objs, slope=0.2):
+    """fp64 restatement of run_fused_kernels for the objects objs (rows b N .. b N + N - 1 of object b): the max over points of
+    lrelu(bn(W_fine . fine + P1[idx1] + P2[idx2] + bias)) (conv_5) and of relu(bn2(conv2(relu(bn1(...))))) per head.  A max over points
+    needs all of an object's rows, not all objects: only the objects' rows and their gathered coarse rows are copied to the host, so the
+    operands may live on the device at any size.  -> (len(objs), 1024), (heads, len(objs), 256)"""
+    h = lambda t: t.cpu().double()
+    rows = torch.cat([torch.arange(b * N, (b + 1) * N) for b in objs]).to(fine.device)
+    pre = h(fine[rows, :K]) @ h(Wa[:, :K]).t() + h(bias) + h(P1[idx1[rows].long()]) + h(P2[idx2[rows].long()])
+    pre = pre * h(scale) + h(shift)
+    nb, heads = len(objs), W2.shape[0]
+    c5 = torch.nn.functional.leaky_relu(pre[:, :1024], slope).view(nb, N, 1024).max(1)[0]
+    H = torch.relu(pre[:, 1024:]).view(nb * N, heads, 1024)
+    y = torch.stack([torch.relu((H[:, hd] @ h(W2[hd]).t() + h(b2[hd])) * h(sc2[hd]) + h(sh2[hd])).view(nb, N, 256).max(1)[0]
+                     for hd in range(heads)])
+    return c5, y
+
+
+def objects_for_tiles(tiles, cut, n0=300):
+    """(B, N) for an operator test at a tile count: B objects of N points, N % 32 != 0, that fill exactly `tiles` tiles of 128 rows, the
+    last one partial; when the last `cut` tiles are cut into single channel blocks, an object boundary off the 32-row grid lies inside
+    them (waves and cut tiles straddle objects) -- where a single tile is cut, that takes objects of fewer than 128 points"""
+    n0 = 40 if 0 < cut * 128 <= n0 else n0
+    for N in range(n0, 2 * n0):
+        for B in ((tiles - 1) * 128 // N + 1, tiles * 128 // N):          # the fewest and the most objects of N points that fit
+            M, c0 = B * N, (tiles - cut) * 128
+            straddle = not cut or any(b * N > c0 and (b * N) % 32 for b in range(1, B))
+            if N % 32 and -(-M // 128) == tiles and M % 128 and straddle:
+                return B, N
+    raise AssertionError("no object size for %d tiles" % tiles)
+
+
+def checked_objects(B, N, first_row):
+    """the objects an fp64 restatement of a per-object kernel needs: the first, one in the middle, the last, and every object with a row
+    at or past first_row (the rows of the cut tiles)"""
+    return sorted({0, B // 2, B - 1} | set(range(min(first_row // N, B - 1), B)))
+
+
 def synth_eval_results(seed, n_img=40):
     """A synthetic ``final_results`` list in the evaluater's format (evaluater/RT_TDA_Evaluater.py:99-105): per image a few
     ground-truth instances of the six NOCS classes, predictions = perturbed ground truth + false positives + misses."""
