@@ -1041,6 +1041,68 @@ int tgp_bn_eval_bwd_pooled(const float *dpool, int ldp, const int32_t *argrow, i
                            int C, const float *mean, const float *var, float eps, const float *gamma, const float *beta, int act, float slope,
                            float *dx, int lddx, float *dgamma, float *dbeta, float *workspace, tgp_stream_t stream);
 
+/* ---- the training batch's random draws on the device (csrc/draws.hip; new symbols, ABI 8 unchanged) ----------------------------
+ * datasets/load_data.py train_batch(draws='device').  Every draw is a pure function of (seed, key, site, counter): the four words
+ * of Philox-4x32-10 with Philox key (seed low, seed high) and Philox counter (counter, site, key low, key high); `keys` (D) are
+ * the items' 64-bit keys.  Transforms: float32 uniform (w >> 8) * 2^-24; float64 uniform ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53;
+ * normals by Box-Muller on 24-bit uniforms.  Permutations: one Philox word (site, counter 0, word 0) keys the four-round
+ * Feistel bijection tgp_cloud_sample walks; element i of the permutation of [0, total) is that bijection cycle-walked from i.
+ * Sites: */
+#define TGP_SITE_HOST 0      /* the per-item scalars, drawn on the host from the same words (datasets/device_draws.py) */
+#define TGP_SITE_BAND 1      /* defor_2D's choice over the band */
+#define TGP_SITE_SEL2K 2     /* _sample_points(PC, 2048) */
+#define TGP_SITE_SEL1K 3     /* _sample_points(PC, 1024) */
+#define TGP_SITE_DEFOR 4     /* defor_3D_pc's uniforms; counter = the selected point's slot */
+#define TGP_SITE_NOISE 5     /* PcJitter's normals; counter = point */
+#define TGP_SITE_DROP 6      /* PcRandomDropout's uniforms; counter = point */
+#define TGP_SITE_SHUFFLE 7   /* pc_sampler's shuffle */
+#define TGP_DRAW_MAX_ITEMS 4096
+#define TGP_DRAW_MAX_TOTAL 65536
+/* an item's status (tgp_draw_alive): the reference's reasons to abandon it (load_data.py:262-265, 288), the deformed cloud below
+ * 26 points (the host path raises there), a window the host refused (source_tables) */
+#define TGP_ITEM_ALIVE 0
+#define TGP_ITEM_NO_DEPTH 1     /* n_depth <= 1 */
+#define TGP_ITEM_NO_MASK 2      /* n_valid <= 1 */
+#define TGP_ITEM_FEW_POINTS 3   /* fewer than min_points after the cut */
+#define TGP_ITEM_BELOW_26 4     /* counts[2] < 0 */
+#define TGP_ITEM_WINDOW 5       /* forced by the host */
+/* out (D, n_counters, 4) uint32: the words of counters 0 .. n_counters - 1 at `site` (tests; the recorder of the host's golden words) */
+int tgp_draw_words(const uint64_t *keys, int D, uint64_t seed, uint32_t site, int n_counters, uint32_t *out, tgp_stream_t stream);
+/* defor_2D's draws (data_augmentation.py:327-336) from tgp_roi_band's band_counts (D, 3), read on the device: defor_on[d] = (validity
+ * == 0 or n_depth > 1 and n_valid > 1) and not u[d] > pro and l >= 1 (u (D) float64: defor_2D's rand(), a per-item scalar); drop_bits
+ * (D, drop_words) every word written: bit r set iff r < l and rank r's position in the item's permutation of [0, l) is below l / 2
+ * -- exactly l / 2 bits, a uniformly chosen subset as choice(l, l // 2, replace=False).  drop_words a multiple of 8 in [8, 2048];
+ * l is taken as min(l, 32 drop_words). */
+int tgp_draw_band_subset(const int *band_counts, const double *u, double pro, const uint64_t *keys, uint64_t seed, int D, int validity,
+                         int *defor_on, uint32_t *drop_bits, int drop_words, tgp_stream_t stream);
+/* _item_total's rules (load_data.py of this package) on tgp_roi_cloud_ex / _defor's counts (D, 3): status (D) TGP_ITEM_* (forced (D)
+ * or NULL: a non-zero entry is the item's status whatever its counts), slot_item (B) the first B alive items in item order, the
+ * alive ones repeated cyclically when fewer than B are alive, -1 when none is; n_alive (1) = min(alive, B).  B <= D <=
+ * TGP_DRAW_MAX_ITEMS.  One workgroup. */
+int tgp_draw_alive(const int *counts, const int *forced, int D, int B, int min_points, int *status, int *slot_item, int *n_alive,
+                   tgp_stream_t stream);
+/* sel (D, n_out) int32 selections of [0, total_d), total_d = totals[d * ld_total] read on the device (totals NULL: total_const), taken
+ * as min(total_d, TGP_DRAW_MAX_TOTAL); total_d <= 0: zeros.  shuffle_always == 0, _sample_points (load_data.py:366-380): i % total
+ * when total < n_out, i when equal, else the first n_out elements of the item's permutation.  shuffle_always != 0, pc_sampler
+ * (data_augmentation.py:12-16): element i % total of the permutation whatever total is (total < n_out: the shuffled rows, repeated). */
+int tgp_draw_selection(const int *totals, int ld_total, int total_const, const uint64_t *keys, uint64_t seed, uint32_t site, int D,
+                       int n_out, int shuffle_always, int32_t *sel, tgp_stream_t stream);
+/* the per-point draws of D items of N points, each buffer optional: defor (D, N, 3) float32 uniforms in [0, 1); noise (D, N, 3) float32
+ * normals of deviation std clamped to [-clip, clip]; drop_u (D, N) float64 uniforms in [0, 1) */
+int tgp_draw_fill(const uint64_t *keys, uint64_t seed, int D, int N, float *defor, float *noise, float std, float clip, double *drop_u,
+                  tgp_stream_t stream);
+/* rows by slot, n tensors in one launch: dst[k] (B, row_words[k]) = src[k] (D, row_words[k]) rows slot_item[s] (32-bit words); a slot
+ * whose item is -1 gets zeros */
+#define TGP_GATHER_SLOTS_MAX 24
+typedef struct tgp_gather_slots_args {
+    const int32_t *slot_item;              /* (B) */
+    int B, D, n;
+    const void *src[TGP_GATHER_SLOTS_MAX];
+    void *dst[TGP_GATHER_SLOTS_MAX];
+    int row_words[TGP_GATHER_SLOTS_MAX];
+} tgp_gather_slots_args;
+int tgp_gather_slots(const tgp_gather_slots_args *args, tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ end), the median of every part above, and the host time of prefetch() and of the
 Writes profiles/train_loop_time.json.
 
     python scripts/train_loop_time.py [--steps 200] [--pd-steps 30] [--warmup 3] [--out profiles/train_loop_time.json]
+    python scripts/train_loop_time.py --device-draws [--steps 200]      # draws host / device at B = 32 and 256 (HostSplit, main_draws)
 """
 import argparse
 import json
@@ -140,8 +141,8 @@ def instrument(tr, marks):
     tr.optimizer.step = optimizer_step
     fin = tr.finish_step
 
-    def finish_step(total=None):
-        ok = fin(total=total)
+    def finish_step(total=None, **kw):
+        ok = fin(total=total, **kw)
         marks.mark("end")
         return ok
     tr.finish_step = finish_step
@@ -189,14 +190,148 @@ def run(pool, tables, persistence, prefetch, steps, warmup, model_save):
     return out
 
 
+class HostSplit(object):
+    """splits the host time of prefetch(): wraps the loader's functions that upload (and, in the host mode, read back) and the ones
+    that draw; times the new device launches with HIP events"""
+    UPLOAD = {"host": ("_roi_records",), "device": ("_upload_frames", "_stack_labels")}
+    DRAWS = {"host": ("defor_draws", "_selection"), "device": ("_item_scalars",)}
+
+    def __init__(self, draws):
+        from tgpose_amd import ops
+        from tgpose_amd.datasets import data_augmentation as da, load_data as ld
+        self.t = dict(upload=0.0, draws=0.0)
+        self.rows, self.events, self.kernel_us, self._undo = [], [], [], []
+        for name in self.UPLOAD[draws]:
+            self._host(ld, name, "upload")
+        for name in self.DRAWS[draws]:
+            self._host(ld, name, "draws", inside="upload" if name == "defor_draws" else None)
+        if draws == "host":
+            for n in ("generate_aug_parameters", "base_draws", "sampler_perm"):
+                self._host(da, n, "draws")
+            for cls in (da.PcJitter, da.PcRandomCutout, da.PcRandomCrop, da.PcRandomDropout):
+                self._host(cls, "draw", "draws")
+        for n in ("draw_band_subset", "draw_alive", "draw_selection", "draw_fill", "gather_slots"):
+            self._dev(ops, n)
+
+    def _host(self, mod, name, bucket, inside=None):
+        fn = getattr(mod, name)
+
+        def w(*a, **kw):
+            t0 = time.perf_counter()
+            try:
+                return fn(*a, **kw)
+            finally:
+                dt = time.perf_counter() - t0
+                self.t[bucket] += dt
+                if inside is not None:                 # called from within another bucket's function: not counted twice
+                    self.t[inside] -= dt
+        setattr(mod, name, w)
+        self._undo.append((mod, name, fn))
+
+    def _dev(self, mod, name):
+        fn = getattr(mod, name)
+
+        def w(*a, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = fn(*a, **kw)
+            e1.record()
+            self.events.append((e0, e1))
+            return r
+        setattr(mod, name, w)
+        self._undo.append((mod, name, fn))
+
+    def batch_done(self, prefetch_ms):
+        self.rows.append((1e3 * self.t["upload"], 1e3 * self.t["draws"], prefetch_ms))
+        self.t = dict(upload=0.0, draws=0.0)
+        self.kernel_us.append(self.events)
+        self.events = []
+
+    def close(self):
+        for mod, name, fn in reversed(self._undo):
+            setattr(mod, name, fn)
+
+    def summary(self):
+        r = np.asarray(self.rows[1:])
+        med = lambda x: float(np.median(x))
+        out = dict(host_upload_ms=med(r[:, 0]), host_draws_ms=med(r[:, 1]), host_other_ms=med(r[:, 2] - r[:, 0] - r[:, 1]))
+        if any(self.kernel_us):
+            out["draw_kernels_us"] = med([1e3 * sum(a.elapsed_time(b) for a, b in ev) for ev in self.kernel_us[1:] if ev])
+        return out
+
+
+def run_draws(pool, tables, draws, batch, steps, warmup, model_save):
+    """one run of the device-draws comparison: prefetch on, persistence off, ``draws`` 'host' or 'device' at batch size ``batch``"""
+    global B
+    from tgpose_amd.datasets import load_data as ld
+    keep, B = B, batch
+    real = ld.TrainBatches
+
+    def batches(items, batch_size, **kw):
+        if draws == "device":
+            kw.update(draws="device", spares=2, seed=5)
+        return real(items, batch_size, **kw)
+    ld.TrainBatches = batches
+    split = HostSplit(draws)
+    timed_it = Timed.__iter__
+
+    def it_with_split(self):
+        it = timed_it(self)
+        pre = it.prefetch
+
+        def prefetch():
+            n = len(self.marks.host_prefetch)
+            pre()
+            if len(self.marks.host_prefetch) > n:
+                split.batch_done(self.marks.host_prefetch[-1])
+        it.prefetch = prefetch
+        return it
+    Timed.__iter__ = it_with_split
+    try:
+        out = run(pool, tables, False, True, steps, warmup, model_save)
+    finally:
+        ld.TrainBatches, Timed.__iter__, B = real, timed_it, keep
+        split.close()
+    out.update(draws=draws, **split.summary())
+    return out
+
+
+def main_draws(a):
+    """profiles/train_loop_device_draws.json: B = 32 and 256, draws host / device alternating (twice each), prefetch on, persistence
+    off; the host mode here is the code path the draws='device' mode leaves untouched"""
+    pool, tables = item_pool()
+    rows = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for batch, steps in ((32, a.steps), (256, a.steps)):
+            for rep in range(2):
+                for draws in ("host", "device"):
+                    r = run_draws(pool, tables, draws, batch, steps, a.warmup, tmp)
+                    r["rep"] = rep
+                    print(json.dumps(r), flush=True)
+                    rows.append(r)
+    out = dict(device=torch.cuda.get_device_name(0), arch=torch.cuda.get_device_properties(0).gcnArchName, runs=rows,
+               note="RL_TDA_train over TrainBatches (roi_mask_pro 0.5, category tables, prefetch on, persistence off), graphed step, Ranger; "
+                    "host_prefetch_ms = host_upload_ms (host mode: _roi_records, i.e. uploads, source tables, both read-backs and the ROI "
+                    "launches; device mode: the frame and label uploads) + host_draws_ms + host_other_ms; draw_kernels_us: device time of "
+                    "the tgp_draw_* and tgp_gather_slots launches per batch; runs alternate host / device in one process")
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--pd-steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_loop_time.json"))
+    ap.add_argument("--device-draws", action="store_true", help="the host / device draws comparison (train_loop_device_draws.json)")
     a = ap.parse_args()
     assert torch.cuda.is_available()
+    if a.device_draws:
+        if a.out.endswith("train_loop_time.json"):
+            a.out = os.path.join(os.path.dirname(a.out), "train_loop_device_draws.json")
+        return main_draws(a)
     pool, tables = item_pool()
     rows = []
     with tempfile.TemporaryDirectory() as tmp:

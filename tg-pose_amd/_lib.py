@@ -212,6 +212,17 @@ PD_STATUS = {1: "TGP_PD_ETETS (tetrahedron / simplex storage)", 2: "TGP_PD_ECAVI
              5: "TGP_PD_ECOLUMNS (H1 column storage)", 6: "TGP_PD_ERANGE (coordinate not finite or below the exact grid)",
              7: "TGP_PD_EFLAT (fewer than 4 affinely independent points)", 8: "TGP_PD_EINTERNAL"}
 
+class GatherSlotsArgs(ctypes.Structure):
+    """struct tgp_gather_slots_args (include/tgpose.h)"""
+    _fields_ = [("slot_item", c_vp), ("B", c_int), ("D", c_int), ("n", c_int),
+                ("src", c_vp * 24), ("dst", c_vp * 24), ("row_words", c_int * 24)]
+
+
+GATHER_SLOTS_MAX, DRAW_MAX_ITEMS, DRAW_MAX_TOTAL = 24, 4096, 65536
+SITE_HOST, SITE_BAND, SITE_SEL2K, SITE_SEL1K, SITE_DEFOR, SITE_NOISE, SITE_DROP, SITE_SHUFFLE = range(8)
+ITEM_ALIVE, ITEM_NO_DEPTH, ITEM_NO_MASK, ITEM_FEW_POINTS, ITEM_BELOW_26, ITEM_WINDOW = range(6)
+c_u64, c_u32, c_f64 = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double
+
 SIGNATURES = {
     "tgp_version": (c_int, []),
     "tgp_graph_node_counts": (c_int, [c_vp, c_vp]),
@@ -359,6 +370,12 @@ SIGNATURES = {
                                 c_vp, c_vp]),
     "tgp_bn_eval_bwd_pooled": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_f32, c_vp, c_vp, c_int,
                                        c_f32, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "tgp_draw_words": (c_int, [c_vp, c_int, c_u64, c_u32, c_int, c_vp, c_vp]),
+    "tgp_draw_band_subset": (c_int, [c_vp, c_vp, c_f64, c_vp, c_u64, c_int, c_int, c_vp, c_vp, c_int, c_vp]),
+    "tgp_draw_alive": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "tgp_draw_selection": (c_int, [c_vp, c_int, c_int, c_vp, c_u64, c_u32, c_int, c_int, c_int, c_vp, c_vp]),
+    "tgp_draw_fill": (c_int, [c_vp, c_u64, c_int, c_int, c_vp, c_vp, c_f32, c_f32, c_vp, c_vp]),
+    "tgp_gather_slots": (c_int, [ctypes.POINTER(GatherSlotsArgs), c_vp]),
 }
 
 ABI_VERSION = 8

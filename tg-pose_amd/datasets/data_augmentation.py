@@ -233,20 +233,27 @@ def view_inputs(records, n, device, operators):
                 cutout_min_points=cut.min_num_points)
 
 
-def defor_2D(roi_mask, rand_r=2, rand_pro=0.3, rng=np.random):
+def defor_2D(roi_mask, rand_r=2, rand_pro=0.3, rng=np.random, draws="host", seed=None, key=0):
     """The reference's mask deformation (data_augmentation.py:319-342) on a GPU (S,S) or (1,S,S) 0/1 float32 mask, S in {64, 128,
     256} -> the deformed (S,S) mask (a new tensor).  Draws as the reference: rng.rand(), then, when it is not > rand_pro and the
     band is not empty, rng.choice(l, l // 2, replace=False).  rand_r is inert, as in the reference (it reaches cv2.erode / dilate
     as their dst: one iteration).  Runs the training loader's kernels with the mask as a frame, identity source tables and unit
-    depth (tgp_roi_band, tgp_roi_cloud_defor without the cut) and scatters the records back; one read-back (the band size)."""
+    depth (tgp_roi_band, tgp_roi_cloud_defor without the cut) and scatters the records back; one read-back (the band size).
+    draws='device': rand() from (seed, key)'s host stream and the choice drawn on the device from the band size it never reads back
+    (tgp_draw_band_subset; the reference's distributions, not its stream; rng is not consumed); no read-back at all -- the mask's
+    values are then not checked to be 0 / 1 (a value other than 1 counts as 0)."""
     from .load_data import defor_draws
+    if draws not in ("host", "device"):
+        raise ValueError("draws must be 'host' or 'device'")
+    if draws == "device" and seed is None:
+        raise ValueError("draws='device' needs a seed")
     if not (torch.is_tensor(roi_mask) and roi_mask.is_cuda and roi_mask.dtype == torch.float32):
         raise TypeError("defor_2D: roi_mask must be a float32 GPU tensor")
     S = roi_mask.shape[-1]
     if not (roi_mask.dim() in (2, 3) and roi_mask.shape[-2] == S and roi_mask.numel() == S * S and S in (64, 128, 256)):
         raise ValueError("defor_2D: roi_mask must be (S,S) or (1,S,S) with S in {64, 128, 256}")
     m = roi_mask.reshape(S, S)
-    if not bool(((m == 0) | (m == 1)).all()):
+    if draws == "host" and not bool(((m == 0) | (m == 1)).all()):
         raise ValueError("defor_2D: roi_mask must hold only 0 and 1")
     dev = m.device
     i32 = lambda a: torch.as_tensor(a, dtype=torch.int32, device=dev)
@@ -254,6 +261,23 @@ def defor_2D(roi_mask, rand_r=2, rand_pro=0.3, rng=np.random):
     depth = torch.ones(1, S, S, dtype=torch.int16, device=dev)
     tabs = torch.arange(S, dtype=torch.int32, device=dev).repeat(1, 2, 1).contiguous()
     args = (depth, mask8, torch.zeros(1, dtype=torch.int64, device=dev), i32([1]), i32([0]), None)
+    cap = S * S
+    if draws == "device":
+        from . import device_draws as dd
+        st = dd.item_streams(seed, [int(key) & (2 ** 64 - 1)])[0]
+        if st.seek(st.DEFOR).rand() > rand_pro:              # the host's scalar decides alone; an empty band changes nothing
+            return m.clone()
+        keys = torch.tensor([int(key) & (2 ** 64 - 1)], dtype=torch.uint64).view(torch.int64).to(dev)
+        band = ops.roi_band(*args, roi_size=S, tables=tabs, mask_val=i32([1]))
+        on, bits = ops.draw_band_subset(band, torch.zeros(1, dtype=torch.float64, device=dev), 1.0, keys, seed, validity=False,
+                                        drop_words=cap // 32)
+        rr = ops.roi_cloud(*args, torch.tensor([[1.0, 1.0, 0.0, 0.0]], device=dev), roi_size=S, tables=tabs, mask_val=i32([1]),
+                           cut_frac=-1.0, defor=(on, bits))
+        pix = (rr.recs[0] >> 16) & 0xffff
+        live = torch.arange(cap, device=dev) < rr.counts[0, 2]
+        out = torch.zeros(cap + 1, dtype=torch.float32, device=dev)
+        out.scatter_(0, torch.where(live, pix, cap).long(), 1.0)
+        return out[:cap].reshape(S, S)
     band = ops.roi_band(*args, roi_size=S, tables=tabs, mask_val=i32([1])).cpu().numpy()
     band[0, :2] = 2                   # the draws of a mask, not of an item: no validity test
     on, bits = defor_draws(band, float(rand_pro), rng)

@@ -24,7 +24,11 @@ the batch (datasets/data_augmentation.py of this package), with the draws made o
 (``tgp_roi_band``: per item n_depth, the undeformed n_valid, the band size l), ONE read-back, the host's draws, then the deformed
 compaction (``tgp_roi_cloud_defor``) in place of ``tgp_roi_cloud_ex``.  ``dzi=True`` draws ``aug_bbox_DZI``
 (tools/dataset_utils.py:24-61) from the same ``rng`` (``aug_bbox_dzi``).  Out of scope, as in DESIGN.md section 8: reading
-files."""
+files.
+
+``draws='device'`` (train_batch, train_clouds, TrainBatches; opt-in) makes every draw a function of (seed, item key, site, counter)
+instead of a position in ``rng`` / ``gen``, the per-point ones and the permutations on the device (csrc/draws.hip), and reads nothing
+back: the reference's distributions, not its stream ("Draws on the device")."""
 import numpy as np
 import torch
 
@@ -82,11 +86,22 @@ def source_tables(bbox_center, scale, img_size=256):
     X0, Y0 = rnd((i01 * x + b1) * scale_ab) + half, rnd((i11 * x + b2) * scale_ab) + half      # per ROI row
     # rot = 0: the cross terms i01, i10 are the solver's rounding noise (~1e-17), so X0 does not depend on the row nor bdelta on the
     # column and the map is separable; a window for which that noise moves a rounding tie is refused rather than approximated
-    sx2, sy2 = (X0[:, None] + adelta[None, :]) >> AB_BITS, (Y0[:, None] + bdelta[None, :]) >> AB_BITS      # OpenCV's map, all pixels
-    sx, sy = sx2[0], sy2[:, 0]
-    if not (np.array_equal(sx2, np.broadcast_to(sx[None, :], sx2.shape)) and np.array_equal(sy2, np.broadcast_to(sy[:, None], sy2.shape))):
+    # OpenCV's map of pixel (r, c) is ((X0[r] + adelta[c]) >> 10, (Y0[r] + bdelta[c]) >> 10): whether the first depends on r (the second
+    # on c) is decided by the DISTINCT values of X0 (bdelta) -- a handful, the noise's -- so only those rows (columns) are walked
+    tabs = _separable_walk(X0, adelta, Y0, bdelta)
+    if tabs is None:
         raise ValueError("source_tables: the walk is not separable for this window (rot = 0 expected)")
+    sx, sy = tabs
     return np.clip(np.stack([sx, sy]), -32768, 32767).astype(np.int32)       # (OpenCV stores the map as shorts)
+
+
+def _separable_walk(X0, adelta, Y0, bdelta):
+    """(source column per ROI column, source row per ROI row) of the map (r, c) -> ((X0[r] + adelta[c]) >> 10, (Y0[r] + bdelta[c]) >> 10),
+    or None when the column depends on r or the row on c.  Only the rows of the distinct X0 (the columns of the distinct bdelta) are
+    walked: which rows differ is decided by the values alone."""
+    sx, sy = (X0[0] + adelta) >> AB_BITS, (Y0 + bdelta[0]) >> AB_BITS
+    sx2, sy2 = (np.unique(X0)[:, None] + adelta[None, :]) >> AB_BITS, (Y0[:, None] + np.unique(bdelta)[None, :]) >> AB_BITS
+    return (sx, sy) if (sx2 == sx[None, :]).all() and (sy2 == sy[:, None]).all() else None
 
 
 def aug_bbox_dzi(bbox, im_H, im_W, rng=np.random, dzi_type=None, scale_ratio=None, shift_ratio=None, pad_scale=None):
@@ -164,7 +179,8 @@ def _selection(total, n_pts, rng):
     return np.arange(n_pts)
 
 
-def train_clouds(items, img_size=256, rng=np.random, device="cuda", min_points=50, roi_mask_pro=None, roi_mask_r=3, dzi=False):
+def train_clouds(items, img_size=256, rng=np.random, device="cuda", min_points=50, roi_mask_pro=None, roi_mask_r=3, dzi=False,
+                 draws="host", seed=None, keys=None, batch_size=None):
     """items: list of dicts -- 'depth' (H,W) uint16 (load_depth's output), 'mask' (H,W) uint8 instance-id image (the reference reads
     ``cv2.imread(mask_path)[:, :, 2]``), 'inst_id' int, 'camK' (3,3) float32, and the window: 'bbox_center' (cx, cy) + 'scale' (the
     caller's aug_bbox_DZI draw) or 'bbox' (y1, x1, y2, x2) for the un-augmented window.  All frames share (H, W).
@@ -174,10 +190,18 @@ def train_clouds(items, img_size=256, rng=np.random, device="cuda", min_points=5
     dzi=True: the window is drawn by aug_bbox_dzi from each item's 'bbox' (FLAGS.DZI_*), all items first.  roi_mask_pro (a float;
     None: no deformation, no draw): defor_2D on each item's mask after one more read-back (defor_draws, after the DZI draws);
     roi_mask_r is inert, as in the reference (it reaches cv2.erode / dilate as their dst).  For one item the stream is the
-    reference's from aug_bbox_DZI on; for a batch, every item's DZI and deformation draws precede the first permutation."""
+    reference's from aug_bbox_DZI on; for a batch, every item's DZI and deformation draws precede the first permutation.
+    draws='device' (seed, keys, batch_size as train_batch's): the same draws as train_batch(draws='device') makes up to the second
+    selection, nothing read back -> dict PC (B,2048,3), pcl_in (B,1024,3), n_alive, status, item_index."""
     dev = torch.device(device)
+    if draws not in ("host", "device"):
+        raise ValueError("draws must be 'host' or 'device'")
     if not items:
         return []
+    if draws == "device":
+        from . import data_augmentation as da
+        return _train_batch_device(items, seed, keys, batch_size, img_size, dev, min_points, da.default_operators(), False, roi_mask_pro,
+                                   roi_mask_r, dzi, clouds_only=True)
     rr, counts = _roi_records(items, img_size, dev, rng, roi_mask_pro, roi_mask_r, dzi)
     deformed = roi_mask_pro is not None
     D = len(items)
@@ -200,18 +224,7 @@ def train_clouds(items, img_size=256, rng=np.random, device="cuda", min_points=5
 def _roi_records(items, img_size, dev, rng=np.random, roi_mask_pro=None, roi_mask_r=3, dzi=False):
     """the items' ROI clouds as records (one tgp_roi_cloud_ex launch) and their counts (one 12-byte read-back per item); with
     roi_mask_pro, the band launch, its read-back, the deformation draws and one tgp_roi_cloud_defor launch instead"""
-    if roi_mask_pro is not None and not (isinstance(roi_mask_pro, (float, int)) and 0.0 <= float(roi_mask_pro) <= 1.0):
-        raise ValueError("roi_mask_pro must be None or a probability in [0, 1]")
-    if not (isinstance(roi_mask_r, (int, np.integer)) and roi_mask_r >= 0):
-        raise ValueError("roi_mask_r must be a non-negative int (it is inert, as in the reference)")
-    if dzi and any("bbox" not in it for it in items):
-        raise ValueError("dzi=True draws the window from each item's 'bbox'")
-    H, W = items[0]["depth"].shape
-    for it in items:            # every item is checked before the first draw: a refused batch leaves rng untouched
-        if it["depth"].shape != (H, W) or it["mask"].shape != (H, W) or it["depth"].dtype != np.uint16 or it["mask"].dtype != np.uint8:
-            raise ValueError("every item needs a uint16 depth image and a uint8 instance mask of one common (H,W)")
-        if not 0 < int(it["inst_id"]) < 256:
-            raise ValueError("inst_id must be a non-zero byte value")
+    H, W = _check_items(items, roi_mask_pro, roi_mask_r, dzi)
     tabs, camk, mval = [], [], []
     for it in items:
         if dzi:
@@ -241,6 +254,23 @@ def _roi_records(items, img_size, dev, rng=np.random, roi_mask_pro=None, roi_mas
     return rr, rr.counts.cpu().numpy()
 
 
+def _check_items(items, roi_mask_pro, roi_mask_r, dzi):
+    """the argument checks of a batch of items, before the first draw -> (H, W)"""
+    if roi_mask_pro is not None and not (isinstance(roi_mask_pro, (float, int)) and 0.0 <= float(roi_mask_pro) <= 1.0):
+        raise ValueError("roi_mask_pro must be None or a probability in [0, 1]")
+    if not (isinstance(roi_mask_r, (int, np.integer)) and roi_mask_r >= 0):
+        raise ValueError("roi_mask_r must be a non-negative int (it is inert, as in the reference)")
+    if dzi and any("bbox" not in it for it in items):
+        raise ValueError("dzi=True draws the window from each item's 'bbox'")
+    H, W = items[0]["depth"].shape
+    for it in items:            # every item is checked before the first draw: a refused batch leaves rng untouched
+        if it["depth"].shape != (H, W) or it["mask"].shape != (H, W) or it["depth"].dtype != np.uint16 or it["mask"].dtype != np.uint8:
+            raise ValueError("every item needs a uint16 depth image and a uint8 instance mask of one common (H,W)")
+        if not 0 < int(it["inst_id"]) < 256:
+            raise ValueError("inst_id must be a non-zero byte value")
+    return H, W
+
+
 def _item_total(counts, min_points, deformed=False):
     """the cut cloud's point count, or None for an item the reference abandons.  deformed: the counts of tgp_roi_cloud_defor, whose
     third entry is -(1 + the deformed point count) below 26 points (tgp_roi_cloud_ex writes -1 and the count is n_valid)"""
@@ -262,7 +292,7 @@ _POSE_KEYS = ("rotation", "translation", "fsnet_scale")
 
 
 def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min_points=50, operators=None, persistence=False,
-                roi_mask_pro=None, roi_mask_r=3, dzi=False):
+                roi_mask_pro=None, roi_mask_r=3, dzi=False, draws="host", seed=None, keys=None, batch_size=None, keep_draws=False):
     """``train_clouds`` plus the reference's two augmentations (load_data.py:333-350): the batch the trainer's step reads.
 
     items: ``train_clouds``' dicts, each also carrying its labels 'rotation' (3,3), 'translation' (3,), 'fsnet_scale' (3,) (the
@@ -284,8 +314,21 @@ def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min
     item_index (B,) int64; and aug_name, a list of the operators' names.
     persistence=True also computes the reference's compute_pd targets from pcl_in (load_data.py:343): pdh1 and pdh2 (B, 2500)
     float32, by ops.persistence_images (no random draws, so the draw order above is unchanged); items that carry 'pdh1' or 'pdh2'
-    themselves are refused."""
+    themselves are refused.
+
+    draws='device' (opt-in; 'host' is everything above, unchanged): no host read between the items and the returned batch.  Every
+    draw is a pure function of (seed, keys[d], draw site, counter) -- Philox-4x32-10, csrc/draws.hip and device_draws.py -- so an
+    item's rows depend on neither its slot, its batch nor rng / gen (not consumed); the reference's distributions, not its
+    stream.  ``keys``: 64 bits per item (default: its position).  ``batch_size`` = B <= len(items): the batch holds the first B
+    items, in item order, that the reference would keep (the rest are spares); with fewer than B alive the alive ones repeat
+    cyclically, with none the rows are zeros.  An item whose deformed cloud has fewer than 26 points (the host path raises there) or
+    whose drawn window source_tables refuses counts as abandoned.  -> the dict above, all on the device, with aug_op (B,) int32
+    (the OPERATOR_NAMES index) in place of aug_name, item_index (B,) int64 (the item in each slot, -1 without one), n_alive ()
+    int32 = min(alive items, B) and status (len(items),) int32 (TGP_ITEM_* of include/tgpose.h).  keep_draws=True adds '_draws':
+    the draw buffers (DRAW_KEYS, one row per item) that _train_batch_from_draws replays."""
     from . import data_augmentation as da
+    if draws not in ("host", "device"):
+        raise ValueError("draws must be 'host' or 'device'")
     if persistence and any("pdh1" in it or "pdh2" in it for it in items):
         raise ValueError("train_batch: persistence=True computes pdh1 / pdh2; the items must not carry them")
     dev = torch.device(device)
@@ -294,6 +337,9 @@ def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min
         raise ValueError("train_batch: the four operators of OPERATOR_NAMES are expected")
     if not items:
         raise ValueError("train_batch: no items")
+    if draws == "device":
+        return _train_batch_device(items, seed, keys, batch_size, img_size, dev, min_points, ops_, persistence, roi_mask_pro, roi_mask_r,
+                                   dzi, keep_draws=keep_draws)
     rr, counts = _roi_records(items, img_size, dev, rng, roi_mask_pro, roi_mask_r, dzi)
     deformed = roi_mask_pro is not None
     keep, sel2k, p1k, shuf, recs, names, defer = [], [], [], [], [], [], []
@@ -351,6 +397,205 @@ def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min
               aug_counts=out["counts"], item_index=up(np.asarray(keep, dtype=np.int64)), aug_name=names)
     if persistence:
         db["pdh1"], db["pdh2"] = ops.persistence_images(pcl_in)
+    return db
+
+
+# ---------------------------------------------------------------------------------------- draws='device': no read between the items
+# and the step.  Every draw is a function of (seed, item key, site, counter) (device_draws.py, csrc/draws.hip): the per-item scalars are
+# made on the host from site 0, everything whose size or existence depends on a device result -- or that scales with the point
+# count -- on the device, into the buffers the host path uploads.  All D = batch_size + spares items run through every launch; the
+# batch's slots are filled from the alive ones at the end (tgp_draw_alive, tgp_gather_slots).
+_DROP_WORDS = 2048          # 65536 band ranks: every ROI size
+
+
+def _uploader(dev):
+    """host array -> device tensor without stalling the host on a CUDA device: through pinned memory, non-blocking"""
+    def up(a):
+        t = torch.from_numpy(np.ascontiguousarray(a))
+        return t.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else t.to(dev)
+    return up
+
+
+def _upload_frames(items, tabs, up, H, W):
+    """the frames and per-item descriptors of tgp_roi_band / tgp_roi_cloud_* -> (args, tables, mask_val, camk)"""
+    D = len(items)
+    camk = []
+    for it in items:
+        K = np.asarray(it["camK"], dtype=np.float32)
+        camk.append([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
+    depth = up(np.stack([it["depth"] for it in items]).view(np.int16))
+    masks = up(np.stack([it["mask"] for it in items]).reshape(-1))
+    args = (depth, masks, up(np.arange(D, dtype=np.int64) * (H * W)), up(np.ones(D, dtype=np.int32)), up(np.arange(D, dtype=np.int32)), None)
+    return args, up(np.asarray(tabs, dtype=np.int32)), up(np.asarray([int(it["inst_id"]) for it in items], dtype=np.int32)), \
+        up(np.asarray(camk, dtype=np.float32))
+
+
+def _stack_labels(items, up):
+    lab = {k: [it[k] for it in items] for k in items[0] if k not in _IMAGE_KEYS}
+    for k in _POSE_KEYS + ("mean_shape", "sym_info", "model_point", "nocs_scale", "cat_id"):
+        if k not in lab:
+            raise ValueError("train_batch: every item needs %r" % k)
+    return {k: up(np.stack([np.asarray(v, dtype=np.float32) for v in lab[k]])) for k in lab}
+
+
+def _keyed_record(op, st):
+    """an operator's scalar draws from an item's stream; its per-point draws (noise, drop_u) are made on the device"""
+    from . import data_augmentation as da
+    if isinstance(op, da.PcJitter):
+        return da._record(da._lib.AUG_NONE if st.uniform() > op.p else da._lib.AUG_JITTER, 2048)
+    if isinstance(op, da.PcRandomDropout):
+        if op._skip(st):
+            return da._record(da._lib.AUG_NONE, 2048)
+        return da._record(da._lib.AUG_DROPOUT, 2048, drop_ratio=st.random_sample() * op.max_dropout_ratio)
+    return op.draw(2048, st, None)
+
+
+def _item_scalars(items, seed, keys, H, W, img_size, dzi, ops_):
+    """the per-item scalars of draws='device', from each item's stream (device_draws.ItemStream) -> dict of host arrays, D rows:
+    tabs, forced (TGP_ITEM_WINDOW where source_tables refused the window), u_defor, aug_bb, aug_rt_t, aug_rt_R, base (the six
+    PC_BasicAugment draws), op_index, op, drop_ratio, boxes"""
+    from . import data_augmentation as da, device_draws as dd
+    D = len(items)
+    sc = dict(tabs=np.zeros((D, 2, img_size), np.int32), forced=np.zeros(D, np.int32), u_defor=np.zeros(D), aug_bb=np.zeros((D, 3), np.float32),
+              aug_rt_t=np.zeros((D, 3), np.float32), aug_rt_R=np.zeros((D, 3, 3), np.float32), base=np.zeros((D, 6), np.float32),
+              op_index=np.zeros(D, np.int32), op=np.zeros(D, np.int32), drop_ratio=np.zeros(D), boxes=np.zeros((D, da._lib.AUGMENT_MAX_TRY, 6)))
+    for d, (it, st) in enumerate(zip(items, dd.item_streams(seed, keys))):
+        if dzi:
+            center, scale = aug_bbox_dzi(it["bbox"], H, W, st.seek(st.DZI))
+        elif "bbox_center" in it:
+            center, scale = it["bbox_center"], it["scale"]
+        else:
+            center, scale = window_without_dzi(it["bbox"], H, W)
+        try:
+            sc["tabs"][d] = source_tables(center, scale, img_size)
+        except ValueError:                       # not separable: the item is abandoned (its table stays pixel (0, 0))
+            sc["forced"][d] = da._lib.ITEM_WINDOW
+        sc["u_defor"][d] = st.seek(st.DEFOR).rand()
+        sc["aug_bb"][d], sc["aug_rt_t"][d], sc["aug_rt_R"][d] = da.generate_aug_parameters(st.seek(st.PARAMS))
+        sc["base"][d] = st.seek(st.BASE).floats32(6)
+        k = st.seek(st.OP_INDEX).randint4()
+        rec = _keyed_record(ops_[k], st.seek(st.OPERATOR))
+        sc["op_index"][d], sc["op"][d], sc["drop_ratio"][d] = k, rec["op"], rec["drop_ratio"]
+        if rec["boxes"] is not None:
+            sc["boxes"][d] = rec["boxes"]
+    return sc
+
+
+def _view_limits(ops_):
+    from . import data_augmentation as da
+    for o in ops_:
+        if isinstance(o, (da.PcRandomCrop, da.PcRandomCutout)) and not 0 <= o.max_try_num < da._lib.AUGMENT_MAX_TRY:
+            raise ValueError("max_try_num must be in [0, %d)" % da._lib.AUGMENT_MAX_TRY)
+    crop = next((o for o in ops_ if isinstance(o, da.PcRandomCrop)), da.PcRandomCrop())
+    cut = next((o for o in ops_ if isinstance(o, da.PcRandomCutout)), da.PcRandomCutout())
+    return dict(crop_max_try=crop.max_try_num, cutout_max_try=cut.max_try_num, crop_min_points=crop.min_num_points,
+                cutout_min_points=cut.min_num_points)
+
+
+DRAW_KEYS = ("tabs", "defor_on", "drop_bits", "aug_bb", "aug_rt_t", "aug_rt_R", "base", "op", "drop_ratio", "boxes", "sel2k", "p1k", "defor",
+             "noise", "drop_u", "shuf")
+
+
+def _augment_rows(rr, dr, lab, ops_, shuffle=None):
+    """the launches that follow the records, on every item's row, from the draws ``dr`` (device tensors under DRAW_KEYS): the 2048
+    selected points, tgp_augment, the two row gathers.  shuffle(counts) draws 'shuf' when dr has none (it needs the launch's M).
+    -> dict of (D, ...) tensors: pcl_in, aug_pcl_in (padded to 4 columns), rotation, translation, fsnet_scale, aug_flags, aug_counts,
+    shuf"""
+    from . import data_augmentation as da
+    D, dev = rr.recs.shape[0], rr.recs.device
+    pc2k = ops.cloud_select(rr, dr["sel2k"])
+    base = da._base_inputs(dr["base"], lab["rotation"], lab["translation"], lab["fsnet_scale"], lab["mean_shape"], lab["sym_info"],
+                           dr["aug_bb"], dr["aug_rt_t"], dr["aug_rt_R"], lab["cat_id"], lab["nocs_scale"], lab["model_point"], dr["defor"])
+    view = dict(op=dr["op"], noise=dr["noise"], drop_ratio=dr["drop_ratio"], drop_u=dr["drop_u"], boxes=dr["boxes"], **_view_limits(ops_))
+    out = ops.augment(pc2k, base=base, view=view, ld_out=4)
+    shuf = dr["shuf"] if "shuf" in dr else shuffle(out["counts"])
+    pcl = ops.gather_rows(out["pc"], dr["p1k"], torch.empty(D, 1024, 4, device=dev))
+    aug = ops.gather_rows(out["view"], shuf, torch.empty(D, 1024, 4, device=dev))
+    return dict(pcl_in=pcl, aug_pcl_in=aug, rotation=out["R"], translation=out["t"], fsnet_scale=out["s"], aug_flags=out["flags"],
+                aug_counts=out["counts"], shuf=shuf)
+
+
+def _train_batch_from_draws(items, dr, img_size=256, device="cuda", min_points=50, operators=None):
+    """The host path's launches on GIVEN draws: ``dr`` holds host arrays under DRAW_KEYS, one row per item ('defor_on' / 'drop_bits'
+    absent: no mask deformation) -- e.g. the buffers a draws='device' batch made, read back.  The counts are read back and the
+    reference's rules applied on the host (_item_total; an item for which the host path raises counts as abandoned here).
+    -> (dict of train_batch's device tensors, one row per KEPT item, list of the kept items)"""
+    from . import data_augmentation as da
+    dev = torch.device(device)
+    ops_ = da.default_operators() if operators is None else list(operators)
+    H, W = _check_items(items, None, 3, False)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    args, tabs, mval, camk = _upload_frames(items, dr["tabs"], up, H, W)
+    t = {k: up(np.asarray(v)) for k, v in dr.items() if k in DRAW_KEYS}
+    defor = (t["defor_on"], t["drop_bits"]) if "defor_on" in t else None
+    rr = ops.roi_cloud(*args, camk, roi_size=img_size, tables=tabs, mask_val=mval, cut_frac=0.15, defor=defor)
+    counts = rr.counts.cpu().numpy()
+    keep = []
+    for d in range(len(items)):
+        try:
+            if _item_total(counts[d], min_points, defor is not None) is not None:
+                keep.append(d)
+        except (ValueError, IndexError):
+            pass
+    rows = _augment_rows(rr, t, _stack_labels(items, up), ops_)
+    kt = up(np.asarray(keep, dtype=np.int64))
+    out = {k: v[kt].contiguous() for k, v in rows.items()}
+    out["pcl_in"], out["aug_pcl_in"] = out["pcl_in"][..., :3].contiguous(), out["aug_pcl_in"][..., :3].contiguous()
+    return out, keep
+
+
+def _train_batch_device(items, seed, keys, batch_size, img_size, dev, min_points, ops_, persistence, roi_mask_pro, roi_mask_r, dzi,
+                        keep_draws=False, clouds_only=False):
+    from . import data_augmentation as da
+    lib = da._lib
+    D = len(items)
+    B = D if batch_size is None else int(batch_size)
+    if seed is None:
+        raise ValueError("draws='device' needs a seed")
+    if not 1 <= B <= D <= lib.DRAW_MAX_ITEMS:
+        raise ValueError("draws='device': 1 <= batch_size <= len(items) <= %d" % lib.DRAW_MAX_ITEMS)
+    keys = np.arange(D, dtype=np.uint64) if keys is None else np.asarray([int(k) & (2 ** 64 - 1) for k in keys], dtype=np.uint64)
+    if keys.shape != (D,):
+        raise ValueError("draws='device': one key per item")
+    if dev.type != "cuda":
+        raise ValueError("draws='device' needs a CUDA device")
+    H, W = _check_items(items, roi_mask_pro, roi_mask_r, dzi)
+    sc = _item_scalars(items, seed, keys, H, W, img_size, dzi, ops_)
+    up = _uploader(dev)
+    args, tabs, mval, camk = _upload_frames(items, sc["tabs"], up, H, W)
+    keys_t = up(keys.view(np.int64))
+    dr = {k: up(sc[k]) for k in ("aug_bb", "aug_rt_t", "aug_rt_R", "base", "op", "drop_ratio", "boxes")}
+    dr["tabs"] = tabs
+    defor = None
+    if roi_mask_pro is not None:
+        band = ops.roi_band(*args, roi_size=img_size, tables=tabs, mask_val=mval)
+        defor = ops.draw_band_subset(band, up(sc["u_defor"]), float(roi_mask_pro), keys_t, seed, drop_words=_DROP_WORDS)
+        dr["defor_on"], dr["drop_bits"] = defor
+    rr = ops.roi_cloud(*args, camk, roi_size=img_size, tables=tabs, mask_val=mval, cut_frac=0.15, defor=defor)
+    status, slot, n_alive = ops.draw_alive(rr.counts, B, min_points, up(sc["forced"]))
+    dr["sel2k"] = ops.draw_selection(rr.counts[:, 2], keys_t, seed, lib.SITE_SEL2K, 2048)
+    dr["p1k"] = ops.draw_selection(2048, keys_t, seed, lib.SITE_SEL1K, 1024)
+    if clouds_only:
+        pc2k = ops.cloud_select(rr, dr["sel2k"])
+        pc1k = ops.gather_rows(torch.nn.functional.pad(pc2k, (0, 1)), dr["p1k"], torch.empty(D, 1024, 4, device=dev))
+        pc2k, pc1k = ops.gather_slots(slot, [pc2k, pc1k])
+        return dict(PC=pc2k, pcl_in=pc1k[..., :3].contiguous(), n_alive=n_alive.reshape(()), status=status, item_index=slot.long())
+    jit = next((o for o in ops_ if isinstance(o, da.PcJitter)), None)
+    dr.update(ops.draw_fill(keys_t, seed, 2048, defor=True, noise=(jit.std, jit.clip) if jit is not None else (0.0, 0.0), drop_u=True))
+    lab = _stack_labels(items, up)
+    rows = _augment_rows(rr, dr, lab, ops_,
+                         shuffle=lambda counts: ops.draw_selection(counts[:, 0], keys_t, seed, lib.SITE_SHUFFLE, 1024, shuffle_always=True))
+    names = [k for k in rows if k != "shuf"] + [k for k in lab if k not in _POSE_KEYS]
+    src = [rows[k] for k in rows if k != "shuf"] + [lab[k] for k in lab if k not in _POSE_KEYS] + [up(sc["op_index"])]
+    got = ops.gather_slots(slot, src)
+    db = dict(zip(names + ["aug_op"], got))
+    db["pcl_in"], db["aug_pcl_in"] = db["pcl_in"][..., :3].contiguous(), db["aug_pcl_in"][..., :3].contiguous()
+    db.update(n_alive=n_alive.reshape(()), status=status, item_index=slot.long())
+    if persistence:            # no read here either: a failed cloud's images are zeros and 'pd_status' names the reason
+        db["pdh1"], db["pdh2"], db["pd_status"] = ops.persistence_images(db["pcl_in"], check_status=False)
+    if keep_draws:
+        dr["shuf"] = rows["shuf"]
+        db["_draws"] = dr
     return db
 
 
@@ -451,11 +696,16 @@ class TrainBatches(object):
       rank / world_size (default: torch.distributed's) give each rank its own slice of it.  seed=None draws the seed once, at
       construction, from ``gen`` (before any augmentation draw; ranks with alike-seeded generators agree); pass one seed to all
       ranks otherwise.  The epoch counts up at every iteration; set_epoch(e) sets it (a resumed run).
+    * draws='device' (train_batch's mode of that name, seeded with ``seed``): a batch is built without a host read.  An item's key
+      is epoch * len(items) + its index, so its rows depend on neither its batch, its slot, the batch size, prefetch nor the rank
+      that builds it, and set_epoch reproduces them.  There is no refill: a batch is handed its own items plus ``spares`` more --
+      the indices that follow it in this rank's epoch order, wrapping (they still appear in their own batch) -- and holds the first
+      batch_size alive ones ('n_alive', 'status', 'item_index' as train_batch documents; -1 marks a slot without an item).
     rng (NumPy) and gen (torch CPU generator; None: torch's default) feed train_batch."""
 
     def __init__(self, items, batch_size, rng=np.random, gen=None, device="cuda", prefetch=True, shuffle=True, drop_last=False,
                  persistence=False, dzi=False, roi_mask_pro=None, roi_mask_r=3, category_tables=None, min_points=50, operators=None,
-                 img_size=256, rank=None, world_size=None, seed=None):
+                 img_size=256, rank=None, world_size=None, seed=None, draws="host", spares=0):
         import torch.distributed as dist
         if not items:
             raise ValueError("TrainBatches: no items")
@@ -480,6 +730,9 @@ class TrainBatches(object):
         if seed is None:
             seed = int(torch.empty((), dtype=torch.int64).random_(generator=gen).item())
         self.seed, self.epoch = int(seed), 0
+        if draws not in ("host", "device") or int(spares) < 0:
+            raise ValueError("TrainBatches: draws must be 'host' or 'device' and spares >= 0")
+        self.draws, self.spares = draws, int(spares)
 
     def __len__(self):
         n = -(-len(self.items) // self.world_size)
@@ -507,6 +760,21 @@ class TrainBatches(object):
                 db[k] = t.index_select(0, cid)
         return db
 
+    def build_device(self, indices, spare_indices, epoch):
+        """one draws='device' batch: the items at ``indices`` and their spares, on the current stream, nothing read back"""
+        idx = list(indices) + list(spare_indices)
+        n = len(self.items)
+        db = train_batch([self.items[i] for i in idx], draws="device", seed=self.seed, keys=[int(epoch) * n + i for i in idx],
+                         batch_size=len(indices), **self.kw)
+        pos = db["item_index"]
+        idx_t = _uploader(self.device)(np.asarray(idx, dtype=np.int64))
+        db["item_index"] = torch.where(pos >= 0, idx_t[pos.clamp(min=0)], pos)
+        if self.tables is not None:
+            cid = db["cat_id"].reshape(-1).long()
+            for k, t in zip(CATEGORY_KEYS, self.tables):
+                db[k] = t.index_select(0, cid)
+        return db
+
     def side_stream(self):
         if self._side is None:
             self._side = torch.cuda.Stream(device=self.device)
@@ -523,12 +791,21 @@ class TrainBatches(object):
     def __iter__(self):
         batches = self.order(self.epoch)
         self.epoch += 1
-        return _EpochBatches(self, batches)
+        return _EpochBatches(self, batches, self.epoch - 1)
 
 
 class _EpochBatches(object):
-    def __init__(self, src, batches):
-        self.src, self.batches, self.at, self.ready = src, batches, 0, None
+    def __init__(self, src, batches, epoch=0):
+        self.src, self.batches, self.at, self.ready, self.epoch = src, batches, 0, None, epoch
+        self.flat = [i for b in batches for i in b]
+        self.start = np.cumsum([0] + [len(b) for b in batches])
+
+    def _build(self, j):
+        if self.src.draws != "device":
+            return self.src.build(self.batches[j])
+        end = int(self.start[j + 1])
+        spare = [self.flat[(end + q) % len(self.flat)] for q in range(self.src.spares)]
+        return self.src.build_device(self.batches[j], spare, self.epoch)
 
     def __iter__(self):
         return self
@@ -539,7 +816,7 @@ class _EpochBatches(object):
             return
         side = self.src.side_stream()
         with torch.cuda.stream(side):
-            db = self.src.build(self.batches[self.at])
+            db = self._build(self.at)
             done = torch.cuda.Event()
             done.record(side)
         self.at += 1
@@ -557,6 +834,6 @@ class _EpochBatches(object):
             return db
         if self.at >= len(self.batches):
             raise StopIteration
-        db = self.src.build(self.batches[self.at])
+        db = self._build(self.at)
         self.at += 1
         return db

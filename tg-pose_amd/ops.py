@@ -1987,3 +1987,106 @@ def bn_eval_bwd_pooled(dpool, argrow, x, rows_per_obj, mean, var, gamma, beta, e
                                             _p(mean), _p(var), float(eps), _p(gamma), _p(beta), act, float(slope), _p(dx), C, _p(dg), _p(db),
                                             _p(ws), _stream(x)), "tgp_bn_eval_bwd_pooled")
     return dx, dg, db
+
+
+# ------------------------------------------------------------------------------------- the training batch's draws on the device
+def _keys(keys, name="keys"):
+    """item keys: a contiguous (D,) int64 GPU tensor holding the 64-bit keys' bit patterns"""
+    if not (torch.is_tensor(keys) and keys.is_cuda and keys.dtype == torch.int64 and keys.dim() == 1 and keys.is_contiguous()):
+        raise TypeError("%s must be a contiguous (D,) int64 GPU tensor" % name)
+    return keys
+
+
+def _u64(seed):
+    return int(seed) & (2 ** 64 - 1)
+
+
+def draw_words(keys, seed, site, n_counters):
+    """tgp_draw_words: the generator's words, (D, n_counters, 4) int32-viewed uint32"""
+    D = _keys(keys).numel()
+    out = torch.empty(D, int(n_counters), 4, device=keys.device, dtype=torch.int32)
+    check(_lib.lib().tgp_draw_words(_p(keys), D, _u64(seed), int(site), int(n_counters), _p(out), _stream(keys)), "tgp_draw_words")
+    return out
+
+
+def draw_band_subset(band_counts, u, pro, keys, seed, validity=True, drop_words=2048):
+    """tgp_draw_band_subset: defor_2D's draws from roi_band's (D,3) counts without reading them back; u (D,) float64 GPU
+    -> (defor_on (D,) int32, drop_bits (D, drop_words) int32)"""
+    _i32(band_counts, "band_counts")
+    D = _keys(keys).numel()
+    if band_counts.shape != (D, 3) or not (u.is_cuda and u.dtype == torch.float64 and u.shape == (D,) and u.is_contiguous()):
+        raise ValueError("draw_band_subset: band_counts must be (D,3) int32 and u (D,) float64")
+    on = torch.empty(D, device=keys.device, dtype=torch.int32)
+    bits = torch.empty(D, int(drop_words), device=keys.device, dtype=torch.int32)
+    check(_lib.lib().tgp_draw_band_subset(_p(band_counts), _p(u), float(pro), _p(keys), _u64(seed), D, 1 if validity else 0, _p(on), _p(bits),
+                                          int(drop_words), _stream(keys)), "tgp_draw_band_subset")
+    return on, bits
+
+
+def draw_alive(counts, B, min_points, forced=None):
+    """tgp_draw_alive: counts (D,3) int32 -> (status (D,), slot_item (B,), n_alive (1,)) int32, nothing read back"""
+    _i32(counts, "counts")
+    D = counts.shape[0]
+    if counts.dim() != 2 or counts.shape[1] != 3 or (forced is not None and _i32(forced, "forced").shape != (D,)):
+        raise ValueError("draw_alive: counts must be (D,3) and forced (D,)")
+    dev = counts.device
+    status, slot, n = (torch.empty(k, device=dev, dtype=torch.int32) for k in (D, int(B), 1))
+    check(_lib.lib().tgp_draw_alive(_p(counts), _p(forced), D, int(B), int(min_points), _p(status), _p(slot), _p(n), _stream(counts)),
+          "tgp_draw_alive")
+    return status, slot, n
+
+
+def draw_selection(totals, keys, seed, site, n_out, shuffle_always=False):
+    """tgp_draw_selection -> (D, n_out) int32.  totals: an int (every item's total) or an int32 GPU tensor view whose element
+    [d] (any constant stride along its one dimension, e.g. counts[:, 2]) is item d's total, read on the device"""
+    D = _keys(keys).numel()
+    sel = torch.empty(D, int(n_out), device=keys.device, dtype=torch.int32)
+    if torch.is_tensor(totals):
+        if not (totals.is_cuda and totals.dtype == torch.int32 and totals.dim() == 1 and totals.numel() == D):
+            raise ValueError("draw_selection: totals must be a (D,) int32 GPU view")
+        ptr, ld, const = _p(totals), max(int(totals.stride(0)), 1), 0
+    else:
+        ptr, ld, const = None, 0, int(totals)
+    check(_lib.lib().tgp_draw_selection(ptr, ld, const, _p(keys), _u64(seed), int(site), D, int(n_out), 1 if shuffle_always else 0, _p(sel),
+                                        _stream(keys)), "tgp_draw_selection")
+    return sel
+
+
+def draw_fill(keys, seed, N, defor=False, noise=None, drop_u=False):
+    """tgp_draw_fill: the per-point draws.  defor: (D,N,3) float32 uniforms; noise = (std, clip): (D,N,3) float32 clamped normals;
+    drop_u: (D,N) float64 uniforms -> dict of the buffers asked for"""
+    D = _keys(keys).numel()
+    dev = keys.device
+    out = {}
+    if defor:
+        out["defor"] = torch.empty(D, N, 3, device=dev)
+    if noise is not None:
+        out["noise"] = torch.empty(D, N, 3, device=dev)
+    if drop_u:
+        out["drop_u"] = torch.empty(D, N, device=dev, dtype=torch.float64)
+    std, clip = (float(v) for v in noise) if noise is not None else (0.0, 0.0)
+    check(_lib.lib().tgp_draw_fill(_p(keys), _u64(seed), D, int(N), _p(out.get("defor")), _p(out.get("noise")), std, clip, _p(out.get("drop_u")),
+                                   _stream(keys)), "tgp_draw_fill")
+    return out
+
+
+def gather_slots(slot_item, tensors):
+    """tgp_gather_slots: for each contiguous GPU tensor (D, ...) of a 4- or 8-byte type, the (B, ...) tensor of its rows slot_item[s]
+    (zeros where slot_item is -1); one launch per _lib.GATHER_SLOTS_MAX tensors"""
+    _i32(slot_item, "slot_item")
+    B = slot_item.numel()
+    tensors = list(tensors)
+    D = tensors[0].shape[0]
+    outs = []
+    for t in tensors:
+        if not (t.is_cuda and t.is_contiguous() and t.shape[0] == D and t.element_size() in (4, 8) and t.numel() > 0):
+            raise ValueError("gather_slots: contiguous (D, ...) GPU tensors of 4- or 8-byte elements")
+        outs.append(torch.empty((B,) + tuple(t.shape[1:]), device=t.device, dtype=t.dtype))
+    for i0 in range(0, len(tensors), _lib.GATHER_SLOTS_MAX):
+        a = _lib.GatherSlotsArgs()
+        part = list(zip(tensors, outs))[i0:i0 + _lib.GATHER_SLOTS_MAX]
+        a.slot_item, a.B, a.D, a.n = _p(slot_item).value, B, D, len(part)
+        for k, (t, o) in enumerate(part):
+            a.src[k], a.dst[k], a.row_words[k] = t.data_ptr(), o.data_ptr(), t[0].numel() * t.element_size() // 4
+        check(_lib.lib().tgp_gather_slots(ctypes.byref(a), _stream(slot_item)), "tgp_gather_slots")
+    return outs

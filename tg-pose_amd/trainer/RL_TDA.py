@@ -249,17 +249,25 @@ class RT_TDA_Trainer(object):
         return output_dict, loss_dict
 
     # -------------------------------------------------------------------------------------------------------------------
-    def loss_is_nan(self, total):
+    def loss_is_nan(self, total, n_alive=None):
         """the loop's NaN test (:217-220) -- one host read of the device scalar.  Data parallel: the ranks must skip or step
-        TOGETHER (a rank that skipped would miss the collective the others wait in), so the flag is max-reduced first."""
+        TOGETHER (a rank that skipped would miss the collective the others wait in), so the flag is max-reduced first.
+        n_alive (a draws='device' batch's count of slots that hold an item of their own, a device int32): read in the same host
+        copy; a batch without an alive item counts as a NaN step, and ``last_n_alive`` keeps the count for the loop."""
         import torch.distributed as dist
         bad = torch.isnan(total.detach()).reshape(-1).any().to(torch.int32)
+        if n_alive is not None:
+            bad = torch.maximum(bad, (n_alive.reshape(-1)[0] == 0).to(torch.int32))
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             bad = bad.to(self.device) if dist.get_backend() == "nccl" else bad.cpu()
             dist.all_reduce(bad, op=dist.ReduceOp.MAX)
-        return bool(bad.item())
+        if n_alive is None:
+            self.last_n_alive = None
+            return bool(bad.item())
+        flag, self.last_n_alive = torch.stack([bad.to(n_alive.device).reshape(()), n_alive.reshape(-1)[0].to(torch.int32)]).tolist()
+        return bool(flag)
 
-    def finish_step(self, total=None):
+    def finish_step(self, total=None, n_alive=None):
         """what follows total_loss.backward() in the loop (:223-226), with the data-parallel gradient exchange in front: the
         clip must see the averaged gradients.  After a graphed_step(overlap=True) replay the exchange has already
         run (bucket by bucket, overlapped with the backward): the replay says so through ``_exchanged``.
@@ -269,8 +277,8 @@ class RT_TDA_Trainer(object):
         zeroing the gradients instead of skipping backward(): no clip, no optimizer / scheduler step, weights untouched.
         Returns False for such a skipped step."""
         from .. import shard
-        if total is not None and self.loss_is_nan(total):
-            print('Found nan in total loss')
+        if total is not None and self.loss_is_nan(total, n_alive):
+            print('Found nan in total loss' if self.last_n_alive != 0 else 'No alive item in the batch')
             self._exchanged = False
             grads = [p.grad for p in self.net1.parameters() if p.grad is not None]
             if grads:
@@ -294,9 +302,9 @@ class RT_TDA_Trainer(object):
             self.optimizer.zero_grad(set_to_none=self._graphed is None and self._buckets is None)
         _, loss_dict = self.RL_TDA_train_step(db)
         total = total_loss(loss_dict)
-        self._skipped = self.loss_is_nan(total)
+        self._skipped = self.loss_is_nan(total, db.get('n_alive'))
         if self._skipped:
-            print('Found nan in total loss')
+            print('Found nan in total loss' if self.last_n_alive != 0 else 'No alive item in the batch')
             return total.detach(), loss_dict
         total.backward()
         self._exchanged = False
@@ -397,20 +405,24 @@ class RT_TDA_Trainer(object):
             epoch_s_time = time.time()
             batches = iter(train_dataloader)
             prefetch = getattr(batches, 'prefetch', None)
+            partial = None                       # draws='device' batches: how many trained with fewer alive items than slots
             for i, data in enumerate(batches, 1):
                 iter_s_time = time.time()
                 step = self._loop_step(data, overlap) if graph else None
+                n_alive = data.get('n_alive') if isinstance(data, dict) else None
                 if step is not None:
                     total = step(data)
                     if prefetch is not None:
                         prefetch()
-                    stepped = self.finish_step(total=total)
+                    stepped = self.finish_step(total=total, n_alive=n_alive) if n_alive is not None else self.finish_step(total=total)
                     loss_dict = step.loss_dict
                 else:
                     total, loss_dict = self.train_iteration(data)
                     if prefetch is not None:
                         prefetch()
                     stepped = not self._skipped
+                if n_alive is not None:
+                    partial = (partial or 0) + (0 < self.last_n_alive < data['pcl_in'].shape[0])
                 if stepped and i % FLAGS.log_every == 0 and rank0 and self.logger is not None:
                     self.logger.info(log_line(e, i, log_values(total, loss_dict)))
                     self.logger.info('The average running time of every {} is {:.4f} sec'.format(FLAGS.log_every, time.time() - iter_s_time))
@@ -418,6 +430,8 @@ class RT_TDA_Trainer(object):
             if rank0 and self.logger is not None:
                 self.logger.info('>>>>>>>>----------Epoch {:02d} train finish,time is {:02f} sec---------<<<<<<<<'.format(
                     e, time.time() - epoch_s_time))
+                if partial is not None:
+                    self.logger.info('Epoch {:02d}: {} batches trained with fewer alive items than slots'.format(e, partial))
             if rank0 and saves_checkpoint(e, total_epoch):
                 self.save_checkpoint(e)
 
