@@ -393,6 +393,25 @@ int tgp_dcd_fwd(const float *dist1, const float *dist2, const int32_t *idx1, con
 int tgp_dcd_bwd(const float *dist1, const float *dist2, const float *w1, const float *w2, const float *gloss,
                 int B, int n, int m, float alpha, float *graddist1, float *graddist2, tgp_stream_t stream);
 
+/* ---- earth mover's distance by auction matching (csrc/emd.hip; additive, ABI stays 8) ----------- */
+
+/* emd.forward (losses/metrics/EMD/emd_module.py:41-80; kernels emd_cuda.cu:95-226), all `iters` auction iterations and the
+ * distance pass in ONE launch, one workgroup per cloud pair with the pair's state in LDS.  xyz1, xyz2 (B,n,3) with coordinates
+ * in [0,1] -> assignment (B,n) int32 (the point of xyz2 matched to each point of xyz1; a bijection once the auction has
+ * converged, not necessarily before) and dist (B,n) the squared distances to it.  Any 1 <= n <= tgp_emd_max_points() (the
+ * reference wants n % 1024 == 0) and any B >= 1; TGP_EINVAL for iters < 1, TGP_EUNSUPPORTED above the cap.  The arithmetic is
+ * DESIGN.md "EMD": the reference's, with its one race (the winner among equal bidders) fixed to the lowest bidder.  Bit-repeatable
+ * and independent of the batch around a pair; no float atomics.  ws: tgp_emd_workspace_bytes(B, n) bytes (0 up to the cap: may
+ * be NULL). */
+int tgp_emd_max_points(void);
+int64_t tgp_emd_workspace_bytes(int B, int n);
+int tgp_emd_fwd(const float *xyz1, const float *xyz2, int B, int n, float eps, int iters, float *dist, int32_t *assignment,
+                void *ws, tgp_stream_t stream);
+/* emd.backward (emd_cuda.cu:284-316): grad_xyz1 (B,n,3) = (grad_dist * 2) * (xyz1 - xyz2[assignment]), WRITTEN (not
+ * accumulated); the gradient for xyz2 is zero, as the reference returns. */
+int tgp_emd_bwd(const float *xyz1, const float *xyz2, const float *grad_dist, const int32_t *assignment, int B, int n,
+                float *grad_xyz1, tgp_stream_t stream);
+
 /* TDA_loss.R_DCD pose normalisation (:326-339): R from the predicted axes p_g, p_r (B,3) and confidences f_g, f_r
  * (B) -- for objects with sym[b*sym_ld] == 1 the green axis is paired with column 0 of the true rotation gR (B,3,3)
  * -- then out[b,i] = (R^T (points[b,i] - p_t[b])) * p_s[b].  R_out (B,3,3) optional. */

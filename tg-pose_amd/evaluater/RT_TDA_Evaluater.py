@@ -20,6 +20,7 @@ import torch
 
 from ..evaluation import load_data_eval as lde
 from ..evaluation.metrics import compute_degree_cm_mAP
+from ..losses.utils_v2.model_utils import calc_cd, calc_emd
 from ..pose import infer_device
 
 SYNSET_NAMES = ['BG', 'bottle', 'bowl', 'camera', 'can', 'laptop', 'mug']                                   # :115
@@ -30,9 +31,18 @@ SYM_INFO = {1: (1, 1, 0, 1), 2: (1, 1, 0, 1), 3: (0, 0, 0, 0), 4: (1, 1, 1, 1), 
 class myEvaluater:
     """``sampler='numpy'``: the reference's draws (one small read-back per chunk for the point counts).  ``sampler='device'``:
     nothing is read back until a chunk's poses are; with ``overlap`` (default) chunk c's results are fetched after chunk c+1
-    has been enqueued, so packing / uploading the next frames runs beside the GPU's work on the current ones."""
+    has been enqueued, so packing / uploading the next frames runs beside the GPU's work on the current ones.
 
-    def __init__(self, net, frames_per_batch=32, max_batch=256, sampler="numpy", seed=0, overlap=True, graph=False):
+    ``recon_stats=True`` (what ``compute_degree_cm_mAP(eval_recon=True)`` reads, eval_utils_v1.py:1517-1518): the forwards run
+    full -- the decoder is needed -- and each detection dict gains ``chamfer_dis_cass`` (``calc_cd``'s cd_p of the reconstruction
+    against the input cloud, the ``Recon`` target of the training loss, trainer/RL_TDA.py:166) and ``emd_dis_cass`` (``calc_emd``
+    with its defaults), one value per detection.  Not available together with ``graph``."""
+
+    def __init__(self, net, frames_per_batch=32, max_batch=256, sampler="numpy", seed=0, overlap=True, graph=False,
+                 recon_stats=False):
+        if recon_stats and graph:
+            raise ValueError("recon_stats is not available on the captured path: pass graph=False")
+        self.recon_stats = bool(recon_stats)
         self.net1 = net.eval()
         # The driver reads the six pose outputs only (:143-150): PH predictor and decoder are dead code here, as in the reference's
         # eval dict, so its forwards run lean BY DEFAULT (TGP_EVAL_FULL_FORWARD=1 or eval_outputs_only=False: the full forward).
@@ -57,7 +67,7 @@ class myEvaluater:
             # the frame afterwards, as the reference drops it (load_data_eval.py:332-337)
         kept = [i for i, a in enumerate(alive) if a and per[i] > 0]
         if not kept:
-            return records, alive, ok, kept, None, None, None
+            return records, alive, ok, kept, None, None, None, None
         ids = [np.asarray(frames[i]["pred_class_ids"]).astype(np.int64) for i in kept]
         t = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float32)).to(self.device, non_blocking=True)
         flat = np.concatenate(ids)
@@ -67,14 +77,23 @@ class myEvaluater:
         pts = torch.cat([clouds[i] for i in kept])
         if ok is not None:
             pts = torch.nan_to_num(pts, nan=0.0)
+        stats = None
         with torch.no_grad():
-            rts, scales = infer_device(self.net1, pts, cat, mean, sym, self.max_batch, eval_outputs_only=self.eval_outputs_only)
+            if self.recon_stats:
+                recon = []
+                rts, scales = infer_device(self.net1, pts, cat, mean, sym, self.max_batch, eval_outputs_only=False, recon_out=recon)
+                # scored in the forwards' own batches: a pair's EMD does not depend on the batch around it, nor does its Chamfer
+                cmf = [calc_cd(r, pts[lo:lo + r.shape[0]])[0] for r, lo in zip(recon, range(0, pts.shape[0], self.max_batch))]
+                emd = [calc_emd(r, pts[lo:lo + r.shape[0]]) for r, lo in zip(recon, range(0, pts.shape[0], self.max_batch))]
+                stats = torch.stack([torch.cat(cmf), torch.cat(emd)])
+            else:
+                rts, scales = infer_device(self.net1, pts, cat, mean, sym, self.max_batch, eval_outputs_only=self.eval_outputs_only)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(self.device))
-        return records, alive, ok, kept, rts, scales, done
+        return records, alive, ok, kept, rts, scales, done, stats
 
     def _finish(self, launched):
-        records, alive, ok, kept, rts, scales, done = launched
+        records, alive, ok, kept, rts, scales, done, stats = launched
         # The copies back are stream-ordered: on the compute stream they would queue behind the NEXT chunk's forward, which
         # has already been enqueued, and the overlap would be lost.  They run on a fetch stream that waits only for this
         # chunk's event.
@@ -89,15 +108,22 @@ class myEvaluater:
             if rts is not None:
                 rts.record_stream(self._fetch), scales.record_stream(self._fetch)
                 rts, scales = rts.cpu().numpy(), scales.cpu().numpy()
+            if stats is not None:
+                stats.record_stream(self._fetch)
+                stats = stats.cpu().numpy()
         out = []
         pos = 0
         empty = dict(pred_RTs=np.zeros((0, 4, 4)), pred_scales=np.zeros((0, 4, 4)))                       # RT_TDA_Evaluater.py:70-71
+        if self.recon_stats:
+            empty.update(chamfer_dis_cass=np.zeros(0, np.float32), emd_dis_cass=np.zeros(0, np.float32))
         for i, rec in enumerate(records):
             fr = rec["frame"]
             n = fr["pred_masks"].shape[2]
             pose = empty
             if i in kept:
                 pose = dict(pred_RTs=rts[pos:pos + n], pred_scales=scales[pos:pos + n])
+                if stats is not None:
+                    pose.update(chamfer_dis_cass=stats[0, pos:pos + n], emd_dis_cass=stats[1, pos:pos + n])
                 pos += n
             if not alive[i]:
                 continue

@@ -13,6 +13,10 @@ repeated for each of the 101 IoU and 62 x 22 pose thresholds.  Here
 Same inputs (the ``final_results`` list the evaluater pickles, evaluation/evaluate.py:53-67), same outputs
 (``iou_3d_aps`` (classes+1, iou thresholds), ``pose_aps`` (classes+1, degree thresholds+1, shift thresholds+1)) and the same
 ``mAP_data.npz`` in ``log_dir``.  The figure the reference also draws is not produced.
+
+``eval_recon=True`` adds the reconstruction statistics of :1508-1543: the per-detection ``chamfer_dis_cass`` / ``emd_dis_cass``
+the evaluater stored (``myEvaluater(recon_stats=True)``) averaged per class, and the mean of the class means.  The reference
+computes them into a local dict it drops; here they are handed back through ``recon_out``.
 """
 import os
 
@@ -115,11 +119,10 @@ def _ap(pred_match, pred_scores, gt_match):
 
 def compute_degree_cm_mAP(final_results, synset_names, log_dir=None, degree_thresholds=[360], shift_thresholds=[100],
                           iou_3d_thresholds=[0.1], iou_pose_thres=0.1, use_matches_for_pose=False, eval_recon=False,
-                          plot_figure=False, device="cuda"):
+                          plot_figure=False, device="cuda", recon_out=None):
+    """recon_out (a dict, with eval_recon): receives "emd" and "cmf", each {class name: mean, ..., "mean": mean of those}"""
     if plot_figure:
         raise NotImplementedError("the AP-curve figure of the reference is not drawn; pass plot_figure=False")
-    if eval_recon:
-        raise NotImplementedError("eval_recon (EMD / Chamfer statistics of the results) is not part of this path")
     num_classes = len(synset_names)
     degree_thres_list = list(degree_thresholds) + [360]
     shift_thres_list = list(shift_thresholds) + [100]
@@ -215,4 +218,34 @@ def compute_degree_cm_mAP(final_results, synset_names, log_dir=None, degree_thre
     if log_dir is not None:
         np.savez(os.path.join(log_dir, 'mAP_data.npz'), pose_aps=pose_aps, degree_thres_list=degree_thres_list,
                  shift_thres_list=shift_thres_list, iou_thres_list=iou_thres_list, iou_3d_aps=iou_3d_aps)
+    if eval_recon:
+        stats = recon_statistics(final_results, synset_names)
+        if recon_out is not None:
+            recon_out.update(stats)
     return iou_3d_aps, pose_aps
+
+
+def recon_statistics(final_results, synset_names):
+    """eval_utils_v1.py:1508-1543: -> {"emd": {...}, "cmf": {...}}; a class without detections has no entry, and "mean" is the
+    mean over the classes that have one (NaN when there is none, as np.mean of nothing is)."""
+    num_classes = len(synset_names)
+    emd_all = {c: [] for c in synset_names}
+    cmf_all = {c: [] for c in synset_names}
+    for result in final_results:
+        pred_class_ids = result['pred_class_ids']
+        if len(pred_class_ids) <= 0:
+            continue
+        cmf_img, emd_img = np.asarray(result["chamfer_dis_cass"]), np.asarray(result["emd_dis_cass"])
+        for cls_id in range(1, num_classes):
+            sel = pred_class_ids == cls_id
+            cmf_dis, emd_dis = cmf_img[sel], emd_img[sel]
+            if len(cmf_dis) <= 0 or len(emd_dis) <= 0:
+                continue
+            cmf_all[synset_names[cls_id]] += cmf_dis.tolist()
+            emd_all[synset_names[cls_id]] += emd_dis.tolist()
+    out = {}
+    for key, table in (("emd", emd_all), ("cmf", cmf_all)):
+        stats = {k: np.mean(np.asarray(v)) for k, v in table.items() if k != "BG" and len(v)}
+        stats["mean"] = np.mean(np.array([v for v in stats.values()]))
+        out[key] = stats
+    return out

@@ -56,7 +56,7 @@ class PoseNet9D(_WithBuffers):
         return self._proj
 
     def forward(self, points, obj_id, enable_proj=False, *, sample_idx=None, inject=None, record=None, cut=None,
-                eval_outputs_only=None):
+                eval_outputs_only=None, probe=None):
         if not points.is_cuda:
             raise RuntimeError("tgpose_amd.PoseNet9D runs on the GPU only (no CPU fallback); move inputs to cuda")
         grad_pts = torch.is_grad_enabled() and points.requires_grad
@@ -91,6 +91,11 @@ class PoseNet9D(_WithBuffers):
             # default; handed down as an argument -- nothing global is rewritten, so nets with different settings do not interfere.
             lean = eval_outputs_only if eval_outputs_only is not None else getattr(self, "eval_outputs_only", None)
             lean = engine.EVAL_OUTPUTS_ONLY if lean is None else bool(lean)
+            if probe is not None:
+                # probe (a dict): the full forward, which also hands over what the six-key eval dict drops -- the reconstruction
+                # (the evaluater's recon_stats scores it), h1, h2.  Never replayed from a graph.
+                return engine.posenet_forward(pk, points, obj_id, bool(FLAGS.train), sample_idx, inject, record,
+                                              FLAGS.gcn_n_num, FLAGS.obj_c, probe=probe, outputs_only=False, proj=proj)
             if getattr(self, "graph_replay", False) and inject is None and record is None and proj is None:
                 # opt-in (net.graph_replay = True): the forward of this (batch, cloud size, output set) is captured once as
                 # a hipGraph and replayed; the returned tensors are the graph's static outputs, valid until the next call

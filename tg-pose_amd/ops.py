@@ -1044,6 +1044,37 @@ def dcd_bwd(dist1, dist2, w1, w2, gloss, alpha):
     return gd1, gd2
 
 
+def emd_max_points():
+    return int(_lib.lib().tgp_emd_max_points())
+
+
+def emd_fwd(xyz1, xyz2, eps, iters):
+    """Auction matching of xyz1 (B,n,3) onto xyz2 (B,n,3), every iteration in one launch (csrc/emd.hip)
+    -> (dist (B,n) float32 squared distances, assignment (B,n) int32)"""
+    _f32(xyz1, "xyz1", 3), _f32(xyz2, "xyz2", 3)
+    if not (xyz1.is_contiguous() and xyz2.is_contiguous()):
+        raise ValueError("emd inputs must be contiguous")
+    if xyz1.shape != xyz2.shape or xyz1.shape[2] != 3:
+        raise ValueError("emd: the two clouds must both be (B, n, 3) (emd_module.py:45)")
+    B, n, _ = xyz1.shape
+    dist = torch.empty(B, n, device=xyz1.device, dtype=torch.float32)
+    assignment = torch.empty(B, n, device=xyz1.device, dtype=torch.int32)
+    nbytes = int(_lib.lib().tgp_emd_workspace_bytes(B, n))
+    ws = torch.empty(nbytes, device=xyz1.device, dtype=torch.uint8) if nbytes > 0 else None
+    check(_lib.lib().tgp_emd_fwd(_p(xyz1), _p(xyz2), B, n, float(eps), int(iters), _p(dist), _p(assignment), _p(ws),
+                                 _stream(xyz1)), "tgp_emd_fwd")
+    return dist, assignment
+
+
+def emd_bwd(xyz1, xyz2, grad_dist, assignment):
+    """-> grad_xyz1 (B,n,3) = (grad_dist * 2) * (xyz1 - xyz2[assignment]); the gradient for xyz2 is zero"""
+    B, n, _ = xyz1.shape
+    grad = torch.empty_like(xyz1)
+    check(_lib.lib().tgp_emd_bwd(_p(xyz1), _p(xyz2), _p(_f32(grad_dist.contiguous(), "grad_dist", 2)),
+                                 _p(_i32(assignment, "assignment")), B, n, _p(grad), _stream(xyz1)), "tgp_emd_bwd")
+    return grad
+
+
 def canonicalize(points, gR, p_g, f_g, p_r, f_r, p_t, p_s, sym):
     """R_DCD pose normalisation -> (points_re_n (B,n,3), R (B,3,3))"""
     c = lambda t: _f32(t.contiguous(), "arg")
