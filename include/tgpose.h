@@ -484,7 +484,9 @@ int tgp_transpose(const float *src, int ld_src, int rows, int cols, float *dst, 
  * ------------------------------------------------------------------------------------------------------------------ */
 
 /* HSlayer_surface.graph_conv (gcn3d.py:91-106): dg (B,n,C) -> dsdn (3, S*C), the gradient w.r.t. the unit support
- * directions (F.normalize's own backward stays with the caller).  workspace: tgp_gconv_bwd_workspace_floats(B, n, C). */
+ * directions (F.normalize's own backward stays with the caller).  workspace: tgp_gconv_bwd_workspace_floats(B, n, C).
+ * C >= 128 with 256 % C == 0 or C % 256 == 0, k <= 64 (the kernel stages two 16-point streams per workgroup): a narrower C is
+ * TGP_EUNSUPPORTED, here and in tgp_gconv_hs_bwd, and nothing is launched. */
 int64_t tgp_gconv_bwd_workspace_floats(int B, int n, int C);
 int tgp_gconv_surface_bwd(const float *xyz, const int32_t *idx, const float *sdn, const float *dg, int ldg, int B, int n, int k,
                           int S, int C, float *dsdn, float *workspace, tgp_stream_t stream);

@@ -1521,7 +1521,8 @@ def test_nbrmax_bwd_gather_vs_scatter(ops, B, n_src, n_rows, k, C, per_object):
 @pytest.mark.parametrize("B,n,k,C", [(2, 300, 20, 128), (2, 257, 20, 256), (3, 64, 8, 512), (1, 40, 5, 128)])
 def test_gconv_hs_bwd_gather_vs_scatter(ops, B, n, k, C):
     """the scatter-free backward of HS_layer.graph_conv (gcn3d.py:157-180) against the first version's atomic scatter on the same
-    inputs: d proj (centre and support halves) and d directions to summation-order accuracy; two runs agree bit for bit."""
+    inputs: d proj (centre and support halves) and d directions to summation-order accuracy; two runs agree bit for bit.
+    (The independent reference of both kernels is the fp64 backward of tests/test_graph_bwd_gpu.py.)"""
     gen = torch.Generator().manual_seed(n + C)
     xyz = torch.randn(B, n, 3, generator=gen)
     idx = torch.randint(0, n, (B, n, k), generator=gen, dtype=torch.int32)

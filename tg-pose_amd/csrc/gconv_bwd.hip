@@ -160,6 +160,9 @@ static int gconv_bwd_launch(bool surface, const float *xyz, const int32_t *idx, 
     if (!(xyz && idx && sdn && dg && dsdn && workspace) || B <= 0 || n <= 0 || k <= 0 || k > GB_MAXK || S != GB_S || C <= 0 ||
         ldg < C || (C > 256 && C % 256 != 0) || (C < 256 && 256 % C != 0))
         return TGP_EINVAL;
+    // the kernel stages GB_PTS * streams points' neighbour rows in arrays of 2 * GB_PTS: two streams at the most, so C >= 128
+    // (the network's widths are 128 / 256 / 512; a narrower layer would need staging sized to 256 / C streams)
+    if (C < 128) return TGP_EUNSUPPORTED;
     const int cw = C < 256 ? C : 256;
     const int streams = 256 / cw;
     const dim3 grid(tgp_xcd_grid(B, tgp_cdiv(n, GB_PTS * streams) * tgp_cdiv(C, cw)));

@@ -238,7 +238,12 @@ __global__ __launch_bounds__(256) void gconv_bwd_slot_kernel(const float *__rest
 #pragma unroll
         for (int s = 0; s < GG_S; ++s) m[s] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY), ax[s] = ay[s] = az[s] = aw[s] = 255;
         // theta as in the forward kernel (fmaf chain, relu), value theta * support, strict '>' in slot order: the first maximum wins
-        for (int j = half; j < k; j += RL::SPLIT) {
+        // (the trip count is the same for both lane groups: with `for (j = half; j < k; j += SPLIT)` an odd k left the upper group out of
+        // the last round, and a shuffle from a lane that is not running returns nothing useful -- at k - 1 >= 32 that lane holds slot
+        // k - 1's own direction and id, so the slot was taken as a zero direction to row 0.  The upper group now repeats slot k - 1 there:
+        // same value, same slot number, and the merge below keeps either.)
+        for (int j0 = 0; j0 < k; j0 += RL::SPLIT) {
+            const int j = min(j0 + half, k - 1);
             const float ux = __shfl(dx, j, 64), uy = __shfl(dy, j, 64), uz = __shfl(dz, j, 64);
             const float *prow = proj + ((int64_t)b * n + __shfl(nj, j, 64)) * ldp + C + cb;
             float4 sup[GG_S];

@@ -1366,8 +1366,15 @@ def transpose_both(w):
     return wt, planes
 
 
+def _gconv_bwd_width(C, name):
+    # tgp_gconv_surface_bwd / tgp_gconv_hs_bwd stage two 16-point streams per workgroup: 256 / C <= 2
+    if C < 128:
+        raise ValueError("%s: C = %d is not supported, the scatter backward needs C >= 128 (and 256 %% C == 0 or C %% 256 == 0)" % (name, C))
+
+
 def gconv_surface_bwd(xyz, idx, sdn, dg, S, C):
     """-> dsdn (3, S*C)"""
+    _gconv_bwd_width(C, "gconv_surface_bwd")
     dg, ldg = _rows(dg, "dg")
     B, n, k = idx.shape
     dsdn = torch.empty(3, S * C, device=xyz.device, dtype=torch.float32)
@@ -1379,6 +1386,7 @@ def gconv_surface_bwd(xyz, idx, sdn, dg, S, C):
 
 def gconv_hs_bwd(xyz, idx, proj, sdn, dg, S, C):
     """-> (dproj (B,n,8C) = [d centre | d support], dsdn (3, S*C))"""
+    _gconv_bwd_width(C, "gconv_hs_bwd")
     proj, ldp = _rows(proj, "proj")
     dg, ldg = _rows(dg, "dg")
     B, n, k = idx.shape
