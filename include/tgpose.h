@@ -412,6 +412,25 @@ int tgp_emd_fwd(const float *xyz1, const float *xyz2, int B, int n, float eps, i
 int tgp_emd_bwd(const float *xyz1, const float *xyz2, const float *grad_dist, const int32_t *assignment, int B, int n,
                 float *grad_xyz1, tgp_stream_t stream);
 
+/* ---- farthest point sampling (csrc/fps.hip; additive, ABI stays 8) ------------------------------ */
+
+/* farthest_points (core/utils/farthest_points_torch.py:6-62, dist_func = F.pairwise_distance), all n steps of every cloud in ONE
+ * launch, one workgroup per cloud with the cloud and its running distances in registers.  xyz (B,M,ld) rows of ld = 3 or 4
+ * floats (4: the padded rows tgp_augment writes; the fourth is not read); counts (B) int32, may be NULL (= M): cloud b is its
+ * first counts[b] rows, 1 <= counts[b] <= M (values outside are clamped).  init_center != 0: the running distances start as the
+ * distances to start (B,3), or with start NULL to the cloud's centroid, summed as the pairwise tree over the row index and divided
+ * by (float)counts[b] (DESIGN.md section 3 "Farthest point sampling": it does not depend on M or on the batch); init_center == 0:
+ * they start at 1e7f (the first centre is row 0) and start is not read.
+ * -> idx (B,n) int32: for counts[b] > n the n centres in selection order (each the lowest row of the maximum running distance);
+ * for counts[b] <= n no step runs and idx[i] = i % counts[b] (_sample_points' tiling).  dist_out (B,M) / clusters_out (B,M) int32,
+ * each may be NULL: the final running distances and, per row, the last step whose centre came at least as close as every centre
+ * before it (-1: none; the reference's `clusters`); with counts[b] <= n the initial distances and -1.  Rows at and beyond
+ * counts[b] are not written.  The arithmetic is the reference's bit for bit; bit-repeatable, no atomics.
+ * Any 1 <= M <= tgp_fps_max_points(), n >= 1, B >= 1; TGP_EUNSUPPORTED above the cap. */
+int tgp_fps_max_points(void);
+int tgp_fps(const float *xyz, int ld, const int32_t *counts, int B, int M, int n, const float *start, int init_center,
+            int32_t *idx, float *dist_out, int32_t *clusters_out, tgp_stream_t stream);
+
 /* TDA_loss.R_DCD pose normalisation (:326-339): R from the predicted axes p_g, p_r (B,3) and confidences f_g, f_r
  * (B) -- for objects with sym[b*sym_ld] == 1 the green axis is paired with column 0 of the true rotation gR (B,3,3)
  * -- then out[b,i] = (R^T (points[b,i] - p_t[b])) * p_s[b].  R_out (B,3,3) optional. */

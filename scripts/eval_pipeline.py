@@ -3,7 +3,9 @@ dataset, which is not available offline): depth frame + detection masks -> cloud
 pred_results, through tgpose_amd.evaluater.RT_TDA_Evaluater.myEvaluater.  Host -> device copies of the frames are INSIDE the
 timed region (78 MB per 32 frames).  Prints one JSON line per sampler.
 
-    python scripts/eval_pipeline.py [frames=128] [detections per frame=6]
+    python scripts/eval_pipeline.py [frames=128] [detections per frame=6] [--sampler numpy|device|fps]
+
+--sampler: that sampler alone (without the captured graph); default: numpy, device, device with the graph.
 """
 import json
 import os
@@ -18,15 +20,23 @@ from tests.util import synth_depth_scene
 from tgpose_amd import PoseNet9D, seeded_state_dict, FLAGS
 from tgpose_amd.evaluater.RT_TDA_Evaluater import myEvaluater
 
-n_frames = int(sys.argv[1]) if len(sys.argv) > 1 else 128
-per = int(sys.argv[2]) if len(sys.argv) > 2 else 6
+argv = sys.argv[1:]
+only = None
+if "--sampler" in argv:
+    at = argv.index("--sampler")
+    only = argv[at + 1]
+    if only not in ("numpy", "device", "fps"):
+        raise SystemExit("--sampler must be numpy, device or fps")
+    del argv[at:at + 2]
+n_frames = int(argv[0]) if len(argv) > 0 else 128
+per = int(argv[1]) if len(argv) > 1 else 6
 dev = "cuda:0"
 net = PoseNet9D()
 net.load_state_dict(seeded_state_dict(0), strict=True)
 net = net.to(dev).eval()
 FLAGS.train = 0
 records = [dict(frame=synth_depth_scene(7000 + i, per)) for i in range(n_frames)]
-for sampler, graph in (("numpy", False), ("device", False), ("device", True)):
+for sampler, graph in (((only, False),) if only else (("numpy", False), ("device", False), ("device", True))):
     ev = myEvaluater(net, frames_per_batch=32, max_batch=192, sampler=sampler, seed=1, graph=graph)
     np.random.seed(0)
     torch.manual_seed(0)

@@ -318,6 +318,8 @@ SIGNATURES = {
     "tgp_emd_workspace_bytes": (c_i64, [c_int, c_int]),
     "tgp_emd_fwd": (c_int, [c_vp, c_vp, c_int, c_int, c_f32, c_int, c_vp, c_vp, c_vp, c_vp]),
     "tgp_emd_bwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
+    "tgp_fps_max_points": (c_int, []),
+    "tgp_fps": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "tgp_generate_rt": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     "tgp_canonicalize": (c_int, [c_vp] * 9 + [c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "tgp_heads_fused": (c_int, [ctypes.POINTER(HeadsFusedArgs), c_vp]),

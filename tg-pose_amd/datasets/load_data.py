@@ -179,6 +179,14 @@ def _selection(total, n_pts, rng):
     return np.arange(n_pts)
 
 
+def farthest_point_sample(xyz, npoint):
+    """PoseDataset.farthest_point_sample (load_data.py:382-393): the indices of ``npoint`` farthest points of xyz (M,3), a float32
+    GPU tensor, in selection order (core/utils/farthest_points_torch.farthest_points with init_center=True)"""
+    from ..core.utils.farthest_points_torch import farthest_points
+    _, idx = farthest_points(xyz, n_clusters=npoint, return_center_indexes=True, init_center=True)
+    return idx
+
+
 def train_clouds(items, img_size=256, rng=np.random, device="cuda", min_points=50, roi_mask_pro=None, roi_mask_r=3, dzi=False,
                  draws="host", seed=None, keys=None, batch_size=None):
     """items: list of dicts -- 'depth' (H,W) uint16 (load_depth's output), 'mask' (H,W) uint8 instance-id image (the reference reads
@@ -292,7 +300,8 @@ _POSE_KEYS = ("rotation", "translation", "fsnet_scale")
 
 
 def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min_points=50, operators=None, persistence=False,
-                roi_mask_pro=None, roi_mask_r=3, dzi=False, draws="host", seed=None, keys=None, batch_size=None, keep_draws=False):
+                roi_mask_pro=None, roi_mask_r=3, dzi=False, draws="host", seed=None, keys=None, batch_size=None, keep_draws=False,
+                pcl_select="random"):
     """``train_clouds`` plus the reference's two augmentations (load_data.py:333-350): the batch the trainer's step reads.
 
     items: ``train_clouds``' dicts, each also carrying its labels 'rotation' (3,3), 'translation' (3,), 'fsnet_scale' (3,) (the
@@ -325,10 +334,22 @@ def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min
     whose drawn window source_tables refuses counts as abandoned.  -> the dict above, all on the device, with aug_op (B,) int32
     (the OPERATOR_NAMES index) in place of aug_name, item_index (B,) int64 (the item in each slot, -1 without one), n_alive ()
     int32 = min(alive items, B) and status (len(items),) int32 (TGP_ITEM_* of include/tgpose.h).  keep_draws=True adds '_draws':
-    the draw buffers (DRAW_KEYS, one row per item) that _train_batch_from_draws replays."""
+    the draw buffers (DRAW_KEYS, one row per item) that _train_batch_from_draws replays.
+
+    pcl_select='fps' (opt-in; 'random' is everything above, unchanged, draw streams included): pcl_in is the farthest point sampling
+    of the augmented 2048-point cloud -- what the reference's _sample_points docstring announces and its farthest_point_sample
+    method computes, but its __getitem__ never calls (:366-393) -- by ops.farthest_points (csrc/fps.hip, one launch for the batch,
+    reading the padded rows in place; centroid start, DESIGN.md section 3 "Farthest point sampling").  A deviation from the
+    reference's stream: the second _sample_points permutation is NOT drawn, so with draws='host' every later
+    draw from ``rng`` moves up by that permutation; with draws='device' its site is simply not used and every other draw is the
+    same.  persistence=True then runs on the FPS pcl_in.  In this mode only, the batch also carries PC (B,2048,3), the augmented
+    cloud, and pcl_index (B,1024) int32, its rows in selection order: pcl_in == PC[pcl_index]."""
     from . import data_augmentation as da
     if draws not in ("host", "device"):
         raise ValueError("draws must be 'host' or 'device'")
+    if pcl_select not in ("random", "fps"):
+        raise ValueError("pcl_select must be 'random' or 'fps'")
+    fps = pcl_select == "fps"
     if persistence and any("pdh1" in it or "pdh2" in it for it in items):
         raise ValueError("train_batch: persistence=True computes pdh1 / pdh2; the items must not carry them")
     dev = torch.device(device)
@@ -339,7 +360,7 @@ def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min
         raise ValueError("train_batch: no items")
     if draws == "device":
         return _train_batch_device(items, seed, keys, batch_size, img_size, dev, min_points, ops_, persistence, roi_mask_pro, roi_mask_r,
-                                   dzi, keep_draws=keep_draws)
+                                   dzi, keep_draws=keep_draws, fps=fps)
     rr, counts = _roi_records(items, img_size, dev, rng, roi_mask_pro, roi_mask_r, dzi)
     deformed = roi_mask_pro is not None
     keep, sel2k, p1k, shuf, recs, names, defer = [], [], [], [], [], [], []
@@ -355,7 +376,8 @@ def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min
         s2 = _selection(total, 2048, rng)                                         # :335
         sel2k.append(s2)
         defor.append(de[0][torch.from_numpy(s2.astype(np.int64))])                # the rows of the selected points only
-        p1k.append(_selection(2048, 1024, rng).astype(np.int32))                  # :336
+        if not fps:
+            p1k.append(_selection(2048, 1024, rng).astype(np.int32))              # :336
         k = int(rng.randint(0, len(ops_)))                                        # :346
         rec = ops_[k].draw(2048, rng, gen)                                        # :347
         recs.append(rec)
@@ -390,11 +412,14 @@ def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min
         m = out["counts"][:, 0].cpu().numpy()
         for i in defer:
             shuf[i] = da.sampler_perm(int(m[i]), 1024, rng)
-    pcl_in = ops.gather_rows(out["pc"], up(np.stack(p1k)), torch.empty(B, 1024, 4, device=dev))[..., :3].contiguous()
+    pcl_index = ops.farthest_points(out["pc"], 1024) if fps else up(np.stack(p1k))
+    pcl_in = ops.gather_rows(out["pc"], pcl_index, torch.empty(B, 1024, 4, device=dev))[..., :3].contiguous()
     aug = ops.gather_rows(out["view"], up(np.stack(shuf)), torch.empty(B, 1024, 4, device=dev))[..., :3].contiguous()
     db = {k: v for k, v in stacked.items() if k not in _POSE_KEYS}
     db.update(pcl_in=pcl_in, aug_pcl_in=aug, rotation=out["R"], translation=out["t"], fsnet_scale=out["s"], aug_flags=out["flags"],
               aug_counts=out["counts"], item_index=up(np.asarray(keep, dtype=np.int64)), aug_name=names)
+    if fps:
+        db.update(PC=out["pc"][..., :3].contiguous(), pcl_index=pcl_index)
     if persistence:
         db["pdh1"], db["pdh2"] = ops.persistence_images(pcl_in)
     return db
@@ -496,11 +521,12 @@ DRAW_KEYS = ("tabs", "defor_on", "drop_bits", "aug_bb", "aug_rt_t", "aug_rt_R", 
              "noise", "drop_u", "shuf")
 
 
-def _augment_rows(rr, dr, lab, ops_, shuffle=None):
+def _augment_rows(rr, dr, lab, ops_, shuffle=None, fps=False):
     """the launches that follow the records, on every item's row, from the draws ``dr`` (device tensors under DRAW_KEYS): the 2048
     selected points, tgp_augment, the two row gathers.  shuffle(counts) draws 'shuf' when dr has none (it needs the launch's M).
+    fps: the rows of pcl_in are the farthest point sampling of the augmented cloud instead of dr['p1k'] (not read).
     -> dict of (D, ...) tensors: pcl_in, aug_pcl_in (padded to 4 columns), rotation, translation, fsnet_scale, aug_flags, aug_counts,
-    shuf"""
+    shuf; with fps also PC (the augmented cloud, padded to 4 columns) and pcl_index"""
     from . import data_augmentation as da
     D, dev = rr.recs.shape[0], rr.recs.device
     pc2k = ops.cloud_select(rr, dr["sel2k"])
@@ -509,13 +535,17 @@ def _augment_rows(rr, dr, lab, ops_, shuffle=None):
     view = dict(op=dr["op"], noise=dr["noise"], drop_ratio=dr["drop_ratio"], drop_u=dr["drop_u"], boxes=dr["boxes"], **_view_limits(ops_))
     out = ops.augment(pc2k, base=base, view=view, ld_out=4)
     shuf = dr["shuf"] if "shuf" in dr else shuffle(out["counts"])
-    pcl = ops.gather_rows(out["pc"], dr["p1k"], torch.empty(D, 1024, 4, device=dev))
+    p1k = ops.farthest_points(out["pc"], 1024) if fps else dr["p1k"]
+    pcl = ops.gather_rows(out["pc"], p1k, torch.empty(D, 1024, 4, device=dev))
     aug = ops.gather_rows(out["view"], shuf, torch.empty(D, 1024, 4, device=dev))
-    return dict(pcl_in=pcl, aug_pcl_in=aug, rotation=out["R"], translation=out["t"], fsnet_scale=out["s"], aug_flags=out["flags"],
+    rows = dict(pcl_in=pcl, aug_pcl_in=aug, rotation=out["R"], translation=out["t"], fsnet_scale=out["s"], aug_flags=out["flags"],
                 aug_counts=out["counts"], shuf=shuf)
+    if fps:
+        rows.update(PC=out["pc"], pcl_index=p1k)
+    return rows
 
 
-def _train_batch_from_draws(items, dr, img_size=256, device="cuda", min_points=50, operators=None):
+def _train_batch_from_draws(items, dr, img_size=256, device="cuda", min_points=50, operators=None, pcl_select="random"):
     """The host path's launches on GIVEN draws: ``dr`` holds host arrays under DRAW_KEYS, one row per item ('defor_on' / 'drop_bits'
     absent: no mask deformation) -- e.g. the buffers a draws='device' batch made, read back.  The counts are read back and the
     reference's rules applied on the host (_item_total; an item for which the host path raises counts as abandoned here).
@@ -537,15 +567,17 @@ def _train_batch_from_draws(items, dr, img_size=256, device="cuda", min_points=5
                 keep.append(d)
         except (ValueError, IndexError):
             pass
-    rows = _augment_rows(rr, t, _stack_labels(items, up), ops_)
+    rows = _augment_rows(rr, t, _stack_labels(items, up), ops_, fps=pcl_select == "fps")
     kt = up(np.asarray(keep, dtype=np.int64))
     out = {k: v[kt].contiguous() for k, v in rows.items()}
-    out["pcl_in"], out["aug_pcl_in"] = out["pcl_in"][..., :3].contiguous(), out["aug_pcl_in"][..., :3].contiguous()
+    for k in ("pcl_in", "aug_pcl_in", "PC"):
+        if k in out:
+            out[k] = out[k][..., :3].contiguous()
     return out, keep
 
 
 def _train_batch_device(items, seed, keys, batch_size, img_size, dev, min_points, ops_, persistence, roi_mask_pro, roi_mask_r, dzi,
-                        keep_draws=False, clouds_only=False):
+                        keep_draws=False, clouds_only=False, fps=False):
     from . import data_augmentation as da
     lib = da._lib
     D = len(items)
@@ -574,7 +606,8 @@ def _train_batch_device(items, seed, keys, batch_size, img_size, dev, min_points
     rr = ops.roi_cloud(*args, camk, roi_size=img_size, tables=tabs, mask_val=mval, cut_frac=0.15, defor=defor)
     status, slot, n_alive = ops.draw_alive(rr.counts, B, min_points, up(sc["forced"]))
     dr["sel2k"] = ops.draw_selection(rr.counts[:, 2], keys_t, seed, lib.SITE_SEL2K, 2048)
-    dr["p1k"] = ops.draw_selection(2048, keys_t, seed, lib.SITE_SEL1K, 1024)
+    if not fps:
+        dr["p1k"] = ops.draw_selection(2048, keys_t, seed, lib.SITE_SEL1K, 1024)
     if clouds_only:
         pc2k = ops.cloud_select(rr, dr["sel2k"])
         pc1k = ops.gather_rows(torch.nn.functional.pad(pc2k, (0, 1)), dr["p1k"], torch.empty(D, 1024, 4, device=dev))
@@ -584,12 +617,15 @@ def _train_batch_device(items, seed, keys, batch_size, img_size, dev, min_points
     dr.update(ops.draw_fill(keys_t, seed, 2048, defor=True, noise=(jit.std, jit.clip) if jit is not None else (0.0, 0.0), drop_u=True))
     lab = _stack_labels(items, up)
     rows = _augment_rows(rr, dr, lab, ops_,
-                         shuffle=lambda counts: ops.draw_selection(counts[:, 0], keys_t, seed, lib.SITE_SHUFFLE, 1024, shuffle_always=True))
+                         shuffle=lambda counts: ops.draw_selection(counts[:, 0], keys_t, seed, lib.SITE_SHUFFLE, 1024, shuffle_always=True),
+                         fps=fps)
     names = [k for k in rows if k != "shuf"] + [k for k in lab if k not in _POSE_KEYS]
     src = [rows[k] for k in rows if k != "shuf"] + [lab[k] for k in lab if k not in _POSE_KEYS] + [up(sc["op_index"])]
     got = ops.gather_slots(slot, src)
     db = dict(zip(names + ["aug_op"], got))
     db["pcl_in"], db["aug_pcl_in"] = db["pcl_in"][..., :3].contiguous(), db["aug_pcl_in"][..., :3].contiguous()
+    if fps:
+        db["PC"] = db["PC"][..., :3].contiguous()
     db.update(n_alive=n_alive.reshape(()), status=status, item_index=slot.long())
     if persistence:            # no read here either: a failed cloud's images are zeros and 'pd_status' names the reason
         db["pdh1"], db["pdh2"], db["pd_status"] = ops.persistence_images(db["pcl_in"], check_status=False)
@@ -701,11 +737,13 @@ class TrainBatches(object):
       that builds it, and set_epoch reproduces them.  There is no refill: a batch is handed its own items plus ``spares`` more --
       the indices that follow it in this rank's epoch order, wrapping (they still appear in their own batch) -- and holds the first
       batch_size alive ones ('n_alive', 'status', 'item_index' as train_batch documents; -1 marks a slot without an item).
+    * pcl_select='fps' (train_batch's option of that name): pcl_in by farthest point sampling; the batches then also carry PC and
+      pcl_index.
     rng (NumPy) and gen (torch CPU generator; None: torch's default) feed train_batch."""
 
     def __init__(self, items, batch_size, rng=np.random, gen=None, device="cuda", prefetch=True, shuffle=True, drop_last=False,
                  persistence=False, dzi=False, roi_mask_pro=None, roi_mask_r=3, category_tables=None, min_points=50, operators=None,
-                 img_size=256, rank=None, world_size=None, seed=None, draws="host", spares=0):
+                 img_size=256, rank=None, world_size=None, seed=None, draws="host", spares=0, pcl_select="random"):
         import torch.distributed as dist
         if not items:
             raise ValueError("TrainBatches: no items")
@@ -714,7 +752,9 @@ class TrainBatches(object):
         self.prefetch = bool(prefetch) and self.device.type == "cuda"
         self.shuffle, self.drop_last = shuffle, drop_last
         self.kw = dict(img_size=img_size, device=self.device, min_points=min_points, operators=operators, persistence=persistence,
-                       roi_mask_pro=roi_mask_pro, roi_mask_r=roi_mask_r, dzi=dzi)
+                       roi_mask_pro=roi_mask_pro, roi_mask_r=roi_mask_r, dzi=dzi, pcl_select=pcl_select)
+        if pcl_select not in ("random", "fps"):
+            raise ValueError("TrainBatches: pcl_select must be 'random' or 'fps'")
         on = dist.is_available() and dist.is_initialized()
         self.world_size = int(world_size if world_size is not None else (dist.get_world_size() if on else 1))
         self.rank = int(rank if rank is not None else (dist.get_rank() if on else 0))

@@ -32,6 +32,8 @@ class myEvaluater:
     """``sampler='numpy'``: the reference's draws (one small read-back per chunk for the point counts).  ``sampler='device'``:
     nothing is read back until a chunk's poses are; with ``overlap`` (default) chunk c's results are fetched after chunk c+1
     has been enqueued, so packing / uploading the next frames runs beside the GPU's work on the current ones.
+    ``sampler='fps'``: as 'device', with farthest point sampling of each detection's cloud (``fps_pool`` candidates at most,
+    load_data_eval.clouds_from_frames) in place of the keyed draw: no random number enters, two runs give the same poses.
 
     ``recon_stats=True`` (what ``compute_degree_cm_mAP(eval_recon=True)`` reads, eval_utils_v1.py:1517-1518): the forwards run
     full -- the decoder is needed -- and each detection dict gains ``chamfer_dis_cass`` (``calc_cd``'s cd_p of the reconstruction
@@ -39,7 +41,10 @@ class myEvaluater:
     with its defaults), one value per detection.  Not available together with ``graph``."""
 
     def __init__(self, net, frames_per_batch=32, max_batch=256, sampler="numpy", seed=0, overlap=True, graph=False,
-                 recon_stats=False):
+                 recon_stats=False, fps_pool=4096):
+        if sampler not in ("numpy", "device", "fps"):
+            raise ValueError("sampler must be 'numpy', 'device' or 'fps'")
+        self.fps_pool = int(fps_pool)
         if recon_stats and graph:
             raise ValueError("recon_stats is not available on the captured path: pass graph=False")
         self.recon_stats = bool(recon_stats)
@@ -61,7 +66,8 @@ class myEvaluater:
             clouds = lde.clouds_from_frames(frames, camK, device=self.device)
             alive, ok = [c is not None for c in clouds], None
         else:
-            clouds, ok = lde.clouds_from_frames(frames, camK, sampler="device", seed=self.seed, device=self.device)
+            clouds, ok = lde.clouds_from_frames(frames, camK, sampler=self.sampler, seed=self.seed, device=self.device,
+                                                fps_pool=self.fps_pool)
             alive = [True] * len(frames)                     # decided in _finish from `ok`
             # an invalid detection's rows are NaN: zero them for the forward (objects are independent in eval mode) and drop
             # the frame afterwards, as the reference drops it (load_data_eval.py:332-337)

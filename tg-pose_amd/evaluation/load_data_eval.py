@@ -16,6 +16,9 @@ reference's order (frame by frame, detection by detection; a frame the reference
 the draws of its earlier detections, as there), and their prefixes are uploaded for the gather.
 ``sampler='device'`` draws a keyed pseudo-random permutation on the device instead (``tgp_cloud_sample``): nothing is
 read back, frames cannot be dropped on the host, so invalid detections come back as NaN rows with ``valid`` False.
+``sampler='fps'`` draws nothing at all: farthest point sampling (``tgp_fps``, csrc/fps.hip -- what the reference's ``_sample_points``
+docstring announces) of each detection's cloud, thinned evenly to ``fps_pool`` candidates first when it is longer.  Like
+``'device'`` it reads nothing back and returns ``(clouds, valid)``; the result is a pure function of the frames.
 
 What stays on the host, as integer arithmetic on four numbers per detection: ``get_bbox`` (the window rule of
 ``tools.eval_utils``, source twin ``network/point_sample/pc_sample_sphere.py:456-484``).  File reading / unpickling
@@ -130,14 +133,44 @@ def build(frames, camK=REAL_INTRINSICS, img_size=256, device="cuda"):
     return RoiClouds(ops.roi_cloud(*upload(frames, camK, dev), roi_size=img_size), per_frame)
 
 
-def clouds_from_frames(frames, camK=REAL_INTRINSICS, img_size=256, n_pts=1024, sampler="numpy", rng=np.random, seed=0, device="cuda"):
+def _fps_clouds(rc, n_pts, fps_pool):
+    """sampler='fps': per detection the candidates are the whole cloud (total <= fps_pool) or the evenly spaced records
+    floor(i * total / fps_pool), i < fps_pool -- integer arithmetic on the device -- gathered by tgp_cloud_select; tgp_fps on the
+    candidates with per-detection counts (a cloud of at most n_pts points is tiled there, as _sample_points tiles it); one row
+    gather.  An invalid detection selects record -1 throughout, whose point is NaN."""
+    recs = rc.records.recs
+    dev = recs.device
+    m = min(int(fps_pool), recs.shape[1])
+    total = rc.counts[:, 2].long().clamp(min=0, max=recs.shape[1])
+    ok = (rc.counts[:, 2] > 0) & (rc.counts[:, 0] > 1) & (rc.counts[:, 1] > 1)
+    cand = torch.where(ok, total.clamp(max=m), torch.zeros_like(total))
+    i = torch.arange(m, device=dev, dtype=torch.int64)[None, :]
+    sel = torch.where((total > m)[:, None], (i * total[:, None]) // m, i)
+    sel = torch.where(i < cand[:, None], sel, torch.full_like(sel, -1)).int()
+    pts = ops.cloud_select(rc.records, sel)
+    idx = ops.farthest_points(pts, n_pts, counts=cand.clamp(min=1).int())
+    out = torch.gather(pts, 1, idx.long()[:, :, None].expand(-1, -1, 3))
+    return out, ok
+
+
+def clouds_from_frames(frames, camK=REAL_INTRINSICS, img_size=256, n_pts=1024, sampler="numpy", rng=np.random, seed=0, device="cuda",
+                       fps_pool=4096):
     """-> list over frames of ``pcl_in`` (n_det, n_pts, 3) float32 GPU tensors; ``None`` for a frame the reference's
     ``__getitem__`` drops (:332-337).  Raises IndexError / ZeroDivisionError where the reference does (fewer than 26 valid
-    points :350, an empty cloud after the cut :411).  With sampler='device' returns (list of tensors, list of bool masks)."""
+    points :350, an empty cloud after the cut :411).  With sampler='device' or 'fps' returns (list of tensors, list of bool masks).
+    sampler='fps' consumes neither ``rng`` nor ``seed``; ``fps_pool`` (at most ops.fps_max_points()) is the number of candidates a
+    longer cloud is thinned to before the sampling."""
+    if sampler == "fps" and not 1 <= int(fps_pool) <= ops.fps_max_points():
+        raise ValueError("fps_pool must be in [1, %d] (ops.fps_max_points())" % ops.fps_max_points())
     rc = build(frames, camK, img_size, device)
     D = sum(rc.per_frame)
     dev = torch.device(device)
     empty = torch.zeros(0, n_pts, 3, device=dev)
+    if sampler == "fps":
+        if D == 0:
+            return [empty for _ in rc.per_frame], [torch.zeros(0, dtype=torch.bool, device=dev) for _ in rc.per_frame]
+        out, ok = _fps_clouds(rc, n_pts, fps_pool)
+        return list(out.split(rc.per_frame)), list(ok.split(rc.per_frame))
     if sampler == "device":
         if D == 0:
             return [empty for _ in rc.per_frame], [torch.zeros(0, dtype=torch.bool, device=dev) for _ in rc.per_frame]
@@ -145,7 +178,7 @@ def clouds_from_frames(frames, camK=REAL_INTRINSICS, img_size=256, n_pts=1024, s
         ok = (rc.counts[:, 2] > 0) & (rc.counts[:, 0] > 1) & (rc.counts[:, 1] > 1)
         return list(out.split(rc.per_frame)), list(ok.split(rc.per_frame))
     if sampler != "numpy":
-        raise ValueError("sampler must be 'numpy' or 'device'")
+        raise ValueError("sampler must be 'numpy', 'device' or 'fps'")
     if D == 0:
         return [empty for _ in rc.per_frame]
     counts = rc.counts.cpu().numpy()                         # the one read-back: 12 bytes per detection

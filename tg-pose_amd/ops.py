@@ -1075,6 +1075,43 @@ def emd_bwd(xyz1, xyz2, grad_dist, assignment):
     return grad
 
 
+def fps_max_points():
+    return int(_lib.lib().tgp_fps_max_points())
+
+
+def farthest_points(xyz, n, counts=None, start=None, init_center=True, return_distances=False, return_clusters=False):
+    """Farthest point sampling of a batch of clouds in one launch (tgp_fps, csrc/fps.hip; the reference's farthest_points bit for bit,
+    DESIGN.md section 3 "Farthest point sampling").
+
+    xyz (B,M,3) or (B,M,4) float32 whose rows are 3 or 4 floats apart (a [..., :3] view of padded rows is read in place; a fourth
+    column is not read), M <= fps_max_points().  counts (B,) int32: each cloud's live prefix, 1 <= counts[b] <= M (default M).
+    start (B,3): the virtual first centre; None with init_center: the cloud's centroid (pairwise-tree sum); init_center=False: the
+    first centre is row 0.  -> idx (B,n) int32: the centres in selection order where counts[b] > n, else i % counts[b]
+    [, distances (B,M) float32][, clusters (B,M) int32]; rows at and beyond counts[b] are NaN / -1."""
+    _f32(xyz, "xyz", 3)
+    B, M, C = xyz.shape
+    ld = xyz.stride(1) if M > 1 else C                       # the stride of a dimension of size 1 says nothing
+    if C not in (3, 4) or ld not in (3, 4) or C > ld or xyz.stride(2) != 1 or (B > 1 and xyz.stride(0) != M * ld):
+        raise ValueError("farthest_points: xyz must be (B, M, 3 or 4) with rows 3 or 4 floats apart and clouds M rows apart")
+    n = int(n)
+    if B < 1 or M < 1 or n < 1:
+        raise ValueError("farthest_points: B, M and n must be at least 1")
+    if M > fps_max_points():
+        raise ValueError("farthest_points: M = %d is above the cap of %d points; thin the cloud first" % (M, fps_max_points()))
+    if counts is not None and _i32(counts, "counts").shape != (B,):
+        raise ValueError("farthest_points: counts must be (B,)")
+    if start is not None and (not _f32(start, "start").is_contiguous() or start.shape != (B, 3)):
+        raise ValueError("farthest_points: start must be a contiguous (B,3) tensor")
+    dev = xyz.device
+    idx = torch.empty(B, n, device=dev, dtype=torch.int32)
+    dist = torch.full((B, M), float("nan"), device=dev) if return_distances else None
+    clusters = torch.full((B, M), -1, device=dev, dtype=torch.int32) if return_clusters else None
+    check(_lib.lib().tgp_fps(_p(xyz), ld, _p(counts), B, M, n, _p(start), 1 if init_center else 0, _p(idx), _p(dist), _p(clusters),
+                             _stream(xyz)), "tgp_fps")
+    out = (idx,) + ((dist,) if return_distances else ()) + ((clusters,) if return_clusters else ())
+    return out[0] if len(out) == 1 else out
+
+
 def canonicalize(points, gR, p_g, f_g, p_r, f_r, p_t, p_s, sym):
     """R_DCD pose normalisation -> (points_re_n (B,n,3), R (B,3,3))"""
     c = lambda t: _f32(t.contiguous(), "arg")
