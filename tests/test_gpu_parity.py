@@ -3629,6 +3629,69 @@ def test_planes_gather_equals_gather_then_split(ops):
     assert torch.equal(d0, d1) and torch.equal(P0.buf, P1.buf) and torch.equal(P0.amax, P1.amax)
 
 
+def _ref_units(w, pairs, steps, permuted=False):
+    """numpy restatement of the fused kernels' staging image: `pairs` (units, 32, 2) names the (K-step, output block) of pair q of each
+    64 KB unit; a pair is two 1 KB pieces (plane 0: fp16 hi, plane 1: lo), a piece [lane = 32 h + r][8 fp16] = W[32 block + r][k], where
+    slot 8 h + t of a K-step is column 16 step + 8 h + t (natural K order) or 32 (step >> 1) + 16 (step & 1) + 8 (t >> 2) + 4 h + (t & 3)
+    (permuted: the order in which the previous layer's accumulators hold a block's channels).  Steps >= `steps`, columns >= K and rows
+    >= N are zero.  Returns the image as uint16."""
+    N, K = w.shape
+    step = pairs[:, :, 0].reshape(-1, 32, 1, 1, 1)                     # axes: unit, pair q, half h, row r, slot t
+    blk = pairs[:, :, 1].reshape(-1, 32, 1, 1, 1)
+    h, r, t = np.arange(2).reshape(1, 1, 2, 1, 1), np.arange(32).reshape(1, 1, 1, 32, 1), np.arange(8).reshape(1, 1, 1, 1, 8)
+    col = 32 * (step >> 1) + 16 * (step & 1) + 8 * (t >> 2) + 4 * h + (t & 3) if permuted else 16 * step + 8 * h + t
+    row, col, live = np.broadcast_arrays(32 * blk + r, col, step < steps)
+    ok = live & (col < K) & (row < N)
+    v = np.where(ok, w[np.minimum(row, N - 1), np.minimum(col, K - 1)], np.float32(0)).astype(np.float32)
+    hi = v.astype(np.float16)
+    lo = (v - hi.astype(np.float32)).astype(np.float16)
+    return np.stack([hi, lo], axis=2).view(np.uint16).reshape(-1)      # [unit][q][plane][h][r][t]
+
+
+def _unit_pairs(nb, units_per_group, groups):
+    """(step, block) of every pair: a unit holds nb output blocks of 32 / nb K-steps, pair q = s * nb + j; units_per_group consecutive units
+    walk the K-steps of a group of nb output blocks"""
+    q = np.arange(32)
+    return np.array([[((w * (32 // nb) + q // nb), (gr * nb + q % nb)) for w in range(units_per_group)] for gr in range(groups)]) \
+        .transpose(0, 1, 3, 2).reshape(-1, 32, 2)
+
+
+def test_staging_unit_images_equal_their_documented_layout(ops):
+    """tgp_proj_pack, tgp_hs_chain_pack and tgp_dec_pack (one pack kernel behind the three) against the layout the kernels' comments
+    document, bit for bit: unit, pair, plane, lane 32 h + r, eight fp16 values; hi = fp16(v), lo = fp16(v - fp32(hi)); natural and
+    permuted K order; zero padding of the columns beyond K (K1 = 132 is no multiple of 16) and of the steps beyond the layer's."""
+    gen = torch.Generator().manual_seed(77)
+
+    def weights(n, k):
+        w = torch.randn(n, k, generator=gen) * 0.3
+        w[0, 0], w[1, 3], w[2, 5], w[3, 7], w[n - 1, k - 1] = 0.5, -2.0, 0.0, 30001.37, 1.0      # exact fp16 values (lo = 0), one near 3e4
+        return w
+
+    def image(t):
+        return t.cpu().numpy().view(np.uint16)
+
+    for n, k in [(128, 128), (256, 256)]:                              # per group of four output blocks K / 128 units of eight K-steps
+        w = weights(n, k)
+        want = _ref_units(w.numpy(), _unit_pairs(4, k // 128, n // 128), k // 16)
+        assert (want.reshape(-1, 32, 2, 512)[:, :, 1] != 0).any()      # (the lo halves carry something)
+        assert np.array_equal(image(ops.proj_pack(g(w))), want)
+    # an HS layer's last GEMM + the next projection: layer 1 = 9 K-steps x 4 blocks = 36 pairs (two units in memory, the second one
+    # K-step 8 -- its columns 132 .. 143 zero -- and 28 empty pairs), then layer 2 as a projection
+    w1, w2 = weights(128, 132), weights(1152, 128)
+    want = np.concatenate([_ref_units(w1.numpy(), _unit_pairs(4, 2, 1), 9), _ref_units(w2.numpy(), _unit_pairs(4, 1, 9), 8)])
+    assert want.size * 2 == 11 * 65536 and np.array_equal(image(ops.hs_chain_pack(g(w1), g(w2))), want)
+    # the decoder: layer 2 rows 0-255 (8 units of 4 K-steps x 8 blocks) | layer 3 columns 0-255 (4 units) | the same of rows / columns
+    # 256-511 | layer 4 (2 units of 8 K-steps x 4 blocks); layers 3 and 4 in permuted K order, layer 2 as its operand comes
+    d2, d3, d4 = weights(512, 512), weights(256, 512), weights(128, 256)
+    for h1_permuted in (False, True):
+        want = np.concatenate([_ref_units(d2[:256].numpy(), _unit_pairs(8, 8, 1), 32, h1_permuted),
+                               _ref_units(d3[:, :256].numpy(), _unit_pairs(8, 4, 1), 16, True),
+                               _ref_units(d2[256:].numpy(), _unit_pairs(8, 8, 1), 32, h1_permuted),
+                               _ref_units(d3[:, 256:].numpy(), _unit_pairs(8, 4, 1), 16, True),
+                               _ref_units(d4.numpy(), _unit_pairs(4, 2, 1), 16, True)])
+        assert np.array_equal(image(ops.dec_pack(g(d2), g(d3), g(d4), h1_permuted=h1_permuted)), want)
+
+
 @pytest.mark.parametrize("M,N,K,rpo", [(4112, 1152, 128, 1028), (1300, 640, 268, 100), (1310, 384, 64, 64), (8224 // 4, 512, 512, 257),
                                        (2056, 128, 132, 1028), (300, 128, 64, 100)])
 def test_gemm_pp_bit_identical_to_split_kernel(ops, M, N, K, rpo):

@@ -23,13 +23,7 @@
 // Against the four launches it replaces (three gemm_pp launches + tgp_rows_out) layer 2's sums are identical; layers 3 / 4 add the
 // sixteen products of a K-step in another order (the permutation) and the last conv adds its 128 products per half wave first: results
 // agree to rounding (tests/test_gpu_parity.py::test_decoder_chain_on_planes_only states the bar), not bit for bit.
-#include "tgp_common.h"
-#include "../../include/tgpose.h"
-
-typedef _Float16 df16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 df16x4 __attribute__((ext_vector_type(4)));
-typedef float df32x4 __attribute__((ext_vector_type(4)));
-typedef float df32x16 __attribute__((ext_vector_type(16)));
+#include "mfma_unit.h"
 
 #define DF_C1 512                          // channels of the operand (the first conv's output) and of layer 2
 #define DF_C3 256
@@ -45,7 +39,6 @@ typedef float df32x16 __attribute__((ext_vector_type(16)));
 #define DF_U4 2
 #define DF_UNITS (2 * DF_U2H + 2 * DF_U3H + DF_U4)
 #define DF_NVEC (3 * DF_C1 + 3 * DF_C3 + 3 * DF_C4 + 3 * DF_C4 + 4)      // bias | scale | shift per layer, W5 (3 x 128), b5 (3, padded)
-#define DF_SB() __builtin_amdgcn_sched_barrier(0)
 
 struct DecParams {
     const char *h1_pl; int h1_kt; const uint32_t *h1_amax;       // the operand: (M, 512) as blocked fp16 planes + its magnitude words
@@ -58,19 +51,6 @@ struct DecParams {
     const int *pred;                                             // (may be NULL) run only while *pred == 0 ... unused
     int M, tiles;
 };
-
-__device__ __forceinline__ float df_mix_lo(uint32_t hpair, float v)     // v - (float)(low half of hpair), one rounding
-{
-    float d;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hpair), "v"(v));
-    return d;
-}
-__device__ __forceinline__ float df_mix_hi(uint32_t hpair, float v)     // v - (float)(high half of hpair)
-{
-    float d;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hpair), "v"(v));
-    return d;
-}
 
 __global__ __launch_bounds__(256, 1) void dec_fused_kernel(DecParams p)
 {
@@ -85,14 +65,11 @@ __global__ __launch_bounds__(256, 1) void dec_fused_kernel(DecParams p)
     const int rb = min(m0 >> 5, nblk - 1);
 
     // ---- staging: unit u is 64 KB at units + 64 KB u; piece j = 4 j0 + wave is 1 KB at offset 1024 j of the unit and of the buffer
-    const uint32_t voff0 = lane * 16 + wave * 1024;
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)df_smem) + wave * 1024;
+    const uint32_t voff0 = tgp_dma_voff0(lane, wave), lds0 = tgp_dma_lds0(df_smem, wave);
     const char *u_src = p.units;                                 // scalar base of the unit being staged
     auto dma = [&](const int buf, const int j0) {
         const uint32_t lds = lds0 + buf * DF_UNIT + j0 * 4096;
-        const uint32_t vo = voff0 + j0 * 4096;
-        // inline assembly: opaque to the compiler's counters; vmcnt(0) is written by hand before the barrier that ends a unit
-        asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(vo), "s"(u_src), "{m0}"(lds) : "memory");
+        tgp_lds_dma(voff0 + j0 * 4096, u_src, lds);
     };
 #pragma unroll
     for (int j0 = 0; j0 < DF_NDMA; ++j0) dma(0, j0);
@@ -111,7 +88,7 @@ __global__ __launch_bounds__(256, 1) void dec_fused_kernel(DecParams p)
     // predicated fp32 chain to redo the layers (as gemm_pp_tile does for a planes-only operand)
     if (p.h1_amax && m0 < p.M) {
         const uint32_t am = p.h1_amax[rb];
-        if ((am >= 0x477fe000u || (am != 0u && am < 0x3d800000u)) && lane == 0) atomicOr(p.flag, 1);
+        if (TGP_FP16_OUT_OF_RANGE(am) && lane == 0) atomicOr(p.flag, 1);
     }
     // the wave's points as B fragments of layer 2: K-step kt, plane q at h1_pl + ((rb * kt_all + kt) * 2 + q) * 1024 + 16 lane
     const char *h1 = p.h1_pl + (int64_t)rb * p.h1_kt * 2048 + lane * 16;
@@ -122,9 +99,9 @@ __global__ __launch_bounds__(256, 1) void dec_fused_kernel(DecParams p)
 #pragma unroll
     for (int i = 0; i < 8; ++i) load_h1(0, bcur, i);
 
-    df32x16 acc2[8];                                             // one half of layer 2's sums, then (in place) its activations as fp16 hi / lo fragments
-    df32x16 acc3[DF_C3 / 32];
-    df32x16 acc4[DF_C4 / 32];
+    f32x16 acc2[8];                                             // one half of layer 2's sums, then (in place) its activations as fp16 hi / lo fragments
+    f32x16 acc3[DF_C3 / 32];
+    f32x16 acc4[DF_C4 / 32];
 #pragma unroll
     for (int j = 0; j < DF_C3 / 32; ++j)
 #pragma unroll
@@ -136,7 +113,7 @@ __global__ __launch_bounds__(256, 1) void dec_fused_kernel(DecParams p)
     float4 e_b, e_sc, e_sh, e_v;
     uint32_t e_hi[8], e_lo[8];                                   // the block's packed halves: [2 g] = channels 0, 1 of group g, [2 g + 1] = 2, 3
     float e_l4[4];
-    auto epi = [&](df32x16 &acc, const float *vec, const int C, const int blk, const int sl) {
+    auto epi = [&](f32x16 &acc, const float *vec, const int C, const int blk, const int sl) {
         const int g = sl >> 3, ph = sl & 7;
         const float *pv = vec + 32 * blk + 4 * h + 8 * g;
         if (ph == 0) {                                            // (the vectors two gaps ahead of their first use)
@@ -154,14 +131,14 @@ __global__ __launch_bounds__(256, 1) void dec_fused_kernel(DecParams p)
             // ReLU as max(v, -0): what `v > 0 ? v : v * 0` gives for every number (a NaN becomes -0; non-finite sums are caught at the end)
             e_v.x = fmaxf(e_v.x, -0.f), e_v.y = fmaxf(e_v.y, -0.f), e_v.z = fmaxf(e_v.z, -0.f), e_v.w = fmaxf(e_v.w, -0.f);
         } else if (ph == 6) {
-            const df32x4 x = {e_v.x, e_v.y, e_v.z, e_v.w};
-            const uint2 hh = __builtin_bit_cast(uint2, __builtin_convertvector(x, df16x4));
+            const f32x4 x = {e_v.x, e_v.y, e_v.z, e_v.w};
+            const uint2 hh = __builtin_bit_cast(uint2, __builtin_convertvector(x, f16x4));
             e_hi[2 * g] = hh.x, e_hi[2 * g + 1] = hh.y;
-            e_l4[0] = df_mix_lo(hh.x, e_v.x), e_l4[1] = df_mix_hi(hh.x, e_v.y);
+            e_l4[0] = tgp_mix_lo(hh.x, e_v.x), e_l4[1] = tgp_mix_hi(hh.x, e_v.y);
         } else {
-            e_l4[2] = df_mix_lo(e_hi[2 * g + 1], e_v.z), e_l4[3] = df_mix_hi(e_hi[2 * g + 1], e_v.w);
-            const df32x4 rest = {e_l4[0], e_l4[1], e_l4[2], e_l4[3]};
-            const uint2 ll = __builtin_bit_cast(uint2, __builtin_convertvector(rest, df16x4));
+            e_l4[2] = tgp_mix_lo(e_hi[2 * g + 1], e_v.z), e_l4[3] = tgp_mix_hi(e_hi[2 * g + 1], e_v.w);
+            const f32x4 rest = {e_l4[0], e_l4[1], e_l4[2], e_l4[3]};
+            const uint2 ll = __builtin_bit_cast(uint2, __builtin_convertvector(rest, f16x4));
             e_lo[2 * g] = ll.x, e_lo[2 * g + 1] = ll.y;
             if (g == 3) {                                        // the block's last slice: the packed halves go back into the accumulator
 #pragma unroll
@@ -169,47 +146,22 @@ __global__ __launch_bounds__(256, 1) void dec_fused_kernel(DecParams p)
             }
         }
     };
-    auto frag = [&](const df32x16 &a, const int half, const int plane) {       // K-step `half` of a converted block, plane 0 = hi
+    auto frag = [&](const f32x16 &a, const int half, const int plane) {       // K-step `half` of a converted block, plane 0 = hi
         const int o = plane * 8 + half * 4;
-        return __builtin_bit_cast(df16x8, make_uint4(__float_as_uint(a[o]), __float_as_uint(a[o + 1]), __float_as_uint(a[o + 2]), __float_as_uint(a[o + 3])));
+        return __builtin_bit_cast(f16x8, make_uint4(__float_as_uint(a[o]), __float_as_uint(a[o + 1]), __float_as_uint(a[o + 2]), __float_as_uint(a[o + 3])));
     };
     const float *v2 = s_vec, *v3 = s_vec + 3 * DF_C1, *v4 = v3 + 3 * DF_C3, *w5 = v4 + 3 * DF_C4, *b5 = w5 + 3 * DF_C4;
 
-    __builtin_amdgcn_s_waitcnt(0x0f70);                          // vmcnt(0): this wave's DMA has landed
+    __builtin_amdgcn_s_waitcnt(tgp_waitcnt(0));                  // vmcnt(0): this wave's DMA has landed
     __syncthreads();
 
-    // One staging unit = 32 (K-step s, output block j) pairs, q = s * NB + j, three MFMAs each (smallest terms first, as in the tile kernel:
-    // W lo x H hi, W hi x H lo, W hi x H hi); gap 1: the weight fragments of pair q + 2 (+ FILL_A), gap 2: a DMA piece of the next unit
-    // (+ FILL_B), gap 3: FILL_C.  BH / BL: the points' hi / lo fragments of K-step s.
+    // unit GU of the image (buffer GU & 1) as TGP_UNIT_BODY; STAGE: unit GU + 1 is staged in its gaps, all of it landed at its end
 #define DF_BODY(GU, ACC, NB, BH, BL, STAGE, FILL_A, FILL_B, FILL_C)                                                          \
     {                                                                                                                        \
-        const char *wrow = df_smem + ((GU) & 1) * DF_UNIT + lane * 16;                                                       \
+        const char *wbuf = df_smem + ((GU) & 1) * DF_UNIT + lane * 16;                                                       \
         u_src = p.units + (int64_t)((GU) + 1) * DF_UNIT;                                                                     \
-        auto wfrag = [&](int q, int plane) { return *reinterpret_cast<const uint4 *>(wrow + (q * 2 + plane) * 1024); };      \
-        uint4 wh0 = wfrag(0, 0), wl0 = wfrag(0, 1), wh1 = wfrag(1, 0), wl1 = wfrag(1, 1);                                    \
-        DF_SB();                                                                                                             \
-        _Pragma("unroll") for (int q = 0; q < 32; ++q) {                                                                     \
-            const int s = q / (NB), j = q % (NB);                                                                            \
-            uint4 wh2 = wh1, wl2 = wl1;                                                                                      \
-            const df16x8 bh = BH, bl = BL;                                                                                   \
-            ACC[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(df16x8, wl0), bh, ACC[j], 0, 0, 0);           \
-            DF_SB();                                                                                                         \
-            if (q + 2 < 32) wh2 = wfrag(q + 2, 0), wl2 = wfrag(q + 2, 1);                                                    \
-            FILL_A;                                                                                                          \
-            DF_SB();                                                                                                         \
-            ACC[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(df16x8, wh0), bl, ACC[j], 0, 0, 0);           \
-            DF_SB();                                                                                                         \
-            if ((STAGE) && q < DF_NDMA) dma(((GU) & 1) ^ 1, q);                                                              \
-            FILL_B;                                                                                                          \
-            DF_SB();                                                                                                         \
-            ACC[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(df16x8, wh0), bh, ACC[j], 0, 0, 0);           \
-            DF_SB();                                                                                                         \
-            FILL_C;                                                                                                          \
-            DF_SB();                                                                                                         \
-            wh0 = wh1, wl0 = wl1, wh1 = wh2, wl1 = wl2;                                                                      \
-        }                                                                                                                    \
-        __builtin_amdgcn_s_waitcnt(0x0f70);     /* vmcnt(0): this wave's share of the next unit has landed (and its fragments) */ \
-        __syncthreads();                        /* ... everybody's has, and this buffer's readers are done */                \
+        TGP_UNIT_BODY(wbuf, 32, NB, ACC, BH, BL, if ((STAGE) && q < DF_NDMA) dma(((GU) & 1) ^ 1, q), FILL_A, FILL_B,         \
+                      TGP_UNIT_GAP(FILL_C), TGP_UNIT_END(tgp_waitcnt(0)))                                                    \
     }
     // layer 3, unit U of a half (HALF = 0 / 1): K-steps 4 U .. 4 U + 3 of the half = converted blocks 2 U, 2 U + 1 of acc2; in its gaps the
     // epilogue of blocks 2 U + 2, 2 U + 3 (two slices per pair); its last unit loads the second half's first operand fragments
@@ -230,7 +182,7 @@ __global__ __launch_bounds__(256, 1) void dec_fused_kernel(DecParams p)
         const int g0 = half * (DF_U2H + DF_U3H);
 #pragma unroll 1
         for (int u = 0; u < DF_U2H; ++u) {
-            DF_BODY(g0 + u, acc2, 8, __builtin_bit_cast(df16x8, bcur[s][0]), __builtin_bit_cast(df16x8, bcur[s][1]), true, ,
+            DF_BODY(g0 + u, acc2, 8, __builtin_bit_cast(f16x8, bcur[s][0]), __builtin_bit_cast(f16x8, bcur[s][1]), true, ,
                     , if (q >= 16 && q < 24 && u + 1 < DF_U2H) load_h1(u + 1, bnxt, q - 16))
 #pragma unroll
             for (int i = 0; i < 8; ++i) bcur[i >> 1][i & 1] = bnxt[i >> 1][i & 1];
@@ -357,14 +309,12 @@ __global__ __launch_bounds__(256, 1) void dec_l1_kernel(DecL1Params p)
     const int nblk = (p.M + 31) >> 5;
     const int rb = min(m0 >> 5, nblk - 1);
 
-    const uint32_t voff0 = lane * 16 + wave * 1024;
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)dl_smem) + wave * 1024;
+    const uint32_t voff0 = tgp_dma_voff0(lane, wave), lds0 = tgp_dma_lds0(dl_smem, wave);
     const char *u_src = p.wa_pl + (int64_t)(single < 0 ? 0 : single) * DL_ABUF;
     auto dma = [&](const int buf, const int j0) {
         if (j0 * 4 + 3 >= DL_APIECES && wave >= (DL_APIECES & 3)) return;      // pieces 34, 35 do not exist
         const uint32_t lds = lds0 + buf * DL_ABUF + j0 * 4096;
-        const uint32_t vo = voff0 + j0 * 4096;
-        asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(vo), "s"(u_src), "{m0}"(lds) : "memory");
+        tgp_lds_dma(voff0 + j0 * 4096, u_src, lds);
     };
 #pragma unroll
     for (int j0 = 0; j0 < DL_NDMA; ++j0) dma(0, j0);
@@ -387,7 +337,7 @@ __global__ __launch_bounds__(256, 1) void dec_l1_kernel(DecL1Params p)
         // the input side of the fp16 range guard, as in the tile kernels: a block that cannot be split faithfully raises the chain's flag
         if (p.fine_amax && m0 < p.M) {
             const uint32_t am = p.fine_amax[rb];
-            if ((am >= 0x477fe000u || (am != 0u && am < 0x3d800000u)) && lane == 0) atomicOr(p.flag, 1);
+            if (TGP_FP16_OUT_OF_RANGE(am) && lane == 0) atomicOr(p.flag, 1);
         }
     }
     const int i1 = p.idx1[row], i2 = p.idx2[row];
@@ -396,7 +346,7 @@ __global__ __launch_bounds__(256, 1) void dec_l1_kernel(DecL1Params p)
     const float *rbp = p.rowbias ? p.rowbias + (int64_t)(row / p.rows_per_obj) * p.ldrb + 4 * h : nullptr;
     char *h1 = p.h1_pl + (int64_t)rb * p.h1_kt * 2048 + lane * 16;          // + ((2 cb + s2) * 2 + plane) * 1024
 
-    df32x16 acc[2];
+    f32x16 acc[2];
     DlG g[2];
     uint32_t a2[2][16];                    // a block's activations as packed fp16: [0..7] hi (K-tile 2 b: 0..3, 2 b + 1: 4..7), [8..15] lo
     float amax = 0.f;
@@ -417,13 +367,12 @@ __global__ __launch_bounds__(256, 1) void dec_l1_kernel(DecL1Params p)
     // (its vectors are read from LDS four slices earlier); in the tile kernel's order: + bias, + P1 row, + P2 row, + per-object bias,
     // BatchNorm fold, ReLU
     float4 e_b, e_sc, e_sh, e_bn, e_scn, e_shn, e_v;
-    float e_l4[4];
     auto epi_read = [&](const int cb, const int m) {
         const float *pv = s_vec + 32 * cb + 4 * h + 8 * m;
         e_bn = *reinterpret_cast<const float4 *>(pv), e_scn = *reinterpret_cast<const float4 *>(pv + DF_C1);
         e_shn = *reinterpret_cast<const float4 *>(pv + 2 * DF_C1);
     };
-    auto epi = [&](const df32x16 &ac, const DlG &d, uint32_t (&a)[16], const int cb, const int sl) {
+    auto epi = [&](const f32x16 &ac, const DlG &d, uint32_t (&a)[16], const int cb, const int sl) {
         const int m = sl >> 3, ph = sl & 7;
         if (ph == 0) {
             e_b = e_bn, e_sc = e_scn, e_sh = e_shn;
@@ -445,18 +394,15 @@ __global__ __launch_bounds__(256, 1) void dec_l1_kernel(DecL1Params p)
             e_v.x = fmaxf(e_v.x, -0.f), e_v.y = fmaxf(e_v.y, -0.f), e_v.z = fmaxf(e_v.z, -0.f), e_v.w = fmaxf(e_v.w, -0.f);   // ReLU as max(v, -0)
             amax = fmaxf(amax, fmaxf(fmaxf(e_v.x, e_v.y), fmaxf(e_v.z, e_v.w)));
         } else {
-            const df32x4 x = {e_v.x, e_v.y, e_v.z, e_v.w};
-            const uint2 hh = __builtin_bit_cast(uint2, __builtin_convertvector(x, df16x4));
-            e_l4[0] = df_mix_lo(hh.x, e_v.x), e_l4[1] = df_mix_hi(hh.x, e_v.y), e_l4[2] = df_mix_lo(hh.y, e_v.z), e_l4[3] = df_mix_hi(hh.y, e_v.w);
-            const df32x4 rest = {e_l4[0], e_l4[1], e_l4[2], e_l4[3]};
-            const uint2 ll = __builtin_bit_cast(uint2, __builtin_convertvector(rest, df16x4));
+            uint2 hh, ll;
+            tgp_split4(e_v, hh, ll);
             a[2 * m] = hh.x, a[2 * m + 1] = hh.y, a[8 + 2 * m] = ll.x, a[8 + 2 * m + 1] = ll.y;
         }
     };
 
     // the weights of block 0 and the vectors (LDS) are in when at most the 34 fragment loads issued after them (and what followed) fly:
     // block 0's conv1 starts on the fragments that have arrived (heads_fused_kernel's prologue)
-    __builtin_amdgcn_s_waitcnt(0x0070 | (34 & 15) | ((34 >> 4) << 14));      // vmcnt(34) lgkmcnt(0)
+    __builtin_amdgcn_s_waitcnt(tgp_waitcnt(34, 0));               // vmcnt(34) lgkmcnt(0)
     __builtin_amdgcn_s_barrier();
     // iteration cb (0 .. 17): conv1 of block cb (cb < 16) into acc[cb & 1]; in its gaps the weights of block cb + 1, the epilogue of
     // block cb - 1 (from acc[(cb - 1) & 1], g[(cb - 1) & 1] into a2[(cb - 1) & 1]), the gathers of block cb (into g[cb & 1]) and the
@@ -466,16 +412,16 @@ __global__ __launch_bounds__(256, 1) void dec_l1_kernel(DecL1Params p)
         const int cb = (CB);                                                                                                 \
         const char *arow = dl_smem + (P) * DL_ABUF + lane * 16;                                                              \
         u_src = p.wa_pl + (int64_t)(cb + 1 < DL_NCB ? cb + 1 : DL_NCB - 1) * DL_ABUF;                                        \
-        df32x16 &ax = acc[(P)];                                                                                              \
+        f32x16 &ax = acc[(P)];                                                                                               \
         if (MM) { _Pragma("unroll") for (int e = 0; e < 16; ++e) ax[e] = 0.f; }                                              \
         uint4 fh0 = *reinterpret_cast<const uint4 *>(arow), fl0 = *reinterpret_cast<const uint4 *>(arow + 1024);             \
         uint4 fh1 = *reinterpret_cast<const uint4 *>(arow + 2048), fl1 = *reinterpret_cast<const uint4 *>(arow + 3072);      \
         if (E1) epi_read(cb - 1, 0);                                                                                         \
-        DF_SB();                                                                                                             \
+        TGP_SB();                                                                                                            \
         _Pragma("unroll") for (int s = 0; s < DL_STEPS; ++s) {                                                               \
             uint4 fh2 = fh1, fl2 = fl1;                                                                                      \
-            if (MM) ax = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(df16x8, fl0), __builtin_bit_cast(df16x8, bh[s]), ax, 0, 0, 0); \
-            DF_SB();                                                                                                         \
+            if (MM) ax = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fl0), __builtin_bit_cast(f16x8, bh[s]), ax, 0, 0, 0); \
+            TGP_SB();                                                                                                        \
             if (s + 2 < DL_STEPS && (MM)) {                                                                                  \
                 fh2 = *reinterpret_cast<const uint4 *>(arow + (s + 2) * 2048);                                               \
                 fl2 = *reinterpret_cast<const uint4 *>(arow + (s + 2) * 2048 + 1024);                                        \
@@ -485,21 +431,21 @@ __global__ __launch_bounds__(256, 1) void dec_l1_kernel(DecL1Params p)
                 _Pragma("unroll") for (int t2 = 0; t2 < 2; ++t2)                                                             \
                     if (2 * (s - DL_NDMA) + t2 < 12) gather1(g[(P)], cb, 2 * (s - DL_NDMA) + t2);                            \
             }                                                                                                                \
-            DF_SB();                                                                                                         \
-            if (MM) ax = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(df16x8, fh0), __builtin_bit_cast(df16x8, bl[s]), ax, 0, 0, 0); \
-            DF_SB();                                                                                                         \
+            TGP_SB();                                                                                                        \
+            if (MM) ax = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fh0), __builtin_bit_cast(f16x8, bl[s]), ax, 0, 0, 0); \
+            TGP_SB();                                                                                                        \
             if ((E1) && 2 * s < 32) epi(acc[(P) ^ 1], g[(P) ^ 1], a2[(P) ^ 1], cb - 1, 2 * s);                               \
             if ((ST) && s >= 2 && s < 6) store1(a2[(P)], cb - 2, s - 2);                                                     \
-            DF_SB();                                                                                                         \
-            if (MM) ax = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(df16x8, fh0), __builtin_bit_cast(df16x8, bh[s]), ax, 0, 0, 0); \
-            DF_SB();                                                                                                         \
+            TGP_SB();                                                                                                        \
+            if (MM) ax = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fh0), __builtin_bit_cast(f16x8, bh[s]), ax, 0, 0, 0); \
+            TGP_SB();                                                                                                        \
             if ((E1) && 2 * s + 1 < 32) epi(acc[(P) ^ 1], g[(P) ^ 1], a2[(P) ^ 1], cb - 1, 2 * s + 1);                       \
-            DF_SB();                                                                                                         \
+            TGP_SB();                                                                                                        \
             fh0 = fh1, fl0 = fl1, fh1 = fh2, fl1 = fl2;                                                                      \
         }                                                                                                                    \
-        /* the next block's weights have landed; this block's twelve gathers -- issued after the last DMA piece, so the twelve  \
+        /* the next block's weights have landed; this block's twelve gathers -- issued after the last DMA piece, so the twelve \
            youngest operations in flight -- may still be on their way (their first use, in the next iteration, waits for them) */ \
-        if (MM) __builtin_amdgcn_s_waitcnt(0x0f70 | 12); else __builtin_amdgcn_s_waitcnt(0x0f70);                             \
+        if (MM) __builtin_amdgcn_s_waitcnt(tgp_waitcnt(12)); else __builtin_amdgcn_s_waitcnt(tgp_waitcnt(0));                \
         __syncthreads();                                                                                                     \
     }
     if (single >= 0) {                                            // one channel block of a tile behind the last full round
@@ -568,31 +514,6 @@ extern "C" int tgp_dec_l1(const tgp_dec_l1_args *a, tgp_stream_t stream)
     return TGP_LAUNCH_RESULT();
 }
 
-// ---- weights -> staging units.  W (N, K) fp32 row-major; a unit is 64 pieces of 1 KB: piece (q * 2 + plane), q = s * (N / 32) + j over the
-// unit's K-steps s and the N / 32 output blocks j, holds [lane = 32 h + r][8 fp16] = W[32 j + r][k(step, 8 h + t)], t = 0 .. 7, as its
-// fp16 hi (plane 0) / lo (plane 1) part.  permuted = 0: k = 16 step + slot (layer 2: the operand planes' natural order); 1: slot
-// 8 h + t of step 2 b + s2 is channel 32 b + 16 s2 + 8 (t >> 2) + 4 h + (t & 3) -- the order in which the previous layer's accumulators hold
-// a block's channels.
-__global__ void dec_pack_kernel(const float *__restrict__ W, int ld, int N, int K, int permuted, uint16_t *__restrict__ out)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t total = (int64_t)N * K;
-    if (t >= total) return;
-    const int nb = N / 32, spu = 32 / nb;                         // K-steps per unit
-    const int tt = (int)(t & 7), rr = (int)((t >> 3) & 31), hh = (int)((t >> 8) & 1);
-    const int q = (int)((t >> 9) & 31);
-    const int unit = (int)(t >> 14);
-    const int s = q / nb, j = q % nb;
-    const int step = unit * spu + s;
-    const int col = permuted ? 32 * (step >> 1) + 16 * (step & 1) + 8 * (tt >> 2) + 4 * hh + (tt & 3) : 16 * step + 8 * hh + tt;
-    const float v = W[(int64_t)(32 * j + rr) * ld + col];
-    const _Float16 hi = (_Float16)v;
-    const _Float16 lo = (_Float16)(v - (float)hi);
-    uint16_t *dst = out + (int64_t)unit * (DF_UNIT / 2) + (int64_t)(q * 2) * 512 + (hh * 32 + rr) * 8 + tt;
-    dst[0] = __builtin_bit_cast(uint16_t, hi);
-    dst[512] = __builtin_bit_cast(uint16_t, lo);
-}
-
 extern "C" int64_t tgp_dec_pack_bytes(void) { return (int64_t)DF_UNITS * DF_UNIT; }
 
 extern "C" int tgp_dec_pack(const float *w2, const float *w3, const float *w4, int h1_permuted, void *out, tgp_stream_t stream)
@@ -600,17 +521,16 @@ extern "C" int tgp_dec_pack(const float *w2, const float *w3, const float *w4, i
     TGP_REQUIRE(w2 && w3 && w4 && out && (reinterpret_cast<uintptr_t>(out) & 15) == 0);
     uint16_t *o = reinterpret_cast<uint16_t *>(out);
     const int64_t U = DF_UNIT / 2;
-    // staging order: layer 2 rows 0-255 | layer 3 columns 0-255 | layer 2 rows 256-511 | layer 3 columns 256-511 | layer 4
+    // staging order: layer 2 rows 0-255 | layer 3 columns 0-255 | layer 2 rows 256-511 | layer 3 columns 256-511 | layer 4; a unit holds
+    // all N / 32 output blocks of its 1024 / N K-steps.  Layer 2's K order is the operand planes' (natural, or dec_l1's accumulator order:
+    // h1_permuted); layers 3 / 4 read the previous layer's accumulators: permuted
     for (int half = 0; half < 2; ++half) {
         uint16_t *base = o + (int64_t)half * (DF_U2H + DF_U3H) * U;
-        hipLaunchKernelGGL(dec_pack_kernel, dim3(256 * DF_C1 / 256), dim3(256), 0, tgp_hs(stream), w2 + (int64_t)half * 256 * DF_C1, DF_C1, 256,
-                           DF_C1, h1_permuted ? 1 : 0, base);
-        hipLaunchKernelGGL(dec_pack_kernel, dim3(DF_C3 * 256 / 256), dim3(256), 0, tgp_hs(stream), w3 + half * 256, DF_C1, DF_C3, 256, 1,
-                           base + (int64_t)DF_U2H * U);
+        if (const int e = tgp_pack_units(w2 + (int64_t)half * 256 * DF_C1, DF_C1, 256, DF_C1, 8, DF_U2H, DF_C1 / 16, DF_U2H, h1_permuted ? 1 : 0,
+                                         base, tgp_hs(stream))) return e;
+        if (const int e = tgp_pack_units(w3 + half * 256, DF_C1, DF_C3, 256, 8, DF_U3H, 16, DF_U3H, 1, base + (int64_t)DF_U2H * U, tgp_hs(stream))) return e;
     }
-    hipLaunchKernelGGL(dec_pack_kernel, dim3(DF_C4 * DF_C3 / 256), dim3(256), 0, tgp_hs(stream), w4, DF_C3, DF_C4, DF_C3, 1,
-                       o + (int64_t)(2 * DF_U2H + 2 * DF_U3H) * U);
-    return TGP_LAUNCH_RESULT();
+    return tgp_pack_units(w4, DF_C3, DF_C4, DF_C3, 4, DF_U4, DF_C3 / 16, DF_U4, 1, o + (int64_t)(2 * DF_U2H + 2 * DF_U3H) * U, tgp_hs(stream));
 }
 
 extern "C" int tgp_dec_fused(const tgp_dec_fused_args *a, tgp_stream_t stream)

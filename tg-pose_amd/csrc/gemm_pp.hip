@@ -17,8 +17,9 @@
 // sequence of gemm_split_tile<..., F16> -- so results are bit-identical to that kernel whatever the tile shape
 // (tests/test_gpu_parity.py::test_gemm_pp_bit_identical_to_split_kernel).
 #include "gemm_epi.h"
+#include "mfma_unit.h"
 
-#define PP_WAIT_VM(N) __builtin_amdgcn_s_waitcnt(0x0f70 | ((N) & 15) | (((N) >> 4) << 14))
+#define PP_WAIT_VM(N) __builtin_amdgcn_s_waitcnt(tgp_waitcnt(N))
 
 #ifdef TGP_DEV   // development build: wall-clock stamps (100 MHz) per workgroup -- entry, first stage landed, K loop done, epilogue done
 __device__ unsigned long long *tgp_pp_stamps = nullptr;
@@ -84,7 +85,7 @@ __device__ __forceinline__ void gemm_pp_tile(const GemmParams &p, const int m0, 
             const uint32_t v = rb < nblk ? p.a_amax[rb] : 0u;
             am = v > am ? v : am;
         }
-        exact = am >= 0x477fe000u || (am != 0u && am < 0x3d800000u);       // >= 65504 | all below 2^-4 (and not all zero)
+        exact = TGP_FP16_OUT_OF_RANGE(am);
         if (exact && !p.A) {
             // a planes-only operand: nothing to recompute from.  The tile runs on the split (its result is wrong or imprecise) and
             // the flag tells the caller's predicated fp32 chain to redo the layer(s)
@@ -119,9 +120,7 @@ __device__ __forceinline__ void gemm_pp_tile(const GemmParams &p, const int m0, 
                 const int kt = min(s * KTS + ct[j], KT - 1);               // a K-tile past the end: any valid piece (its MFMAs are skipped)
                 const char *src = cbase[j] + (int64_t)kt * 2048;
                 const uint32_t lds = lds0 + stage * STAGE_BYTES + j * NW * 1024;
-                // inline assembly: opaque to the compiler's counters, so no vmcnt(0) appears before the fragment reads that
-                // follow; the waits are written by hand below (as in heads_fused.hip)
-                asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "{m0}"(lds) : "memory");
+                tgp_lds_dma(src, lds);                                     // (the waits are written by hand below)
             }
         };
 #pragma unroll

@@ -14,15 +14,8 @@
 //   after the 32 channel blocks: + bias2, BatchNorm fold, ReLU, max over the object's points as order-preserving keys (atomicMax).
 // One wave per SIMD (the points' fine features as B fragments: 136 registers, conv2's accumulators: 128), four waves per
 // workgroup sharing the LDS-staged weight blocks (double buffered: 2 x 67 KB).
-#include "tgp_common.h"
-#include "../../include/tgpose.h"
+#include "mfma_unit.h"
 #include <type_traits>
-
-typedef _Float16 hf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 hf16x4 __attribute__((ext_vector_type(4)));
-typedef float hf32x4 __attribute__((ext_vector_type(4)));
-typedef float hf32x2 __attribute__((ext_vector_type(2)));
-typedef float hf32x16 __attribute__((ext_vector_type(16)));
 
 #define HF_STEPS 17                 // K steps of conv1: 272 / 16
 #define HF_C1 1024                  // conv1 channels per head
@@ -47,10 +40,10 @@ struct HeadsParams {
 
 __device__ __forceinline__ void hf_split(const float4 v, uint2 &hi, uint2 &lo)
 {
-    const hf32x4 x = {v.x, v.y, v.z, v.w};
-    const hf16x4 h = __builtin_convertvector(x, hf16x4);
-    const hf32x4 rest = x - __builtin_convertvector(h, hf32x4);
-    const hf16x4 l = __builtin_convertvector(rest, hf16x4);
+    const f32x4 x = {v.x, v.y, v.z, v.w};
+    const f16x4 h = __builtin_convertvector(x, f16x4);
+    const f32x4 rest = x - __builtin_convertvector(h, f32x4);
+    const f16x4 l = __builtin_convertvector(rest, f16x4);
     hi = __builtin_bit_cast(uint2, h);
     lo = __builtin_bit_cast(uint2, l);
 }
@@ -85,7 +78,6 @@ __device__ __forceinline__ void hf_split(const float4 v, uint2 &hi, uint2 &lo)
 #define HP_BUF (HP_PIECES * 1024)
 #define HP_NDMA ((HP_PIECES + 3) / 4)      // 17 wave-instructions per wave and unit (piece j = 4 j0 + wave; piece 67 does not exist)
 #define HP_DMA_A 10                        // DMA pieces of a unit issued in stage A (one per K-step from step 0), the other 7 in stage B
-#define HP_SB() __builtin_amdgcn_sched_barrier(0)
 
 template <bool PLANES, bool STAMPS, int KNOB = 0>
 __global__ __launch_bounds__(256, 1) void heads_fused_kernel(HeadsParams p)
@@ -105,8 +97,7 @@ __global__ __launch_bounds__(256, 1) void heads_fused_kernel(HeadsParams p)
     // ---- staging of a unit u = { conv1 weights of block u + 1 | conv2 weights and epilogue vectors of block u } into buffer buf: piece
     // j = 4 j0 + wave is 1 KB at offset 1024 j of the buffer and of the unit's image in memory (pieces 0 .. 33 from the conv1
     // planes, 34 .. 66 from the conv2 image), so a piece is { LDS base + 4096 j0, scalar source base, vector offset + 4096 j0 }
-    const uint32_t voff0 = lane * 16 + wave * 1024;
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)hf_smem) + wave * 1024;
+    const uint32_t voff0 = tgp_dma_voff0(lane, wave), lds0 = tgp_dma_lds0(hf_smem, wave);
     const char *a_src, *w_src, *mid_src;                         // scalar bases of the unit being staged (set per iteration)
     auto dma_unit = [&](const int u) {
         const int ua = u + 1 < HF_NCB ? u + 1 : HF_NCB - 1;     // (the last unit has no next conv1 block: it re-reads the last one)
@@ -119,15 +110,11 @@ __global__ __launch_bounds__(256, 1) void heads_fused_kernel(HeadsParams p)
         const char *src = j0 * 4 + 3 < HP_APIECES ? a_src : j0 * 4 >= HP_APIECES ? w_src : mid_src;
         if (j0 == HP_NDMA - 1 && (HP_PIECES & 3) != 0) {         // the last round of pieces is short: wave 3 repeats its previous piece
             const uint32_t lds = lds0 + buf * HP_BUF + (wave < (HP_PIECES & 3) ? j0 : j0 - 1) * 4096;
-            const uint32_t vo = voff0 + (wave < (HP_PIECES & 3) ? j0 : j0 - 1) * 4096;
-            asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(vo), "s"(src), "{m0}"(lds) : "memory");
+            tgp_lds_dma(voff0 + (wave < (HP_PIECES & 3) ? j0 : j0 - 1) * 4096, src, lds);
             return;
         }
         const uint32_t lds = lds0 + buf * HP_BUF + j0 * 4096;
-        const uint32_t vo = voff0 + j0 * 4096;
-        // inline assembly: opaque to the compiler's counters (no vmcnt(0) before the LDS reads that follow); vmcnt(0) is written by
-        // hand before the barrier that ends an iteration.  The LDS base travels in m0 as a register-constrained input.
-        asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(vo), "s"(src), "{m0}"(lds) : "memory");
+        tgp_lds_dma(voff0 + j0 * 4096, src, lds);      // (vmcnt(0) is written by hand before the barrier that ends an iteration)
     };
 
     // the first unit (its conv1 half: weights of block 0), then the wave's points as B fragments: fp16 hi / lo planes of fine[row][16 s + 8 h .. + 7]
@@ -139,8 +126,7 @@ __global__ __launch_bounds__(256, 1) void heads_fused_kernel(HeadsParams p)
         for (int j0 = 0; j0 <= (HP_APIECES - 1) / 4; ++j0) {
             const uint32_t lds = lds0 + j0 * 4096;
             const uint32_t vo = voff0 + j0 * 4096;
-            if (j0 * 4 + 3 < HP_APIECES || wave < (HP_APIECES & 3))
-                asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(vo), "s"(a_src), "{m0}"(lds) : "memory");
+            if (j0 * 4 + 3 < HP_APIECES || wave < (HP_APIECES & 3)) tgp_lds_dma(vo, a_src, lds);
         }
         w_src = keep;
     }
@@ -185,7 +171,7 @@ __global__ __launch_bounds__(256, 1) void heads_fused_kernel(HeadsParams p)
     const float *g1p = p.p1 + (int64_t)i1 * p.ldp1 + hd * HF_C1 + 4 * h;           // + cb * 32 + 8 m: four channels of the lane
     const float *g2p = p.p2 + (int64_t)i2 * p.ldp2 + hd * HF_C1 + 4 * h;
 
-    hf32x16 acc2[HF_C2 / 32];
+    f32x16 acc2[HF_C2 / 32];
 #pragma unroll
     for (int ob = 0; ob < HF_C2 / 32; ++ob)
 #pragma unroll
@@ -233,17 +219,14 @@ __global__ __launch_bounds__(256, 1) void heads_fused_kernel(HeadsParams p)
             // the block that produced it (an infinity) or came from non-finite operands (the input guard): epilogue 2 flags both
             e_v.x = fmaxf(e_v.x, -0.f), e_v.y = fmaxf(e_v.y, -0.f), e_v.z = fmaxf(e_v.z, -0.f), e_v.w = fmaxf(e_v.w, -0.f);
         } else if (ph == 6) {
-            // hi = fp16(v); lo = fp16(v - hi), the difference by one mixed-precision fma per element (hi -> fp32 is exact, one rounding:
-            // the value hf_split's convert-and-subtract gives)
-            const hf32x4 x = {e_v.x, e_v.y, e_v.z, e_v.w};
-            hh[m] = __builtin_bit_cast(uint2, __builtin_convertvector(x, hf16x4));
-            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(e_lo[0]) : "v"(hh[m].x), "v"(e_v.x));
-            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(e_lo[1]) : "v"(hh[m].x), "v"(e_v.y));
+            // hi = fp16(v); lo = fp16(v - hi): tgp_split4's steps over two slices (the value hf_split's convert-and-subtract gives)
+            const f32x4 x = {e_v.x, e_v.y, e_v.z, e_v.w};
+            hh[m] = __builtin_bit_cast(uint2, __builtin_convertvector(x, f16x4));
+            e_lo[0] = tgp_mix_lo(hh[m].x, e_v.x), e_lo[1] = tgp_mix_hi(hh[m].x, e_v.y);
         } else {
-            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(e_lo[2]) : "v"(hh[m].y), "v"(e_v.z));
-            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(e_lo[3]) : "v"(hh[m].y), "v"(e_v.w));
-            const hf32x4 rest = {e_lo[0], e_lo[1], e_lo[2], e_lo[3]};
-            ll[m] = __builtin_bit_cast(uint2, __builtin_convertvector(rest, hf16x4));
+            e_lo[2] = tgp_mix_lo(hh[m].y, e_v.z), e_lo[3] = tgp_mix_hi(hh[m].y, e_v.w);
+            const f32x4 rest = {e_lo[0], e_lo[1], e_lo[2], e_lo[3]};
+            ll[m] = __builtin_bit_cast(uint2, __builtin_convertvector(rest, f16x4));
         }
     };
     auto epi1_pack = [&]() {
@@ -253,7 +236,7 @@ __global__ __launch_bounds__(256, 1) void heads_fused_kernel(HeadsParams p)
 
     // ---- stage A: conv1 of block i (32 channels x 32 points, 17 steps x 3 split terms).  Gap 3 s: the fragments of step s + 2 and
     // a DMA piece; gaps 3 s + 1, 3 s + 2: slices 2 s, 2 s + 1 of the previous block's epilogue 1
-    hf32x16 acc1;
+    f32x16 acc1;
     auto stage_a = [&](const char *base, const bool with_e1, const int wbuf, const bool all_dma) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc1[e] = 0.f;
@@ -262,13 +245,13 @@ __global__ __launch_bounds__(256, 1) void heads_fused_kernel(HeadsParams p)
         uint4 fh0 = *reinterpret_cast<const uint4 *>(arow), fl0 = *reinterpret_cast<const uint4 *>(arow + 1024);
         uint4 fh1 = *reinterpret_cast<const uint4 *>(arow + 2048), fl1 = *reinterpret_cast<const uint4 *>(arow + 3072);
         if (with_e1) epi1_read(base, 0);
-        HP_SB();
+        TGP_SB();
 #pragma unroll
         for (int s = 0; s < HF_STEPS; ++s) {
             uint4 fh2 = fh1, fl2 = fl1;
             // smallest terms first, as in the tile kernel: lo x hi, hi x lo, hi x hi
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hf16x8, fl0), __builtin_bit_cast(hf16x8, bh[s]), acc1, 0, 0, 0);
-            HP_SB();
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fl0), __builtin_bit_cast(f16x8, bh[s]), acc1, 0, 0, 0);
+            TGP_SB();
             if (s + 2 < HF_STEPS && !(KNOB & 4)) {
                 fh2 = *reinterpret_cast<const uint4 *>(arow + (s + 2) * 2048);
                 fl2 = *reinterpret_cast<const uint4 *>(arow + (s + 2) * 2048 + 1024);
@@ -276,15 +259,15 @@ __global__ __launch_bounds__(256, 1) void heads_fused_kernel(HeadsParams p)
             // the next unit's pieces target the other buffer, whose last readers passed the barrier
             if (all_dma) dma(wbuf, s);
             else if (s < HP_DMA_A) dma(wbuf, s);
-            HP_SB();
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hf16x8, fh0), __builtin_bit_cast(hf16x8, bl[s]), acc1, 0, 0, 0);
-            HP_SB();
+            TGP_SB();
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fh0), __builtin_bit_cast(f16x8, bl[s]), acc1, 0, 0, 0);
+            TGP_SB();
             if (with_e1) epi1(base, 2 * s);
-            HP_SB();
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hf16x8, fh0), __builtin_bit_cast(hf16x8, bh[s]), acc1, 0, 0, 0);
-            HP_SB();
+            TGP_SB();
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fh0), __builtin_bit_cast(f16x8, bh[s]), acc1, 0, 0, 0);
+            TGP_SB();
             if (with_e1) epi1(base, 2 * s + 1);
-            HP_SB();
+            TGP_SB();
             fh0 = fh1, fl0 = fl1, fh1 = fh2, fl1 = fl2;
         }
         if (with_e1) epi1_pack();
@@ -297,32 +280,32 @@ __global__ __launch_bounds__(256, 1) void heads_fused_kernel(HeadsParams p)
         constexpr int NQ = 2 * (HF_C2 / 32);
         auto wfrag = [&](int q, int plane) { return *reinterpret_cast<const uint4 *>(wrow + (q * 2 + plane) * 1024); };
         uint4 wh0 = wfrag(0, 0), wl0 = wfrag(0, 1), wh1 = wfrag(1, 0), wl1 = wfrag(1, 1);
-        HP_SB();
+        TGP_SB();
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             uint4 wh2 = wh1, wl2 = wl1;
             const int s2 = q / (HF_C2 / 32), ob = q % (HF_C2 / 32);
-            acc2[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hf16x8, a2h[s2]), __builtin_bit_cast(hf16x8, wl0), acc2[ob], 0, 0, 0);
-            HP_SB();
+            acc2[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a2h[s2]), __builtin_bit_cast(f16x8, wl0), acc2[ob], 0, 0, 0);
+            TGP_SB();
             if (q + 2 < NQ && !(KNOB & 4)) wh2 = wfrag(q + 2, 0), wl2 = wfrag(q + 2, 1);
-            HP_SB();
-            acc2[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hf16x8, a2l[s2]), __builtin_bit_cast(hf16x8, wh0), acc2[ob], 0, 0, 0);
-            HP_SB();
+            TGP_SB();
+            acc2[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a2l[s2]), __builtin_bit_cast(f16x8, wh0), acc2[ob], 0, 0, 0);
+            TGP_SB();
             if (stage && q + HP_DMA_A < HP_NDMA) dma(wbuf, q + HP_DMA_A);
-            HP_SB();
-            acc2[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hf16x8, a2h[s2]), __builtin_bit_cast(hf16x8, wh0), acc2[ob], 0, 0, 0);
-            HP_SB();
+            TGP_SB();
+            acc2[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a2h[s2]), __builtin_bit_cast(f16x8, wh0), acc2[ob], 0, 0, 0);
+            TGP_SB();
             if (gcb >= 0 && q < 8) gather1(gcb, q);
             if (copy_pre && q >= 8) pre[2 * (q - 8)] = acc1[2 * (q - 8)], pre[2 * (q - 8) + 1] = acc1[2 * (q - 8) + 1];
-            HP_SB();
+            TGP_SB();
             wh0 = wh1, wl0 = wl1, wh1 = wh2, wl1 = wl2;
         }
     };
 
     // this wave's DMA pieces have landed when at most the 34 fragment loads issued after them (and what followed) are in flight: block 0's
     // conv1 starts on the fragments that have arrived (the compiler's own waits cover each first use) instead of behind the last of them
-    if constexpr (PLANES) __builtin_amdgcn_s_waitcnt(0x0f70 | (34 & 15) | ((34 >> 4) << 14));
-    else __builtin_amdgcn_s_waitcnt(0x0f70);
+    if constexpr (PLANES) __builtin_amdgcn_s_waitcnt(tgp_waitcnt(34));
+    else __builtin_amdgcn_s_waitcnt(tgp_waitcnt(0));
     __builtin_amdgcn_s_barrier();
     const unsigned long long t_pro = HP_T();
 
@@ -333,7 +316,7 @@ __global__ __launch_bounds__(256, 1) void heads_fused_kernel(HeadsParams p)
     stage_a(hf_smem, false, 1, true);
 #pragma unroll
     for (int e = 0; e < 16; ++e) pre[e] = acc1[e];
-    __builtin_amdgcn_s_waitcnt(0x0f70);
+    __builtin_amdgcn_s_waitcnt(tgp_waitcnt(0));
     __syncthreads();
     // iterations 1 .. 31: buffer i & 1 holds { conv1 weights of block i | conv2 weights and vectors of block i - 1 }
 #pragma unroll 1
@@ -342,13 +325,13 @@ __global__ __launch_bounds__(256, 1) void heads_fused_kernel(HeadsParams p)
         const unsigned long long t0 = HP_T();
         dma_unit(i);
         stage_a(base, true, (i & 1) ^ 1, false);
-        if (STAMPS) HP_SB();
+        if (STAMPS) TGP_SB();
         const unsigned long long t1 = HP_T();
-        if (STAMPS) HP_SB();
+        if (STAMPS) TGP_SB();
         stage_b(base, i, true, true, (i & 1) ^ 1);
-        if (STAMPS) HP_SB();
+        if (STAMPS) TGP_SB();
         const unsigned long long t2 = HP_T();
-        __builtin_amdgcn_s_waitcnt(0x0f70);                      // vmcnt(0): this wave's share of the next unit has landed (and its gathers)
+        __builtin_amdgcn_s_waitcnt(tgp_waitcnt(0));              // vmcnt(0): this wave's share of the next unit has landed (and its gathers)
         __syncthreads();                                         // ... everybody's has, and this buffer's readers are done
         const unsigned long long t3 = HP_T();
         t_a += t1 - t0, t_b += t2 - t1, t_bar += t3 - t2;
@@ -483,8 +466,6 @@ struct ConvMaxParams {
     const char *fine_pl; int fine_kt; const uint32_t *fine_amax;      // (round 4) the points' features as blocked fp16 planes
 };
 
-__device__ __forceinline__ constexpr int cm_vmcnt(int n) { return 0x0f70 | (n & 15) | ((n >> 4) << 14); }
-
 template <bool PLANES, int KNOB = 0>
 __global__ __launch_bounds__(256, 2) void conv_max_fused_kernel(ConvMaxParams p)
 {
@@ -509,16 +490,13 @@ __global__ __launch_bounds__(256, 2) void conv_max_fused_kernel(ConvMaxParams p)
     const int row = min(m0 + r, p.M - 1);
 
     // the first block's weights travel while the points' fragments are fetched
-    const uint32_t voff0 = lane * 16 + wave * 1024;
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)hf_smem) + wave * 1024;
+    const uint32_t voff0 = tgp_dma_voff0(lane, wave), lds0 = tgp_dma_lds0(hf_smem, wave);
     auto dma = [&](const int cb, const int buf, const int j0) {
         if ((KNOB & 1) && cb != cb0) return;
         const char *src = p.wa_pl + (int64_t)cb * CM_BUF;
         const int jj = (j0 == CM_NDMA - 1 && wave >= (CM_PIECES & 3)) ? j0 - 1 : j0;    // pieces 34, 35 do not exist
         const uint32_t lds = lds0 + buf * CM_BUF + jj * 4096;
-        const uint32_t vo = voff0 + jj * 4096;
-        // inline assembly: opaque to the compiler's counters; the waits are written by hand before the barrier that ends an iteration
-        asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(vo), "s"(src), "{m0}"(lds) : "memory");
+        tgp_lds_dma(voff0 + jj * 4096, src, lds);      // (the waits are written by hand before the barrier that ends an iteration)
     };
 #pragma unroll
     for (int j0 = 0; j0 < CM_NDMA; ++j0) dma(cb0, 0, j0);
@@ -596,7 +574,7 @@ __global__ __launch_bounds__(256, 2) void conv_max_fused_kernel(ConvMaxParams p)
     // taken on the floats -- LeakyReLU with a slope in [0, 1] is max(v, slope v), to the bit -- and keyed once per block; a NaN or an
     // infinity among the values makes the key a NaN's (chk), as the per-element keys did.  Slots 32, 33: the other half's maxima, the
     // atomics.
-    auto epi = [&](auto plain, const hf32x16 &acc, const int cb, const int t, const bool next_) {
+    auto epi = [&](auto plain, const f32x16 &acc, const int cb, const int t, const bool next_) {
         const bool next = next_ && !(KNOB & 16);
         if (t < 32) {
             const int e = t >> 1, off = (e & 3) + 8 * (e >> 2);
@@ -633,46 +611,46 @@ __global__ __launch_bounds__(256, 2) void conv_max_fused_kernel(ConvMaxParams p)
     };
     // iteration: block cb's 51 MFMAs into accN; in their gaps the next step's fragments, the DMA of block cb + 1 (with_dma), block
     // cb - 1's epilogue from accP (with_epi) and block cb's vectors
-    auto iter = [&](auto plain, hf32x16 &accN, const hf32x16 &accP, const int cb, const int buf, const bool with_epi, const bool with_dma) {
+    auto iter = [&](auto plain, f32x16 &accN, const f32x16 &accP, const int cb, const int buf, const bool with_epi, const bool with_dma) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) accN[e] = 0.f;
         const char *wrow = hf_smem + buf * CM_BUF + lane * 16;
         // (fragments one step ahead: the SIMD's other wave covers the LDS latency, and the registers are needed)
         uint4 fh0 = *reinterpret_cast<const uint4 *>(wrow), fl0 = *reinterpret_cast<const uint4 *>(wrow + 1024);
-        HP_SB();
+        TGP_SB();
 #pragma unroll
         for (int s = 0; s < HF_STEPS; ++s) {
             uint4 fh1 = fh0, fl1 = fl0;
-            accN = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hf16x8, ah[s]), __builtin_bit_cast(hf16x8, fl0), accN, 0, 0, 0);
-            HP_SB();
+            accN = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah[s]), __builtin_bit_cast(f16x8, fl0), accN, 0, 0, 0);
+            TGP_SB();
             if (s + 1 < HF_STEPS && !(KNOB & 4)) {
                 fh1 = *reinterpret_cast<const uint4 *>(wrow + (s + 1) * 2048);
                 fl1 = *reinterpret_cast<const uint4 *>(wrow + (s + 1) * 2048 + 1024);
             }
             if (with_dma && s < CM_NDMA) dma(cb + 1, buf ^ 1, s);
-            HP_SB();
-            accN = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hf16x8, al[s]), __builtin_bit_cast(hf16x8, fh0), accN, 0, 0, 0);
-            HP_SB();
+            TGP_SB();
+            accN = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, al[s]), __builtin_bit_cast(f16x8, fh0), accN, 0, 0, 0);
+            TGP_SB();
             if (with_epi && !(KNOB & 8)) epi(plain, accP, cb - 1, 2 * s, true);
-            HP_SB();
-            accN = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hf16x8, ah[s]), __builtin_bit_cast(hf16x8, fh0), accN, 0, 0, 0);
-            HP_SB();
+            TGP_SB();
+            accN = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah[s]), __builtin_bit_cast(f16x8, fh0), accN, 0, 0, 0);
+            TGP_SB();
             if (with_epi && !(KNOB & 8)) epi(plain, accP, cb - 1, 2 * s + 1, true);
             if (s == HF_STEPS - 1) bN = p.bias[cb * 32 + r], scN = p.scale[cb * 32 + r], shN = p.shift[cb * 32 + r];
-            HP_SB();
+            TGP_SB();
             fh0 = fh1, fl0 = fl1;
         }
         bP = bN, scP = scN, shP = shN;
         if (with_dma) {
             // this wave's DMA pieces have landed when at most the sixteen gathers issued after the last piece (and whatever followed
             // them) are outstanding; without an epilogue nothing was issued behind them
-            if (with_epi && !(KNOB & 10)) __builtin_amdgcn_s_waitcnt(cm_vmcnt(16));
-            else __builtin_amdgcn_s_waitcnt(cm_vmcnt(0));
+            if (with_epi && !(KNOB & 10)) __builtin_amdgcn_s_waitcnt(tgp_waitcnt(16));
+            else __builtin_amdgcn_s_waitcnt(tgp_waitcnt(0));
             __builtin_amdgcn_s_barrier();
         }
     };
     auto run = [&](auto plain) {
-        hf32x16 acc0, acc1;
+        f32x16 acc0, acc1;
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc1[e] = 0.f;
         iter(plain, acc0, acc1, cb0, 0, false, cb0 + 1 < cb1);
@@ -693,7 +671,7 @@ __global__ __launch_bounds__(256, 2) void conv_max_fused_kernel(ConvMaxParams p)
 
 #pragma unroll
     for (int e = 0; e < 16; ++e) g1[e] = at(p.p1 + cb0 * 32, o1[e] + r4), g2[e] = at(p.p2 + cb0 * 32, o2[e] + r4);
-    __builtin_amdgcn_s_waitcnt(cm_vmcnt(0));
+    __builtin_amdgcn_s_waitcnt(tgp_waitcnt(0));
     __syncthreads();
     if (plain_wave) run(std::true_type{});
     else run(std::false_type{});
@@ -823,7 +801,7 @@ extern "C" int tgp_heads_fused(const tgp_heads_fused_args *a, tgp_stream_t strea
     static TgpLdsAttr attr;
 #define HF_LAUNCH(...)                                                                                       \
     do {                                                                                                     \
-        const int e_ = tgp_lds_attr(attr, reinterpret_cast<const void *>(heads_fused_kernel<__VA_ARGS__>), 2 * HP_BUF);   \
+        const int e_ = tgp_lds_attr(attr, reinterpret_cast<const void *>(heads_fused_kernel<__VA_ARGS__>), 2 * HP_BUF); \
         if (e_) return e_;                                                                                   \
         hipLaunchKernelGGL((heads_fused_kernel<__VA_ARGS__>), grid, dim3(256), 2 * HP_BUF, tgp_hs(stream), p); \
         return TGP_LAUNCH_RESULT();                                                                          \

@@ -24,21 +24,12 @@
 // or is wholly below 2^-4, raises the device flag; the caller's two tile-kernel launches follow predicated on it (tgp_gemm_args.pred)
 // and rewrite both results with their own per-tile guards.  The rule is the tile kernels' applied per 32-row block (a superset of their
 // per-tile rule), so whenever the flag stays 0 both paths compute the same bits.
-#include "tgp_common.h"
-#include "../../include/tgpose.h"
+#include "mfma_unit.h"
 #include <type_traits>
-#include <cstdlib>
-
-typedef _Float16 hc16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 hc16x4 __attribute__((ext_vector_type(4)));
-typedef float hc32x4 __attribute__((ext_vector_type(4)));
-typedef float hc32x16 __attribute__((ext_vector_type(16)));
 
 #define HC_UNIT (64 * 1024)                // one staging unit in memory: 32 (K-step, output block) pairs x 2 planes of 1 KB
 #define HC_BUF (72 * 1024)                 // an LDS buffer: room for 36 pairs (layer 1 of the 132 -> 128 shape is ONE unit of 9 K-steps x 4 blocks)
-#define HC_SB() __builtin_amdgcn_sched_barrier(0)
 #define HR_SLOT (32 * 1024)                // hs_proj_kernel: one slot of its ring of four half units
-__device__ __forceinline__ constexpr int hc_vmcnt(int n) { return 0x0f70 | (n & 15) | ((n >> 4) << 14); }
 
 struct HcParams {
     const char *a_pl; int a_kt; const uint32_t *a_amax;          // layer 1's operand (M rows) as blocked fp16 planes + its magnitude words
@@ -59,74 +50,29 @@ struct HcParams {
     const float *a_f32; int lda; const float *w_f32; int ldw; int K2, ngt;
 };
 
-__device__ __forceinline__ float hc_mix_lo(uint32_t hpair, float v)     // v - (float)(low half of hpair), one rounding
-{
-    float d;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hpair), "v"(v));
-    return d;
-}
-__device__ __forceinline__ float hc_mix_hi(uint32_t hpair, float v)     // v - (float)(high half of hpair)
-{
-    float d;
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hpair), "v"(v));
-    return d;
-}
+// ---- a unit of hs_chain_kernel in buffer BUF as TGP_UNIT_BODY (expects: hc_smem, lane, dma(buf, j0), u_src): NQ pairs; NDN DMA rounds
+// of the next unit go out in its gaps (a short unit has fewer gaps than the next unit has rounds: the rest behind it)
+#define HC_BODY(BUF, NQ, ACC, NB, BH, BL, NDN, WAITCNT, FILL_A, FILL_B, FILL_C)                                              \
+    TGP_UNIT_BODY(hc_smem + (BUF) * HC_BUF + lane * 16, NQ, NB, ACC, BH, BL, if (q < (NDN)) dma((BUF) ^ 1, q), FILL_A, FILL_B, TGP_UNIT_GAP(FILL_C), \
+                  _Pragma("unroll") for (int q = (NQ); q < 16; ++q) if (q < (NDN)) dma((BUF) ^ 1, q);                        \
+                  TGP_UNIT_END(WAITCNT))
 
-// ---- the staging-unit body shared by the kernels of this file (expects: hc_smem, lane, dma(buf, j0), u_src)
-// One staging unit = up to 32 (K-step s, output block j) pairs, q = s * NB + j, three MFMAs each (smallest terms first, as in the
-// tile kernel: W lo x A hi, W hi x A lo, W hi x A hi); gap 1: the weight fragments of pair q + 2 (+ FILL_A), gap 2: a DMA piece of
-// the next unit (NDN of them; + FILL_B), gap 3: FILL_C.  BH / BL: the points' hi / lo fragments of K-step s.
-#define HC_BODY(BUF, NQ, ACC, NB, BH, BL, NDN, WAITCNT, FILL_A, FILL_B, FILL_C)                                                       \
+#define HC_GROUP(GI, ACC, PREV, GU0)                                                                                         \
     {                                                                                                                        \
-        const char *wrow = hc_smem + (BUF) * HC_BUF + lane * 16;                                                             \
-        auto wfrag = [&](int q, int plane) { return *reinterpret_cast<const uint4 *>(wrow + (q * 2 + plane) * 1024); };      \
-        uint4 wh0 = wfrag(0, 0), wl0 = wfrag(0, 1), wh1 = wfrag((NQ) > 1 ? 1 : 0, 0), wl1 = wfrag((NQ) > 1 ? 1 : 0, 1);      \
-        HC_SB();                                                                                                             \
-        _Pragma("unroll") for (int q = 0; q < (NQ); ++q) {                                                                   \
-            const int s = q / (NB), j = q % (NB);                                                                            \
-            uint4 wh2 = wh1, wl2 = wl1;                                                                                      \
-            const hc16x8 bh = BH, bl = BL;                                                                                   \
-            ACC[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hc16x8, wl0), bh, ACC[j], 0, 0, 0);           \
-            HC_SB();                                                                                                         \
-            if (q + 2 < (NQ)) wh2 = wfrag(q + 2, 0), wl2 = wfrag(q + 2, 1);                                                  \
-            FILL_A;                                                                                                          \
-            HC_SB();                                                                                                         \
-            ACC[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hc16x8, wh0), bl, ACC[j], 0, 0, 0);           \
-            HC_SB();                                                                                                         \
-            if (q < (NDN)) dma((BUF) ^ 1, q);                                                                                \
-            FILL_B;                                                                                                          \
-            HC_SB();                                                                                                         \
-            ACC[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hc16x8, wh0), bh, ACC[j], 0, 0, 0);           \
-            HC_SB();                                                                                                         \
-            FILL_C;                                                                                                          \
-            HC_SB();                                                                                                         \
-            wh0 = wh1, wl0 = wl1, wh1 = wh2, wl1 = wl2;                                                                      \
-        }                                                                                                                    \
-        _Pragma("unroll") for (int q = (NQ); q < 16; ++q)       /* (a short unit has fewer gaps than the next unit has pieces) */ \
-            if (q < (NDN)) dma((BUF) ^ 1, q);                                                                                \
-        __builtin_amdgcn_s_waitcnt(WAITCNT);    /* this wave's share of the next unit has landed (what was issued after it may fly) */ \
-        __syncthreads();                        /* ... everybody's has, and this buffer's readers are done */                \
-    }
-
-#define HC_ZERO(ACC)                                                  \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j)                     \
-        _Pragma("unroll") for (int e = 0; e < 16; ++e) ACC[j][e] = 0.f;
-#define HC_GROUP(GI, ACC, PREV, GU0)                                                                                              \
-    {                                                                                                                        \
-        HC_ZERO(ACC)                                                                                                         \
+        TGP_ZERO4(ACC)                                                                                                       \
         const bool have_prev = (GI) > 0;                                                                                     \
         _Pragma("unroll") for (int w = 0; w < U2; ++w) {                                                                     \
-            const int gu = (GU0) + (GI) * U2 + w;                          /* the unit's place in this workgroup's stream */    \
+            const int gu = (GU0) + (GI) * U2 + w;                          /* the unit's place in this workgroup's stream */ \
             const int ndn = ((GI) + 1 < ng || w + 1 < U2) ? 16 : 0;                                                          \
             u_src = u2_base + (int64_t)((GI) * U2 + w + 1) * HC_UNIT;                                                        \
-            /* the previous group's 16 stores go out in the unit's second half, behind its DMA pieces: the wait at the unit's end */  \
-            /* leaves exactly them in flight (vmcnt(16)) instead of draining the store path once per unit */                         \
+            /* the previous group's 16 stores go out in the unit's second half, behind its DMA pieces: the wait at the unit's end */ \
+            /* leaves exactly them in flight (vmcnt(16)) instead of draining the store path once per unit */                 \
             if (have_prev && w == 0 && m0 < p.M) {      /* (a wave past the last row issues no stores: it takes the plain wait) */ \
-                HC_BODY(gu & 1, 32, ACC, 4, __builtin_bit_cast(hc16x8, a2h[8 * w + s]), __builtin_bit_cast(hc16x8, a2l[8 * w + s]), \
-                        ndn, 0x4f70, if (q >= 16) store2(PREV, g0 + (GI) - 1, q - 16), , )                                   \
+                HC_BODY(gu & 1, 32, ACC, 4, __builtin_bit_cast(f16x8, a2h[8 * w + s]), __builtin_bit_cast(f16x8, a2l[8 * w + s]), \
+                        ndn, tgp_waitcnt(16), if (q >= 16) store2(PREV, g0 + (GI) - 1, q - 16), , )                          \
             } else {                                                                                                         \
-                HC_BODY(gu & 1, 32, ACC, 4, __builtin_bit_cast(hc16x8, a2h[8 * w + s]), __builtin_bit_cast(hc16x8, a2l[8 * w + s]), \
-                        ndn, 0x0f70, , , )                                                                                   \
+                HC_BODY(gu & 1, 32, ACC, 4, __builtin_bit_cast(f16x8, a2h[8 * w + s]), __builtin_bit_cast(f16x8, a2l[8 * w + s]), \
+                        ndn, tgp_waitcnt(0), , , )                                                                           \
             }                                                                                                                \
         }                                                                                                                    \
     }
@@ -134,10 +80,10 @@ __device__ __forceinline__ float hc_mix_hi(uint32_t hpair, float v)     // v - (
 // in buffer GU0_ & 1; BIASP_: the groups' bias in LDS)
 #define HC_LAYER2(GU0_, BIASP_) \
     /* ================================================================= layer 2: per group of four output blocks U2 units of eight K-steps */ \
-    hc32x16 accA[4], accB[4]; \
+    f32x16 accA[4], accB[4]; \
     float *c2p = p.c2 + (int64_t)rowc * p.ldc2 + 4 * h; \
     /* a finished group leaves in the gaps of the next one: block jj, quad g of group `grp` from `acc`, + bias */ \
-    auto store2 = [&](const hc32x16 (&acc)[4], const int grp, const int idx) {      /* idx = 0 .. 15: (block, quad) */ \
+    auto store2 = [&](const f32x16 (&acc)[4], const int grp, const int idx) {      /* idx = 0 .. 15: (block, quad) */ \
         const int jj = idx >> 2, g = idx & 3; \
         const int c = 128 * grp + 32 * jj + 8 * g; \
         const float4 b = *reinterpret_cast<const float4 *>((BIASP_) + (c - 128 * g0) + 4 * h); \
@@ -190,14 +136,11 @@ __global__ __launch_bounds__(256, 1) void hs_chain_kernel(HcParams p)
     const int rowc = min(row, p.M - 1);
 
     // ---- staging: unit u is 64 KB at units + 64 KB u; piece j = 4 j0 + wave is 1 KB at offset 1024 j of the unit and of the buffer
-    const uint32_t voff0 = lane * 16 + wave * 1024;
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)hc_smem) + wave * 1024;
+    const uint32_t voff0 = tgp_dma_voff0(lane, wave), lds0 = tgp_dma_lds0(hc_smem, wave);
     const char *u_src = p.units;                                  // scalar base of the unit being staged
     auto dma = [&](const int buf, const int j0) {
         const uint32_t lds = lds0 + buf * HC_BUF + j0 * 4096;
-        const uint32_t vo = voff0 + j0 * 4096;
-        // inline assembly: opaque to the compiler's counters; vmcnt(0) is written by hand before the barrier that ends a unit
-        asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(vo), "s"(u_src), "{m0}"(lds) : "memory");
+        tgp_lds_dma(voff0 + j0 * 4096, u_src, lds);
     };
     constexpr int ND_FIRST = (QCAP * 2 + 3) / 4;
 #pragma unroll
@@ -211,7 +154,7 @@ __global__ __launch_bounds__(256, 1) void hs_chain_kernel(HcParams p)
     // fp16 range guard of the operand, from what its producer recorded (bits of max |a| per 32-row block)
     if (m0 < p.M && p.a_amax) {
         const uint32_t am = p.a_amax[rb];
-        if ((am >= 0x477fe000u || (am != 0u && am < 0x3d800000u)) && lane == 0) atomicOr(p.flag, 1);
+        if (TGP_FP16_OUT_OF_RANGE(am) && lane == 0) atomicOr(p.flag, 1);
     }
     // the wave's points as B fragments of layer 1: K-tile kt, plane q at a_pl + ((rb * a_kt + kt) * 2 + q) * 1024 + 16 lane
     uint4 a1h[K1T], a1l[K1T];
@@ -244,13 +187,13 @@ __global__ __launch_bounds__(256, 1) void hs_chain_kernel(HcParams p)
     };
 #pragma unroll
     for (int j = 0; j < HC_RING - 1 && j < NB1; ++j) fetch(j, ring[j]);
-    hc32x16 acc1[NB1];
+    f32x16 acc1[NB1];
 #pragma unroll
     for (int j = 0; j < NB1; ++j)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc1[j][e] = 0.f;
 
-    __builtin_amdgcn_s_waitcnt(0x0f70);                           // vmcnt(0): this wave's DMA (and fragments) have landed
+    __builtin_amdgcn_s_waitcnt(tgp_waitcnt(0));                   // vmcnt(0): this wave's DMA (and fragments) have landed
     __syncthreads();
 
     // ================================================================= layer 1: U1 units of SPU1 K-steps x NB1 output blocks (the last may be short)
@@ -260,8 +203,8 @@ __global__ __launch_bounds__(256, 1) void hs_chain_kernel(HcParams p)
         constexpr int nq = QCAP;
         constexpr int nq_next = u + 1 < U1 ? QCAP : 32;          // (then layer 2's first unit)
         u_src = u + 1 < U1 ? p.units + (int64_t)(u + 1) * QCAP * 2048 : u2_base;
-        HC_BODY(u & 1, nq, acc1, NB1, __builtin_bit_cast(hc16x8, a1h[u * SPU1 + s]), __builtin_bit_cast(hc16x8, a1l[u * SPU1 + s]),
-                (nq_next * 2 + 3) / 4, 0x0f70, , , )
+        HC_BODY(u & 1, nq, acc1, NB1, __builtin_bit_cast(f16x8, a1h[u * SPU1 + s]), __builtin_bit_cast(f16x8, a1l[u * SPU1 + s]),
+                (nq_next * 2 + 3) / 4, tgp_waitcnt(0), , , )
     };
     unit1(std::integral_constant<int, 0>{});
     if constexpr (U1 > 1) unit1(std::integral_constant<int, 1>{});
@@ -280,7 +223,7 @@ __global__ __launch_bounds__(256, 1) void hs_chain_kernel(HcParams p)
 #pragma unroll
         for (int j = 0; j < NB1; ++j) {
             if (j + HC_RING - 1 < NB1) fetch(j + HC_RING - 1, ring[(j + HC_RING - 1) % HC_RING]);
-            HC_SB();
+            TGP_SB();
             const float4 (&lrb)[4] = ring[j % HC_RING][0], (&lr1)[4] = ring[j % HC_RING][1], (&lr2)[4] = ring[j % HC_RING][2];
             float4 v[4];
 #pragma unroll
@@ -303,7 +246,7 @@ __global__ __launch_bounds__(256, 1) void hs_chain_kernel(HcParams p)
                 const uint32_t m01 = b0 > b1 ? b0 : b1, m23 = b2 > b3 ? b2 : b3, m = m01 > m23 ? m01 : m23;
                 if (live) amid = m > amid ? m : amid;
             }
-            HC_SB();
+            TGP_SB();
 #pragma unroll
             for (int g = 0; g < 4; ++g)
                 if (st1) *reinterpret_cast<float4 *>(c1p + 32 * j + 8 * g) = v[g];
@@ -319,13 +262,14 @@ __global__ __launch_bounds__(256, 1) void hs_chain_kernel(HcParams p)
                     };
                     sw(x.x, y.x), sw(x.y, y.y), sw(x.z, y.z), sw(x.w, y.w);
                 }
-                const hc32x4 fx = {x.x, x.y, x.z, x.w}, fy = {y.x, y.y, y.z, y.w};
-                const uint2 hx = __builtin_bit_cast(uint2, __builtin_convertvector(fx, hc16x4));
-                const uint2 hy = __builtin_bit_cast(uint2, __builtin_convertvector(fy, hc16x4));
-                const hc32x4 lx = {hc_mix_lo(hx.x, x.x), hc_mix_hi(hx.x, x.y), hc_mix_lo(hx.y, x.z), hc_mix_hi(hx.y, x.w)};
-                const hc32x4 ly = {hc_mix_lo(hy.x, y.x), hc_mix_hi(hy.x, y.y), hc_mix_lo(hy.y, y.z), hc_mix_hi(hy.y, y.w)};
-                const uint2 qx = __builtin_bit_cast(uint2, __builtin_convertvector(lx, hc16x4));
-                const uint2 qy = __builtin_bit_cast(uint2, __builtin_convertvector(ly, hc16x4));
+                // (tgp_split4's steps for x and y interleaved: both conversions, the eight differences, both conversions)
+                const f32x4 fx = {x.x, x.y, x.z, x.w}, fy = {y.x, y.y, y.z, y.w};
+                const uint2 hx = __builtin_bit_cast(uint2, __builtin_convertvector(fx, f16x4));
+                const uint2 hy = __builtin_bit_cast(uint2, __builtin_convertvector(fy, f16x4));
+                const f32x4 lx = {tgp_mix_lo(hx.x, x.x), tgp_mix_hi(hx.x, x.y), tgp_mix_lo(hx.y, x.z), tgp_mix_hi(hx.y, x.w)};
+                const f32x4 ly = {tgp_mix_lo(hy.x, y.x), tgp_mix_hi(hy.x, y.y), tgp_mix_lo(hy.y, y.z), tgp_mix_hi(hy.y, y.w)};
+                const uint2 qx = __builtin_bit_cast(uint2, __builtin_convertvector(lx, f16x4));
+                const uint2 qy = __builtin_bit_cast(uint2, __builtin_convertvector(ly, f16x4));
                 a2h[2 * j + s2] = make_uint4(hx.x, hx.y, hy.x, hy.y);
                 a2l[2 * j + s2] = make_uint4(qx.x, qx.y, qy.x, qy.y);
                 if (st1 && plp) {                                // (rows past M stay unwritten, as the tile kernel leaves them)
@@ -345,7 +289,7 @@ __global__ __launch_bounds__(256, 1) void hs_chain_kernel(HcParams p)
         }
         if (lane == 0 && m0 < p.M) {
             if (writer && p.c1_amax && m) atomicMax(p.c1_amax + rb, m);
-            if (m >= 0x477fe000u || (m != 0u && m < 0x3d800000u)) atomicOr(p.flag, 1);
+            if (TGP_FP16_OUT_OF_RANGE(m)) atomicOr(p.flag, 1);
         }
     }
 
@@ -394,7 +338,7 @@ __global__ __launch_bounds__(256, 1) void hs_proj_kernel(HcParams p)
             const uint32_t v = b < nblk ? p.a_amax[b] : 0u;
             am = v > am ? v : am;
         }
-        exact = am >= 0x477fe000u || (am != 0u && am < 0x3d800000u);
+        exact = TGP_FP16_OUT_OF_RANGE(am);
     }
     if (exact) {                                                  // (workgroup-uniform; nothing staged yet)
         for (int n = 128 * g0 + lane; n < 128 * (g0 + ng); n += 64) {
@@ -413,15 +357,13 @@ __global__ __launch_bounds__(256, 1) void hs_proj_kernel(HcParams p)
     // ring of four LDS slots: half unit k + 3 is requested while k is multiplied, so a piece has two half units (~3000 cycles) to
     // arrive.  With two 64 KB buffers the next unit was requested one unit ahead and waited for at the end of the current one: on the
     // K = 512 products that wait was a third of the kernel (138 us where the MFMAs are 81).
-    const uint32_t voff0 = lane * 16 + wave * 1024;
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)hc_smem) + wave * 1024;
+    const uint32_t voff0 = tgp_dma_voff0(lane, wave), lds0 = tgp_dma_lds0(hc_smem, wave);
     const char *u2_base = p.units + (int64_t)g0 * U2 * HC_UNIT;
     const char *u_src = u2_base;
     const int nhu = ng * U2 * 2;                                  // half units of this workgroup
     auto dmah = [&](const int slot, const int j0) {               // piece j = 4 j0 + wave of the half unit at u_src
         const uint32_t lds = lds0 + slot * HR_SLOT + j0 * 4096;
-        const uint32_t vo = voff0 + j0 * 4096;
-        asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(vo), "s"(u_src), "{m0}"(lds) : "memory");
+        tgp_lds_dma(voff0 + j0 * 4096, u_src, lds);
     };
     // the wave's operand fragments and the bias first, then the first three half units: the matrix work starts when the fragments and
     // half unit 0 are in (the rounds of half units 1 and 2 -- the 16 youngest requests -- still fly)
@@ -435,7 +377,7 @@ __global__ __launch_bounds__(256, 1) void hs_proj_kernel(HcParams p)
         }
     }
     for (int i = tid; i < 128 * ng; i += 256) s_vec[i] = p.bias2 ? p.bias2[128 * g0 + i] : 0.f;
-    HC_SB();
+    TGP_SB();
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         if (k < nhu) {
@@ -444,20 +386,20 @@ __global__ __launch_bounds__(256, 1) void hs_proj_kernel(HcParams p)
             for (int j0 = 0; j0 < 8; ++j0) dmah(k, j0);
         }
     }
-    if (nhu >= 3) __builtin_amdgcn_s_waitcnt(0x0070 | (16 & 15) | ((16 >> 4) << 14));      // vmcnt(16) lgkmcnt(0)
-    else __builtin_amdgcn_s_waitcnt(0x0070);                      // vmcnt(0) lgkmcnt(0)
+    if (nhu >= 3) __builtin_amdgcn_s_waitcnt(tgp_waitcnt(16, 0));      // vmcnt(16) lgkmcnt(0)
+    else __builtin_amdgcn_s_waitcnt(tgp_waitcnt(0, 0));           // vmcnt(0) lgkmcnt(0)
     __builtin_amdgcn_s_barrier();
 
     // (a wave past the last row issues no stores: its waits count none, i.e. wait for more; a partly live wave issues all of them,
     // masked)
     const bool full = m0 < p.M;
-    hc32x16 accA[4], accB[4];
+    f32x16 accA[4], accB[4];
     float *c2p = p.c2 + (int64_t)rowc * p.ldc2 + 4 * h;
     // a finished group leaves in the gaps of the next one: block jj, quad g of group `grp` from `acc`, + bias.  (Store shapes measured with
     // the development build's knobs: this direct form touches 32 rows x 32 bytes per instruction; 16 rows x 64 bytes after one
     // v_permlane16_swap per register pair was slower -- the swaps are vector instructions --, and the same bytes as 8 rows x 128 bytes
     // through an LDS tile saturated the LDS, which the fragment reads already load to 60 %.)
-    auto store2 = [&](const hc32x16 (&acc)[4], const int grp, const int idx) {      // idx = 0 .. 15: (block, quad)
+    auto store2 = [&](const f32x16 (&acc)[4], const int grp, const int idx) {      // idx = 0 .. 15: (block, quad)
         const int jj = idx >> 2, g = idx & 3;
         const int c = 128 * grp + 32 * jj + 8 * g;
         const float4 b = *reinterpret_cast<const float4 *>(s_vec + (c - 128 * g0) + 4 * h);
@@ -470,47 +412,30 @@ __global__ __launch_bounds__(256, 1) void hs_proj_kernel(HcParams p)
 #define HR_HALF(K_, ACC, S0_, NST, FILL_A)                                                                                   \
     {                                                                                                                        \
         const int k_ = (K_);                                                                                                 \
-        const char *wrow = hc_smem + (k_ & 3) * HR_SLOT + lane * 16;                                                         \
+        const char *wslot = hc_smem + (k_ & 3) * HR_SLOT + lane * 16;                                                        \
         const bool stage = k_ + 3 < nhu;                                                                                     \
         u_src = u2_base + (int64_t)(k_ + 3) * HR_SLOT;                                                                       \
-        auto wfrag = [&](int q, int plane) { return *reinterpret_cast<const uint4 *>(wrow + (q * 2 + plane) * 1024); };      \
-        uint4 wh0 = wfrag(0, 0), wl0 = wfrag(0, 1), wh1 = wfrag(1, 0), wl1 = wfrag(1, 1);                                    \
-        HC_SB();                                                                                                             \
-        _Pragma("unroll") for (int q = 0; q < 16; ++q) {                                                                     \
-            const int s = (S0_) + q / 4, j = q % 4;                                                                          \
-            uint4 wh2 = wh1, wl2 = wl1;                                                                                      \
-            const hc16x8 bh = __builtin_bit_cast(hc16x8, a2h[s]), bl = __builtin_bit_cast(hc16x8, a2l[s]);                   \
-            ACC[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hc16x8, wl0), bh, ACC[j], 0, 0, 0);           \
-            HC_SB();                                                                                                         \
-            if (q + 2 < 16) wh2 = wfrag(q + 2, 0), wl2 = wfrag(q + 2, 1);                                                    \
-            FILL_A;                                                                                                          \
-            HC_SB();                                                                                                         \
-            ACC[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hc16x8, wh0), bl, ACC[j], 0, 0, 0);           \
-            HC_SB();                                                                                                         \
-            if (q < 8 && stage) dmah((k_ + 3) & 3, q);                                                                       \
-            HC_SB();                                                                                                         \
-            ACC[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hc16x8, wh0), bh, ACC[j], 0, 0, 0);           \
-            HC_SB();                                                                                                         \
-            wh0 = wh1, wl0 = wl1, wh1 = wh2, wl1 = wl2;                                                                      \
+        TGP_UNIT_BODY(wslot, 16, 4, ACC, __builtin_bit_cast(f16x8, a2h[(S0_) + s]), __builtin_bit_cast(f16x8, a2l[(S0_) + s]), \
+                      if (q < 8 && stage) dmah((k_ + 3) & 3, q), FILL_A, , /* no gap 3 */, HR_WAIT(k_, stage, NST)           \
+                      __builtin_amdgcn_s_barrier();)    /* the next half unit is in for everybody, and this slot's readers are done */ \
+    }
+#define HR_WAIT(k_, stage, NST)                                                                                              \
+    {                                                                                                                        \
+        const int nd = (k_ + 2 < nhu ? 1 : 0) + (stage ? 1 : 0);                                                             \
+        if ((NST) && full) {                                                                                                 \
+            if (nd == 2) __builtin_amdgcn_s_waitcnt(tgp_waitcnt(32));                                                        \
+            else if (nd == 1) __builtin_amdgcn_s_waitcnt(tgp_waitcnt(24));                                                   \
+            else __builtin_amdgcn_s_waitcnt(tgp_waitcnt(16));                                                                \
+        } else {                                                                                                             \
+            if (nd == 2) __builtin_amdgcn_s_waitcnt(tgp_waitcnt(16));                                                        \
+            else if (nd == 1) __builtin_amdgcn_s_waitcnt(tgp_waitcnt(8));                                                    \
+            else __builtin_amdgcn_s_waitcnt(tgp_waitcnt(0));                                                                 \
         }                                                                                                                    \
-        {                                                                                                                    \
-            const int nd = (k_ + 2 < nhu ? 1 : 0) + (stage ? 1 : 0);                                                         \
-            if ((NST) && full) {                                                                                             \
-                if (nd == 2) __builtin_amdgcn_s_waitcnt(hc_vmcnt(32));                                                       \
-                else if (nd == 1) __builtin_amdgcn_s_waitcnt(hc_vmcnt(24));                                                  \
-                else __builtin_amdgcn_s_waitcnt(hc_vmcnt(16));                                                               \
-            } else {                                                                                                         \
-                if (nd == 2) __builtin_amdgcn_s_waitcnt(hc_vmcnt(16));                                                       \
-                else if (nd == 1) __builtin_amdgcn_s_waitcnt(hc_vmcnt(8));                                                   \
-                else __builtin_amdgcn_s_waitcnt(hc_vmcnt(0));                                                                \
-            }                                                                                                                \
-        }                                                                                                                    \
-        __builtin_amdgcn_s_barrier();       /* the next half unit is in for everybody, and this slot's readers are done */     \
     }
     // group GI of this workgroup into ACC; the previous group's 16 stores (from PREV) ride in its second half unit (NST: are there any)
 #define HR_GROUP(GI, ACC, PREV)                                                                                              \
     {                                                                                                                        \
-        HC_ZERO(ACC)                                                                                                         \
+        TGP_ZERO4(ACC)                                                                                                       \
         const bool have_prev = (GI) > 0;                                                                                     \
         _Pragma("unroll") for (int w = 0; w < U2; ++w) {                                                                     \
             HR_HALF(((GI) * U2 + w) * 2, ACC, 8 * w, false, )                                                                \
@@ -532,14 +457,18 @@ __global__ __launch_bounds__(256, 1) void hs_proj_kernel(HcParams p)
     }
 #undef HR_GROUP
 #undef HR_HALF
+#undef HR_WAIT
 }
 
-// ---- weights -> staging units.  Layer 1: W1 (N1, K1) -> U1 units, pair q = s * NB1 + j of unit u = K-step u * (32 / NB1) + s, output
-// block j; layer 2: W2 (N2, N1) -> per group of four output blocks (N2 / 128 groups) N1 / 128 units, pair q = s * 4 + j of unit w =
-// K-step 8 w + s, output block 4 group + j.  A pair is two pieces of 1 KB, [lane = 32 h + r][8 fp16] = W[32 block + r][16 step + 8 h + t]
-// as its fp16 hi (first piece) / lo part; columns >= K are zero.
-__global__ void hs_chain_pack_kernel(const float *__restrict__ W, int ld, int N, int K, int nb, int steps, int units, int layer2,
-                                     uint16_t *__restrict__ out)
+// ---- weights -> staging units: the fragment-blocked image every kernel built on TGP_UNIT_BODY stages (tgp_hs_chain_pack,
+// tgp_proj_pack, tgp_dec_pack).  W (N, K) fp32 row-major; a unit is 32 pairs of two 1 KB pieces, piece q * 2 + plane =
+// [lane = 32 h + r][8 fp16] = W[32 block + r][k(step, 8 h + t)], t = 0 .. 7, as its fp16 hi (plane 0) / lo (plane 1) part.  Pair q of unit u is
+// K-step (u % upg) * (32 / nb) + q / nb and output block (u / upg) * nb + q % nb: a unit holds nb output blocks of 32 / nb K-steps, and upg
+// units cover the K range of a group of nb blocks.  permuted = 0: k = 16 step + slot (natural order); 1: slot 8 h + t of step 2 b + s2 is
+// channel 32 b + 16 s2 + 8 (t >> 2) + 4 h + (t & 3) -- the order in which the previous layer's accumulators hold a block's channels.  Steps
+// beyond the layer's, columns >= K and rows >= N are zero.
+__global__ void pack_units_kernel(const float *__restrict__ W, int ld, int N, int K, int nb, int upg, int steps, int units, int permuted,
+                                  uint16_t *__restrict__ out)
 {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t total = (int64_t)units * 32 * 512;
@@ -547,21 +476,21 @@ __global__ void hs_chain_pack_kernel(const float *__restrict__ W, int ld, int N,
     const int tt = (int)(t & 7), rr = (int)((t >> 3) & 31), hh = (int)((t >> 8) & 1);
     const int q = (int)((t >> 9) & 31);
     const int unit = (int)(t >> 14);
-    int step, blk;
-    if (layer2) {
-        const int upg = steps / 8;                               // units per group
-        step = (unit % upg) * 8 + q / 4, blk = (unit / upg) * 4 + q % 4;
-    } else {
-        const int spu = 32 / nb;
-        step = unit * spu + q / nb, blk = q % nb;
-    }
-    const int col = 16 * step + 8 * hh + tt, rowi = 32 * blk + rr;
+    const int step = (unit % upg) * (32 / nb) + q / nb, blk = (unit / upg) * nb + q % nb;
+    const int col = permuted ? 32 * (step >> 1) + 16 * (step & 1) + 8 * (tt >> 2) + 4 * hh + (tt & 3) : 16 * step + 8 * hh + tt;
+    const int rowi = 32 * blk + rr;
     const float v = (step < steps && col < K && rowi < N) ? W[(int64_t)rowi * ld + col] : 0.f;
     const _Float16 hi = (_Float16)v;
     const _Float16 lo = (_Float16)(v - (float)hi);
     uint16_t *dst = out + (int64_t)unit * (HC_UNIT / 2) + (int64_t)(q * 2) * 512 + (hh * 32 + rr) * 8 + tt;
     dst[0] = __builtin_bit_cast(uint16_t, hi);
     dst[512] = __builtin_bit_cast(uint16_t, lo);
+}
+
+int tgp_pack_units(const float *W, int ld, int N, int K, int nb, int upg, int steps, int units, int permuted, uint16_t *out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(pack_units_kernel, dim3(units * 64), dim3(256), 0, stream, W, ld, N, K, nb, upg, steps, units, permuted, out);
+    return TGP_LAUNCH_RESULT();
 }
 
 static bool hc_shape(int K1, int N1, int N2, int &k1t, int &u1, int &ng, int &u2)
@@ -586,10 +515,9 @@ extern "C" int tgp_hs_chain_pack(const float *w1, int ld1, int K1, int N1, const
     TGP_REQUIRE(w1 && w2 && out && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && ld1 >= K1 && ld2 >= N1);
     TGP_REQUIRE(hc_shape(K1, N1, N2, k1t, u1, ng, u2));
     uint16_t *o = reinterpret_cast<uint16_t *>(out);
-    hipLaunchKernelGGL(hs_chain_pack_kernel, dim3(u1 * 64), dim3(256), 0, tgp_hs(stream), w1, ld1, N1, K1, N1 / 32, k1t, u1, 0, o);
-    hipLaunchKernelGGL(hs_chain_pack_kernel, dim3(ng * u2 * 64), dim3(256), 0, tgp_hs(stream), w2, ld2, N2, N1, 4, N1 / 16, ng * u2, 1,
-                       o + (int64_t)u1 * (HC_UNIT / 2));
-    return TGP_LAUNCH_RESULT();
+    // layer 1: u1 units of all N1 / 32 output blocks; layer 2: per group of four output blocks (N2 / 128 groups) u2 units of eight K-steps
+    if (const int e = tgp_pack_units(w1, ld1, N1, K1, N1 / 32, u1, k1t, u1, 0, o, tgp_hs(stream))) return e;
+    return tgp_pack_units(w2, ld2, N2, N1, 4, u2, N1 / 16, ng * u2, 0, o + (int64_t)u1 * (HC_UNIT / 2), tgp_hs(stream));
 }
 
 #ifdef TGP_DEV
@@ -653,10 +581,8 @@ extern "C" int64_t tgp_proj_pack_bytes(int K, int N)
 extern "C" int tgp_proj_pack(const float *w, int ld, int K, int N, void *out, tgp_stream_t stream)
 {
     TGP_REQUIRE(w && out && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && ld >= K && tgp_proj_pack_bytes(K, N) > 0);
-    const int units = (N / 128) * (K / 128);
-    hipLaunchKernelGGL(hs_chain_pack_kernel, dim3(units * 64), dim3(256), 0, tgp_hs(stream), w, ld, N, K, 4, K / 16, units, 1,
-                       reinterpret_cast<uint16_t *>(out));
-    return TGP_LAUNCH_RESULT();
+    // per group of four output blocks K / 128 units of eight K-steps
+    return tgp_pack_units(w, ld, N, K, 4, K / 128, K / 16, (N / 128) * (K / 128), 0, reinterpret_cast<uint16_t *>(out), tgp_hs(stream));
 }
 
 extern "C" int tgp_proj_planes(const tgp_proj_planes_args *a, tgp_stream_t stream)
