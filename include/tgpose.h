@@ -431,6 +431,49 @@ int tgp_fps_max_points(void);
 int tgp_fps(const float *xyz, int ld, const int32_t *counts, int B, int M, int n, const float *start, int init_center,
             int32_t *idx, float *dist_out, int32_t *clusters_out, tgp_stream_t stream);
 
+/* ---- depth renderer (csrc/render.hip; additive, ABI stays 8) -------------------------------------- */
+
+/* A z-buffer rasteriser of posed triangle meshes: S scenes in one call, every output a function of the inputs alone (DESIGN.md
+ * section 3 "The depth renderer" states the arithmetic; tests/render_ref.py restates it in numpy and the two agree bit for bit).
+ * Mesh set: verts (n_verts,3) fp32 model units; faces (n_faces,3) int32 LOCAL to their mesh; vptr, fptr (M+1) int32 prefix sums.
+ * Scene set: scene_ptr (S+1) int32 into the instance arrays; inst_mesh (I) int32; inst_id (I) uint8 in 1..255; inst_pose (I,3,4)
+ * fp32 [s R | t], model -> camera in metres; camk (S,4) fp32 = fx, fy, cx, cy.  Everything lives on the device; the host states only
+ * sizes and bounds: max_verts / max_faces (the largest mesh; a longer mesh is cut to them) and max_scene_inst (the longest scene).
+ * -> depth (S,H,W) uint16 millimetres, mask (S,H,W) uint8 instance id, both 0 where no surface; z (S,H,W) fp32 metres, +inf where
+ * empty, and face (S,H,W) int32 (index within the mesh, -1 where empty), each may be NULL; visible (I) int32 pixels won; bbox (I,4)
+ * int32 (y1,x1,y2,x2), y2/x2 exclusive, zeros when invisible; dropped (S,2) int32: triangles with a vertex at p_z <= near, triangles
+ * with a snapped coordinate beyond 2^22 sub-pixel units.  A mesh index outside [0,M), a face index outside its mesh and rows of
+ * vptr / fptr that leave the arrays render nothing.  workspace: tgp_render_workspace_bytes(I, max_verts, max_faces) bytes.
+ * TGP_EINVAL: a NULL required pointer, S, M, H, W, max_verts or max_faces < 1, I < 0, near <= 0 or not finite.  TGP_EUNSUPPORTED:
+ * max_faces >= tgp_render_max_faces() (2^24), max_scene_inst > tgp_render_max_instances() (255), H or W > 16384.  Nothing is
+ * launched on an error.  Three kernels (vertices, triangle boxes, tiles) and one over the instances; graph-capturable. */
+typedef struct {
+    const float *verts;
+    const int32_t *faces;
+    const int32_t *vptr, *fptr;
+    int M, n_verts, n_faces, max_verts, max_faces;
+    const int32_t *scene_ptr;
+    const int32_t *inst_mesh;
+    const uint8_t *inst_id;
+    const float *inst_pose;
+    const float *camk;
+    int S, I, max_scene_inst;
+    int H, W;
+    float near;
+    void *workspace;
+    uint16_t *depth;
+    uint8_t *mask;
+    float *z;          /* may be NULL */
+    int32_t *face;     /* may be NULL */
+    int32_t *visible;
+    int32_t *bbox;
+    int32_t *dropped;
+} tgp_render_args;
+int tgp_render_max_faces(void);
+int tgp_render_max_instances(void);
+int64_t tgp_render_workspace_bytes(int I, int max_verts, int max_faces);
+int tgp_render_depth(const tgp_render_args *args, tgp_stream_t stream);
+
 /* TDA_loss.R_DCD pose normalisation (:326-339): R from the predicted axes p_g, p_r (B,3) and confidences f_g, f_r
  * (B) -- for objects with sym[b*sym_ld] == 1 the green axis is paired with column 0 of the true rotation gR (B,3,3)
  * -- then out[b,i] = (R^T (points[b,i] - p_t[b])) * p_s[b].  R_out (B,3,3) optional. */

@@ -218,6 +218,16 @@ class GatherSlotsArgs(ctypes.Structure):
                 ("src", c_vp * 24), ("dst", c_vp * 24), ("row_words", c_int * 24)]
 
 
+class RenderArgs(ctypes.Structure):
+    """struct tgp_render_args (include/tgpose.h)"""
+    _fields_ = [("verts", c_vp), ("faces", c_vp), ("vptr", c_vp), ("fptr", c_vp),
+                ("M", c_int), ("n_verts", c_int), ("n_faces", c_int), ("max_verts", c_int), ("max_faces", c_int),
+                ("scene_ptr", c_vp), ("inst_mesh", c_vp), ("inst_id", c_vp), ("inst_pose", c_vp), ("camk", c_vp),
+                ("S", c_int), ("I", c_int), ("max_scene_inst", c_int), ("H", c_int), ("W", c_int), ("near", c_f32),
+                ("workspace", c_vp),
+                ("depth", c_vp), ("mask", c_vp), ("z", c_vp), ("face", c_vp), ("visible", c_vp), ("bbox", c_vp), ("dropped", c_vp)]
+
+
 GATHER_SLOTS_MAX, DRAW_MAX_ITEMS, DRAW_MAX_TOTAL = 24, 4096, 65536
 SITE_HOST, SITE_BAND, SITE_SEL2K, SITE_SEL1K, SITE_DEFOR, SITE_NOISE, SITE_DROP, SITE_SHUFFLE = range(8)
 ITEM_ALIVE, ITEM_NO_DEPTH, ITEM_NO_MASK, ITEM_FEW_POINTS, ITEM_BELOW_26, ITEM_WINDOW = range(6)
@@ -320,6 +330,10 @@ SIGNATURES = {
     "tgp_emd_bwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     "tgp_fps_max_points": (c_int, []),
     "tgp_fps": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "tgp_render_max_faces": (c_int, []),
+    "tgp_render_max_instances": (c_int, []),
+    "tgp_render_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
+    "tgp_render_depth": (c_int, [ctypes.POINTER(RenderArgs), c_vp]),
     "tgp_generate_rt": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     "tgp_canonicalize": (c_int, [c_vp] * 9 + [c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "tgp_heads_fused": (c_int, [ctypes.POINTER(HeadsFusedArgs), c_vp]),

@@ -1112,6 +1112,93 @@ def farthest_points(xyz, n, counts=None, start=None, init_center=True, return_di
     return out[0] if len(out) == 1 else out
 
 
+class MeshSet(object):
+    """Triangle meshes packed once for ops.render_depth (tgp_render_depth's mesh set): ``meshes`` is a list of (verts (V,3) float,
+    faces (F,3) int, local to their mesh).  Holds verts (sum V,3) float32, faces (sum F,3) int32 and the prefix sums vptr / fptr
+    (M+1) int32 on ``device``, and on the host the counts, the largest mesh and each mesh's axis-aligned extent."""
+
+    def __init__(self, meshes, device="cuda"):
+        import numpy as np
+        if not meshes:
+            raise ValueError("MeshSet: at least one mesh")
+        vs, fs = [], []
+        for i, (v, f) in enumerate(meshes):
+            v, f = np.ascontiguousarray(v, dtype=np.float32), np.ascontiguousarray(f, dtype=np.int32)
+            if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3 or not len(v) or not len(f):
+                raise ValueError("MeshSet: mesh %d must be (verts (V,3), faces (F,3)) with V, F >= 1" % i)
+            if f.min() < 0 or f.max() >= len(v):
+                raise ValueError("MeshSet: mesh %d has a face index outside its %d vertices" % (i, len(v)))
+            if len(f) >= render_max_faces():
+                raise ValueError("MeshSet: mesh %d has %d faces; the cap is %d" % (i, len(f), render_max_faces() - 1))
+            vs.append(v), fs.append(f)
+        self.n_verts = [len(v) for v in vs]
+        self.n_faces = [len(f) for f in fs]
+        self.extent = np.stack([v.max(0) - v.min(0) for v in vs])
+        self.device = torch.device(device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        self.verts, self.faces = up(np.concatenate(vs)), up(np.concatenate(fs))
+        self.vptr = up(np.concatenate([[0], np.cumsum(self.n_verts)]).astype(np.int32))
+        self.fptr = up(np.concatenate([[0], np.cumsum(self.n_faces)]).astype(np.int32))
+
+    def __len__(self):
+        return len(self.n_verts)
+
+
+def render_max_faces():
+    return int(_lib.lib().tgp_render_max_faces())
+
+
+def render_max_instances():
+    return int(_lib.lib().tgp_render_max_instances())
+
+
+def render_depth(meshset, scene_ptr, inst_mesh, inst_id, inst_pose, camk, H, W, near=0.01, return_z=False, return_face=False):
+    """Depth frames and instance masks of posed meshes, S scenes in one call (tgp_render_depth, csrc/render.hip; the arithmetic is
+    DESIGN.md section 3 "The depth renderer").  All tensors on the mesh set's GPU: scene_ptr (S+1) int32 into the instance arrays,
+    inst_mesh (I) int32, inst_id (I) uint8 in 1..255, inst_pose (I,3,4) float32 [s R | t] (model -> camera, metres), camk (S,4)
+    float32 = fx, fy, cx, cy.  -> dict: depth (S,H,W) uint16 millimetres and mask (S,H,W) uint8, 0 where no surface; visible (I)
+    int32; bbox (I,4) int32 (y1,x1,y2,x2), exclusive ends, zeros when invisible; dropped (S,2) int32 (near rule, guard band);
+    with return_z z (S,H,W) float32 metres, +inf where empty; with return_face face (S,H,W) int32, -1 where empty.
+    Nothing synchronises, except that with more than render_max_instances() instances in all, scene_ptr is read back once to
+    refuse a scene above the cap."""
+    if not isinstance(meshset, MeshSet):
+        raise TypeError("render_depth: meshset must be an ops.MeshSet")
+    for t, name, dt in ((scene_ptr, "scene_ptr", torch.int32), (inst_mesh, "inst_mesh", torch.int32), (inst_id, "inst_id", torch.uint8),
+                        (inst_pose, "inst_pose", torch.float32), (camk, "camk", torch.float32)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise TypeError("render_depth: %s must be a contiguous %s GPU tensor" % (name, str(dt).replace("torch.", "")))
+        if t.device != meshset.verts.device:
+            raise ValueError("render_depth: %s is not on the mesh set's device" % name)
+    S, I = scene_ptr.numel() - 1, inst_mesh.numel()
+    H, W = int(H), int(W)
+    if S < 1 or scene_ptr.dim() != 1 or camk.shape != (S, 4) or inst_mesh.dim() != 1 or inst_id.shape != (I,) or inst_pose.shape != (I, 3, 4):
+        raise ValueError("render_depth: scene_ptr (S+1), inst_mesh (I), inst_id (I), inst_pose (I,3,4), camk (S,4) are expected")
+    if H < 1 or W < 1 or not float(near) > 0.0:
+        raise ValueError("render_depth: H, W and near must be positive")
+    cap = render_max_instances()
+    longest = I if I <= cap else int((scene_ptr[1:] - scene_ptr[:-1]).max().item())
+    if longest > cap:
+        raise ValueError("render_depth: a scene of %d instances; the cap is %d" % (longest, cap))
+    dev = inst_pose.device
+    out = {"depth": torch.empty(S, H, W, device=dev, dtype=torch.uint16), "mask": torch.empty(S, H, W, device=dev, dtype=torch.uint8),
+           "visible": torch.empty(I, device=dev, dtype=torch.int32), "bbox": torch.empty(I, 4, device=dev, dtype=torch.int32),
+           "dropped": torch.empty(S, 2, device=dev, dtype=torch.int32)}
+    if return_z:
+        out["z"] = torch.empty(S, H, W, device=dev, dtype=torch.float32)
+    if return_face:
+        out["face"] = torch.empty(S, H, W, device=dev, dtype=torch.int32)
+    max_v, max_f = max(meshset.n_verts), max(meshset.n_faces)
+    ws = torch.empty(int(_lib.lib().tgp_render_workspace_bytes(I, max_v, max_f)), device=dev, dtype=torch.uint8)
+    a = _lib.RenderArgs(verts=_p(meshset.verts), faces=_p(meshset.faces), vptr=_p(meshset.vptr), fptr=_p(meshset.fptr), M=len(meshset),
+                        n_verts=meshset.verts.shape[0], n_faces=meshset.faces.shape[0], max_verts=max_v, max_faces=max_f,
+                        scene_ptr=_p(scene_ptr), inst_mesh=_p(inst_mesh), inst_id=_p(inst_id), inst_pose=_p(inst_pose), camk=_p(camk),
+                        S=S, I=I, max_scene_inst=longest, H=H, W=W, near=float(near), workspace=_p(ws), depth=_p(out["depth"]),
+                        mask=_p(out["mask"]), z=_p(out.get("z")), face=_p(out.get("face")), visible=_p(out["visible"]),
+                        bbox=_p(out["bbox"]), dropped=_p(out["dropped"]))
+    check(_lib.lib().tgp_render_depth(ctypes.byref(a), _stream(inst_pose)), "tgp_render_depth")
+    return out
+
+
 def canonicalize(points, gR, p_g, f_g, p_r, f_r, p_t, p_s, sym):
     """R_DCD pose normalisation -> (points_re_n (B,n,3), R (B,3,3))"""
     c = lambda t: _f32(t.contiguous(), "arg")
