@@ -1186,6 +1186,51 @@ typedef struct tgp_gather_slots_args {
 } tgp_gather_slots_args;
 int tgp_gather_slots(const tgp_gather_slots_args *args, tgp_stream_t stream);
 
+/* ---- mesh surface sampling (csrc/meshsample.hip; additive, ABI stays 8) ---------------------------------------------------------
+ * uniform_sample (network/point_sample/pc_sample_sphere.py:154-169) for a batch of jobs on a mesh set (verts, faces, vptr, fptr as
+ * tgp_render_depth reads them).  DESIGN.md section 3 "Mesh surface sampling" is the contract; tests/mesh_sample_ref.py restates it in
+ * NumPy and the two agree bit for bit.  All arithmetic is float64 on the float32 vertices, every product and sum rounded on its own.
+ *
+ * Area table: with a = v1 - v0, b = v2 - v0 of face f, cross = (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x),
+ * norm = sqrt((c_x c_x + c_y c_y) + c_z c_z), area = 0.5 norm.  cdf[fptr[m] + f] is the mesh's cumulative area in this FIXED order:
+ * the faces are cut into chunks of TGP_MESH_AREA_CHUNK consecutive faces; local[f] is the serial sum of the areas from the chunk's
+ * first face to f; T[c] is local at the chunk's last face; O[0] = 0, O[c] = O[c - 1] + T[c - 1] (serial); cdf[f] = O[c] + local[f].
+ * The order depends on neither the launch shape nor the other meshes of the set.  A mesh whose vptr / fptr rows leave the arrays or
+ * are empty is not written. */
+#define TGP_MESH_AREA_CHUNK 64
+#define TGP_MESH_SITE 8      /* the draw site of the device uniforms (after TGP_SITE_SHUFFLE) */
+int tgp_mesh_area_cdf(const float *verts, const int32_t *faces, const int32_t *vptr, const int32_t *fptr, int M, int n_verts,
+                      int n_faces, double *cdf, tgp_stream_t stream);
+/* B jobs of n samples each in ONE launch.  Job b samples mesh job_mesh[b]; sample i takes three uniforms (u, r1, r2) in [0, 1):
+ * from u (B,n,3) float64 when given (the reference's np.random.random(), then np.random.random(2)), else from the Philox words of
+ * (seed, keys[b], TGP_MESH_SITE): counter 2i gives u = uniform_f64(w0, w1) and r1 = uniform_f64(w2, w3), counter 2i + 1 gives
+ * r2 = uniform_f64(w0, w1).  Exactly one of u and keys is non-NULL.
+ * With total = cdf at the mesh's last face: face = the first f with cdf[f] >= u total (binary search; np.searchsorted side='left'),
+ * clamped to F - 1; s = sqrt(r1); point = ((1 - s) v0 + (s (1 - r2)) v1) + (s r2) v2 per component; normal = cross / norm (NaN for
+ * a zero-area face).  sqrt and / are correctly rounded.
+ * -> out (B,n,3) or with normals (B,n,6) [point, normal], float64, or with f32 != 0 float32 (the float64 value rounded once);
+ * face (B,n) int32 or NULL; status (B) int32: 0, 1 when total is not a positive finite number (rows are still written), 2 when
+ * job_mesh[b] is outside [0, M) or the mesh's rows leave the arrays (rows are zeros, face -1).  A vertex index outside its mesh is
+ * clamped into it.  TGP_EINVAL: a NULL required pointer, M, n_verts, n_faces, B or n < 1, both or neither of u / keys.
+ * TGP_EUNSUPPORTED: B > 65535.  Nothing is launched on an error. */
+typedef struct tgp_mesh_sample_args {
+    const float *verts;
+    const int32_t *faces;
+    const int32_t *vptr, *fptr;
+    const double *cdf;          /* tgp_mesh_area_cdf's table (n_faces) */
+    int M, n_verts, n_faces;
+    const int32_t *job_mesh;    /* (B) */
+    int B, n;
+    const double *u;            /* (B,n,3) or NULL */
+    const uint64_t *keys;       /* (B) or NULL */
+    uint64_t seed;
+    int normals, f32;
+    void *out;
+    int32_t *face;              /* may be NULL */
+    int32_t *status;
+} tgp_mesh_sample_args;
+int tgp_mesh_sample(const tgp_mesh_sample_args *args, tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -228,6 +228,18 @@ class RenderArgs(ctypes.Structure):
                 ("depth", c_vp), ("mask", c_vp), ("z", c_vp), ("face", c_vp), ("visible", c_vp), ("bbox", c_vp), ("dropped", c_vp)]
 
 
+class MeshSampleArgs(ctypes.Structure):
+    """struct tgp_mesh_sample_args (include/tgpose.h)"""
+    _fields_ = [("verts", c_vp), ("faces", c_vp), ("vptr", c_vp), ("fptr", c_vp), ("cdf", c_vp),
+                ("M", c_int), ("n_verts", c_int), ("n_faces", c_int),
+                ("job_mesh", c_vp), ("B", c_int), ("n", c_int),
+                ("u", c_vp), ("keys", c_vp), ("seed", ctypes.c_uint64),
+                ("normals", c_int), ("f32", c_int),
+                ("out", c_vp), ("face", c_vp), ("status", c_vp)]
+
+
+MESH_SITE, MESH_AREA_CHUNK = 8, 64           # TGP_MESH_SITE, TGP_MESH_AREA_CHUNK
+MESH_STATUS = {1: "the mesh's total area is not a positive finite number", 2: "the mesh index or the mesh's rows are outside the set"}
 GATHER_SLOTS_MAX, DRAW_MAX_ITEMS, DRAW_MAX_TOTAL = 24, 4096, 65536
 SITE_HOST, SITE_BAND, SITE_SEL2K, SITE_SEL1K, SITE_DEFOR, SITE_NOISE, SITE_DROP, SITE_SHUFFLE = range(8)
 ITEM_ALIVE, ITEM_NO_DEPTH, ITEM_NO_MASK, ITEM_FEW_POINTS, ITEM_BELOW_26, ITEM_WINDOW = range(6)
@@ -396,6 +408,8 @@ SIGNATURES = {
     "tgp_draw_selection": (c_int, [c_vp, c_int, c_int, c_vp, c_u64, c_u32, c_int, c_int, c_int, c_vp, c_vp]),
     "tgp_draw_fill": (c_int, [c_vp, c_u64, c_int, c_int, c_vp, c_vp, c_f32, c_f32, c_vp, c_vp]),
     "tgp_gather_slots": (c_int, [ctypes.POINTER(GatherSlotsArgs), c_vp]),
+    "tgp_mesh_area_cdf": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    "tgp_mesh_sample": (c_int, [ctypes.POINTER(MeshSampleArgs), c_vp]),
 }
 
 ABI_VERSION = 8

@@ -38,6 +38,39 @@ from ..evaluation.load_data_eval import CAMERA_INTRINSICS, REAL_INTRINSICS, get_
 AB_BITS = 10          # OpenCV's warpAffine works in 10-bit fixed point (AB_SCALE = 1024)
 
 
+def _category_id(c):
+    from ..evaluater.RT_TDA_Evaluater import SYNSET_NAMES
+    return SYNSET_NAMES.index(c) if isinstance(c, str) and c in SYNSET_NAMES[1:] else None
+
+
+def get_fs_net_scale(c, model, nocs_scale):
+    """PoseDataset.get_fs_net_scale (datasets/load_data.py:453-519): category name c, model (P,3) in NOCS units, nocs_scale ->
+    (the size residual, the category's mean size), both (3,) in millimetres.  The mean sizes are the evaluater's MEAN_SHAPE_MM;
+    a name outside the six categories raises NotImplementedError (the ShapeNet synset ids the reference also lists are not kept)."""
+    from ..evaluater.RT_TDA_Evaluater import MEAN_SHAPE_MM
+    k = _category_id(c)
+    if k is None:
+        raise NotImplementedError("get_fs_net_scale: category %r is not one of the six" % (c,))
+    model = np.asarray(model)
+    size = (model.max(0) - model.min(0)) * nocs_scale * 1000                 # the model's extent in millimetres
+    mean = np.array(MEAN_SHAPE_MM[k])
+    return size - mean.astype(size.dtype), mean
+
+
+def get_sym_info(c, mug_handle=1):
+    """PoseDataset.get_sym_info (datasets/load_data.py:521-543) -> (4,) int32 from the evaluater's SYM_INFO; a mug without a visible
+    handle is (1, 0, 0, 0); any other name is zeros, as in the reference"""
+    from ..evaluater.RT_TDA_Evaluater import SYM_INFO
+    k = _category_id(c)
+    if k is None:
+        return np.array([0, 0, 0, 0], dtype=np.int32)
+    if c == "mug" and mug_handle == 0:
+        return np.array([1, 0, 0, 0], dtype=np.int32)
+    if c == "mug" and mug_handle != 1:
+        return np.array([0, 0, 0, 0], dtype=np.int32)
+    return np.array(SYM_INFO[k], dtype=np.int32)
+
+
 def window_without_dzi(bbox, im_H, im_W):
     """load_data.py:233-238 when FLAGS.DZI_TYPE names none of the augmenting kinds (tools/dataset_utils.py:57-61): get_bbox's window
     -> (bbox_center (cx, cy) float64, scale)."""

@@ -2,7 +2,10 @@
 two loaders read, with pose labels that are the numbers that produced the pixels.
 
 A scene is a list of instances, each ``dict(mesh=index into the mesh set, inst_id=1..255, R=(3,3), t=(3,) metres, s=scale,
-labels=dict)``: the model -> camera map is x_cam = s R x_model + t.  Frames come back to the host once, at generation."""
+labels=dict)``: the model -> camera map is x_cam = s R x_model + t.  Frames come back to the host once, at generation.
+
+``mesh_labels`` makes an instance's ``labels`` from its mesh (ops.mesh_sample_fps, csrc/meshsample.hip) and ``category_tables`` the
+category clouds and persistence images TrainBatches takes, so nothing about a rendered item is hand-written."""
 import numpy as np
 import torch
 
@@ -104,3 +107,53 @@ def scene_frame(meshset, scenes, rendered, index):
                 pred_inst=np.asarray(vis, dtype=np.int32), gt_RTs=RTs,
                 gt_scales=np.asarray([meshset.extent[int(inst["mesh"])] for inst in sc], dtype=np.float64).reshape(-1, 3),
                 gt_class_ids=np.asarray([cls(inst) for inst in sc], dtype=np.int32), gt_handle_visibility=np.ones(len(sc), dtype=np.int32))
+
+
+def _surface_clouds(meshset, meshes, n, seed):
+    """(len(meshes), n, 3) float32 on the device: 2 n surface samples of each mesh thinned to n by farthest point sampling, the
+    draws keyed by (seed, mesh index) -- a mesh's cloud depends on neither the other jobs nor the order of the calls"""
+    meshes = [int(m) for m in meshes]
+    return ops.mesh_sample_fps(meshset, meshes, int(n), 2, keys=meshes, seed=seed)
+
+
+def mesh_labels(meshset, mesh, category, s, n_model=1024, seed=0):
+    """The ``labels`` dict of an instance of mesh ``mesh`` (category name ``category``, scale ``s``: model units -> metres), made
+    from the mesh and nothing hand-written: model_point (n_model,3) float32 in the mesh's own units (ops.mesh_sample_fps, ratio 2,
+    device draws keyed by (seed, mesh)); fsnet_scale and mean_shape (3,) in metres -- load_data.get_fs_net_scale with nocs_scale = s,
+    divided by 1000 as the reference's loader does (:273-276); sym_info, cat_id (0-based), nocs_scale.
+    The size handed to get_fs_net_scale is the mesh's own axis-aligned extent, not the extent of model_point: the samples stop
+    short of the outermost vertices by a fraction of a facet (1.4e-4 to 1.7e-2 model units on the four lathe shapes, up to 1.7 mm
+    at s = 0.1), and the label is the object's size; model_point's own extent differs from it by that much."""
+    from . import load_data as ld
+    from ..evaluater.RT_TDA_Evaluater import SYNSET_NAMES
+    mesh = int(mesh)
+    if not 0 <= mesh < len(meshset):
+        raise ValueError("mesh_labels: mesh index %d is outside the set of %d meshes" % (mesh, len(meshset)))
+    out = _surface_clouds(meshset, [mesh], n_model, seed)
+    ops.mesh_check_status(out["status"], "mesh_labels")
+    ext = np.asarray(meshset.extent[mesh], dtype=np.float32)
+    fsnet_scale, mean_shape = ld.get_fs_net_scale(category, np.stack([np.zeros_like(ext), ext]), s)
+    return dict(model_point=out["points"][0].cpu().numpy(), fsnet_scale=(fsnet_scale / 1000.0).astype(np.float32),
+                mean_shape=(mean_shape / 1000.0).astype(np.float32), sym_info=ld.get_sym_info(category),
+                cat_id=SYNSET_NAMES.index(category) - 1, nocs_scale=np.float32(s))
+
+
+def category_tables(meshset, cat_mesh, n=1024, seed=0):
+    """TrainBatches(category_tables=...)'s triple from each category's canonical mesh: cat_mesh (C) mesh indices, None or a negative
+    index for a category without a mesh (its rows are zeros) -> points_category (C,n,3), pdh1_category (C,2500), pdh2_category
+    (C,2500), float32 numpy.  The clouds are sampled as mesh_labels' model_point (same keys: a category's cloud is its mesh's
+    model_point at the same n and seed); the images are ops.persistence_images of those clouds."""
+    cat_mesh = [-1 if m is None else int(m) for m in cat_mesh]
+    live = [c for c, m in enumerate(cat_mesh) if m >= 0]
+    if not live:
+        raise ValueError("category_tables: no category has a mesh")
+    if any(cat_mesh[c] >= len(meshset) for c in live):
+        raise ValueError("category_tables: a mesh index is outside the set of %d meshes" % len(meshset))
+    out = _surface_clouds(meshset, [cat_mesh[c] for c in live], n, seed)
+    ops.mesh_check_status(out["status"], "category_tables")
+    h1, h2 = ops.persistence_images(out["points"].contiguous())
+    C = len(cat_mesh)
+    tabs = [np.zeros((C, int(n), 3), np.float32), np.zeros((C, h1.shape[1]), np.float32), np.zeros((C, h2.shape[1]), np.float32)]
+    for t, src in zip(tabs, (out["points"], h1, h2)):
+        t[live] = src.cpu().numpy()
+    return tuple(tabs)

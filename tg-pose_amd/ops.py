@@ -1115,7 +1115,8 @@ def farthest_points(xyz, n, counts=None, start=None, init_center=True, return_di
 class MeshSet(object):
     """Triangle meshes packed once for ops.render_depth (tgp_render_depth's mesh set): ``meshes`` is a list of (verts (V,3) float,
     faces (F,3) int, local to their mesh).  Holds verts (sum V,3) float32, faces (sum F,3) int32 and the prefix sums vptr / fptr
-    (M+1) int32 on ``device``, and on the host the counts, the largest mesh and each mesh's axis-aligned extent."""
+    (M+1) int32 on ``device``, and on the host the counts, the largest mesh and each mesh's axis-aligned extent.  ops.mesh_sample
+    reads the same set; its cumulative-area table is built on first use (area_cdf)."""
 
     def __init__(self, meshes, device="cuda"):
         import numpy as np
@@ -1139,9 +1140,130 @@ class MeshSet(object):
         self.verts, self.faces = up(np.concatenate(vs)), up(np.concatenate(fs))
         self.vptr = up(np.concatenate([[0], np.cumsum(self.n_verts)]).astype(np.int32))
         self.fptr = up(np.concatenate([[0], np.cumsum(self.n_faces)]).astype(np.int32))
+        self._area_cdf = None
 
     def __len__(self):
         return len(self.n_verts)
+
+    def area_cdf(self):
+        """(sum F) float64 on the device: each mesh's cumulative triangle area over its own faces in tgp_mesh_area_cdf's fixed
+        order (chunks of 64 faces; DESIGN.md section 3 "Mesh surface sampling").  Built by one launch on the current stream at
+        first use and kept; that stream is synchronised once, there, so that later calls may read the table from any stream
+        (call it before a graph capture that samples from the set)."""
+        if self._area_cdf is None:
+            if self.verts.device.type != "cuda":
+                raise TypeError("MeshSet.area_cdf: the mesh set must be on a GPU")
+            cdf = torch.zeros(self.faces.shape[0], device=self.verts.device, dtype=torch.float64)
+            check(_lib.lib().tgp_mesh_area_cdf(_p(self.verts), _p(self.faces), _p(self.vptr), _p(self.fptr), len(self),
+                                               self.verts.shape[0], self.faces.shape[0], _p(cdf), _stream(self.verts)), "tgp_mesh_area_cdf")
+            torch.cuda.current_stream(self.verts.device).synchronize()
+            self._area_cdf = cdf
+        return self._area_cdf
+
+
+def _mesh_jobs(meshset, job_mesh, what):
+    """job_mesh as a (B) int32 tensor on the mesh set's device.  A host list / array / tensor is checked against the set here; a GPU
+    tensor is not read back: an index outside the set gives status 2 and rows of zeros."""
+    import numpy as np
+    if not isinstance(meshset, MeshSet):
+        raise TypeError("%s: meshset must be an ops.MeshSet" % what)
+    dev = meshset.verts.device
+    if torch.is_tensor(job_mesh) and job_mesh.is_cuda:
+        if job_mesh.dtype != torch.int32 or not job_mesh.is_contiguous() or job_mesh.dim() != 1:
+            raise TypeError("%s: job_mesh on the GPU must be a contiguous (B) int32 tensor" % what)
+        if job_mesh.device != dev:
+            raise ValueError("%s: job_mesh is not on the mesh set's device" % what)
+        jm = job_mesh
+    else:
+        a = np.asarray(job_mesh.numpy() if torch.is_tensor(job_mesh) else job_mesh)
+        if a.size == 0:
+            raise ValueError("%s: at least one job" % what)
+        if a.ndim != 1 or a.dtype.kind not in "iu":
+            raise TypeError("%s: job_mesh must be a (B) sequence of integer mesh indices" % what)
+        if a.size and (a.min() < 0 or a.max() >= len(meshset)):
+            raise ValueError("%s: a mesh index is outside the set of %d meshes" % (what, len(meshset)))
+        jm = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+    if jm.numel() < 1:
+        raise ValueError("%s: at least one job" % what)
+    return jm
+
+
+def mesh_check_status(status, what="mesh_sample"):
+    """one read of the (B) status words; raises TgpError naming the first failed job"""
+    st = status.cpu().tolist()
+    bad = [(b, s) for b, s in enumerate(st) if s != 0]
+    if bad:
+        raise _lib.TgpError("%s: job %d failed: %s (%d of %d jobs failed)" % (what, bad[0][0], _lib.MESH_STATUS.get(bad[0][1], bad[0][1]),
+                                                                             len(bad), len(st)))
+
+
+def mesh_sample(meshset, job_mesh, n, *, u=None, keys=None, seed=0, normals=False, dtype=torch.float32, return_face=False,
+                check_status=False):
+    """Area-weighted surface samples of B jobs in one launch (tgp_mesh_sample, csrc/meshsample.hip; the reference's uniform_sample,
+    DESIGN.md section 3 "Mesh surface sampling").  job_mesh (B): each job's mesh in the set; every job draws n samples from three
+    float64 uniforms per sample: ``u`` (B,n,3) float64 on the device (row i = np.random.random(), np.random.random(2) of the
+    reference's sample i), or Philox words keyed by ``keys`` (B) 64-bit integers under ``seed`` -- exactly one of the two.
+    -> dict: points (B,n,3), or (B,n,6) [point, unit normal] with normals, float64 or rounded once to float32 (dtype); status (B)
+    int32 (0; 1: the mesh has no positive finite area; 2: no such mesh); with return_face face (B,n) int32 within the mesh.
+    Nothing synchronises unless check_status, which reads status once and raises TgpError."""
+    import numpy as np
+    jm = _mesh_jobs(meshset, job_mesh, "mesh_sample")
+    dev = meshset.verts.device
+    B, n = jm.numel(), int(n)
+    if n < 1:
+        raise ValueError("mesh_sample: n must be at least 1")
+    if (u is None) == (keys is None):
+        raise ValueError("mesh_sample: exactly one of u (host draws) and keys (device draws) is expected")
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError("mesh_sample: dtype must be torch.float32 or torch.float64")
+    if u is not None:
+        if not (torch.is_tensor(u) and u.is_cuda and u.dtype == torch.float64 and u.is_contiguous()):
+            raise TypeError("mesh_sample: u must be a contiguous float64 GPU tensor")
+        if u.device != dev:
+            raise ValueError("mesh_sample: u is not on the mesh set's device")
+        if tuple(u.shape) != (B, n, 3):
+            raise ValueError("mesh_sample: u must be (B, n, 3) = (%d, %d, 3)" % (B, n))
+        kt = None
+    else:
+        if torch.is_tensor(keys):
+            if keys.dtype != torch.int64 or not keys.is_contiguous():
+                raise TypeError("mesh_sample: keys as a tensor must be contiguous int64 (the 64-bit keys' bits)")
+            if keys.is_cuda and keys.device != dev:
+                raise ValueError("mesh_sample: keys is not on the mesh set's device")
+            kt = keys.to(dev)
+        else:
+            kt = torch.from_numpy(np.asarray([int(k) & (2 ** 64 - 1) for k in keys], dtype=np.uint64).view(np.int64)).to(dev)
+        if tuple(kt.shape) != (B,):
+            raise ValueError("mesh_sample: keys must be (B) = (%d)" % B)
+    out = {"points": torch.empty(B, n, 6 if normals else 3, device=dev, dtype=dtype), "status": torch.empty(B, device=dev, dtype=torch.int32)}
+    if return_face:
+        out["face"] = torch.empty(B, n, device=dev, dtype=torch.int32)
+    a = _lib.MeshSampleArgs(verts=_p(meshset.verts), faces=_p(meshset.faces), vptr=_p(meshset.vptr), fptr=_p(meshset.fptr),
+                            cdf=_p(meshset.area_cdf()), M=len(meshset), n_verts=meshset.verts.shape[0], n_faces=meshset.faces.shape[0],
+                            job_mesh=_p(jm), B=B, n=n, u=_p(u), keys=_p(kt), seed=int(seed) & (2 ** 64 - 1), normals=int(bool(normals)),
+                            f32=int(dtype == torch.float32), out=_p(out["points"]), face=_p(out.get("face")), status=_p(out["status"]))
+    check(_lib.lib().tgp_mesh_sample(ctypes.byref(a), _stream(meshset.verts)), "tgp_mesh_sample")
+    if check_status:
+        mesh_check_status(out["status"])
+    return out
+
+
+def mesh_sample_fps(meshset, job_mesh, n, ratio=2, *, u=None, keys=None, seed=0, normals=False, dtype=torch.float32, check_status=False):
+    """sample_points_from_mesh(fps=True): ratio * n surface samples per job (mesh_sample), thinned to the n that
+    farthest_points(init_center=False) selects from their float32 coordinates (row 0 is the first centre, as in the reference), and
+    the rows gathered in selection order -- three launches and a gather, nothing read back.  u, when given, is (B, ratio * n, 3).
+    -> dict: points (B,n,3|6), index (B,n) int32 into the ratio * n samples, status (B)."""
+    n, ratio = int(n), int(ratio)
+    if n < 1 or ratio < 1:
+        raise ValueError("mesh_sample_fps: n and ratio must be at least 1")
+    if ratio * n > fps_max_points():
+        raise ValueError("mesh_sample_fps: ratio * n = %d is above the cap of %d points" % (ratio * n, fps_max_points()))
+    dense = mesh_sample(meshset, job_mesh, ratio * n, u=u, keys=keys, seed=seed, normals=normals, dtype=dtype, check_status=check_status)
+    pts = dense["points"]
+    xyz = pts[..., :3].to(torch.float32).contiguous()
+    idx = farthest_points(xyz, n, init_center=False)
+    rows = torch.gather(pts, 1, idx.long().unsqueeze(-1).expand(-1, -1, pts.shape[-1]))
+    return {"points": rows, "index": idx, "status": dense["status"]}
 
 
 def render_max_faces():
