@@ -1231,6 +1231,55 @@ typedef struct tgp_mesh_sample_args {
 } tgp_mesh_sample_args;
 int tgp_mesh_sample(const tgp_mesh_sample_args *args, tgp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Ball crop (network/point_sample/pc_sample_sphere.py:258-280, 350-371: crop_ball_from_pts / crop_ball_from_depth_image): the
+ * pixels of a depth frame whose point lies within a ball round a pose's centre, for J jobs in one launch.  Additive: the ABI
+ * number stays.  DESIGN.md section 3 "Ball crop and tracking" is the contract; tests/ball_ref.py restates it in NumPy and the
+ * kernel agrees with it bit for bit.
+ *
+ * Job j crops frame job_img[j] round centers[j] (3 float32, metres) with the radius ladder ladder[j] (TGP_BALL_LEVELS float32,
+ * ascending: the reference's radius and its products by 1.10).  centers and ladder are DEVICE pointers.
+ *   depth (I,H,W) uint16 millimetres; camk (I,4) fx, fy, cx, cy as tgp_roi_cloud takes it; H, W < 32768, H*W < 2^24.
+ *   masks NULL: no mask.  Else mask_off (J) int64 / mask_stride (J) / mask_val (J, or NULL) address job j's mask exactly as
+ *   tgp_roi_cloud_ex addresses a detection's: byte masks[mask_off[j] + pixel * mask_stride[j]], admitted when non-zero
+ *   (mask_val NULL or 0) or when equal to mask_val[j] (> 0).
+ * A pixel is VALID when depth > 0 and the mask admits it.  Its point is the one tgp_cloud_select gives for that source pixel and
+ * depth (same bits).  d = sqrt((dx^2 + dy^2) + dz^2) against the centre, float32, each operation rounded on its own, the root
+ * correctly rounded.  The point's level is the smallest i with d <= ladder[i]; L is the first level whose cumulative count of
+ * valid pixels reaches 10, or TGP_BALL_LEVELS - 1 when none does; the crop is the valid pixels of level <= L in row-major order.
+ *   recs   (J, cap) uint32: the crop's pixel indices y*W + x, the first min(count, cap) entries written
+ *   counts (J, 4) int32: valid pixels of the frame under the mask; the crop's count (the true one, also above cap); L; status --
+ *          0 ok, 1 nothing within ladder[last] (the reference then takes every valid point: call again with a ladder of 1e9),
+ *          2 no valid pixel (the reference recurses without end), 3 job_img[j] outside [0, I) (nothing is read)
+ * full_scan = 0: distances are evaluated only inside the pixel rectangle that can hold points within ladder[last] of the centre
+ * (whole frame when the ball reaches z <= 0 or an argument is not finite); full_scan != 0: everywhere.  Same result either way.
+ * One workgroup of TGP_BALL_THREADS threads per job; a job's result does not depend on the other jobs; no float atomics.
+ * TGP_EINVAL (before any launch): a NULL required pointer, masks without mask_off / mask_stride, a size out of range, cap < 1.
+ *
+ * tgp_ball_cloud_pts: the same crop of point lists pts (I, N, 3) float32 (crop_ball_from_pts): every point is valid, a record is
+ * the point's index, N <= 2^30 - 1024. */
+#define TGP_BALL_LEVELS 10
+#define TGP_BALL_THREADS 1024
+int tgp_ball_cloud(const uint16_t *depth, const uint8_t *masks, const int64_t *mask_off, const int *mask_stride, const int *mask_val,
+                   const int *job_img, const float *centers, const float *ladder, const float *camk, int J, int I, int H, int W, int cap,
+                   int full_scan, uint32_t *recs, int *counts, tgp_stream_t stream);
+int tgp_ball_cloud_pts(const float *pts, const int *job_img, const float *centers, const float *ladder, int J, int I, int N, int cap,
+                       uint32_t *recs, int *counts, tgp_stream_t stream);
+/* The reference's selection from the crop.  With n = min(counts[j][1], cap), the reference doubles its index list until it holds
+ * n_pts entries: length n * 2^m, the first such >= n_pts, element e being entry e mod n.  tgp_ball_select: out[j][i] =
+ * point(recs[j][sel[j][i] mod n]) and pix[j][i] = that pixel index (to gather image / coord rows); sel (J, n_pts) int32 indexes
+ * the doubled list, an index outside it (or n = 0, or a record that names no pixel) gives NaNs and pix -1, never a fault.
+ * tgp_ball_sample: the same with sel[j][i] = element i of the keyed permutation of the doubled list's length that
+ * tgp_cloud_sample walks (no read-back); rows of jobs whose status is not 0 are NaN / -1.
+ * Exactly one of depth (with camk; frames (I,H,W)) and pts (lists (I,W,3), H = 1) is non-NULL.  out (J, n_pts, 3) float32,
+ * pix (J, n_pts) int32; cap, n_pts <= 2^29 (TGP_EINVAL above). */
+int tgp_ball_select(const uint32_t *recs, const int *counts, const int32_t *sel, const int *job_img, const uint16_t *depth,
+                    const float *camk, const float *pts, int J, int I, int H, int W, int cap, int n_pts, float *out, int32_t *pix,
+                    tgp_stream_t stream);
+int tgp_ball_sample(const uint32_t *recs, const int *counts, const int *job_img, const uint16_t *depth, const float *camk,
+                    const float *pts, int J, int I, int H, int W, int cap, int n_pts, uint64_t seed, float *out, int32_t *pix,
+                    tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

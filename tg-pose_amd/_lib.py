@@ -239,6 +239,7 @@ class MeshSampleArgs(ctypes.Structure):
 
 
 MESH_SITE, MESH_AREA_CHUNK = 8, 64           # TGP_MESH_SITE, TGP_MESH_AREA_CHUNK
+BALL_LEVELS, BALL_THREADS = 10, 1024         # TGP_BALL_LEVELS, TGP_BALL_THREADS
 MESH_STATUS = {1: "the mesh's total area is not a positive finite number", 2: "the mesh index or the mesh's rows are outside the set"}
 GATHER_SLOTS_MAX, DRAW_MAX_ITEMS, DRAW_MAX_TOTAL = 24, 4096, 65536
 SITE_HOST, SITE_BAND, SITE_SEL2K, SITE_SEL1K, SITE_DEFOR, SITE_NOISE, SITE_DROP, SITE_SHUFFLE = range(8)
@@ -410,6 +411,10 @@ SIGNATURES = {
     "tgp_gather_slots": (c_int, [ctypes.POINTER(GatherSlotsArgs), c_vp]),
     "tgp_mesh_area_cdf": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
     "tgp_mesh_sample": (c_int, [ctypes.POINTER(MeshSampleArgs), c_vp]),
+    "tgp_ball_cloud": (c_int, [c_vp] * 9 + [c_int] * 6 + [c_vp, c_vp, c_vp]),
+    "tgp_ball_cloud_pts": (c_int, [c_vp] * 4 + [c_int] * 4 + [c_vp, c_vp, c_vp]),
+    "tgp_ball_select": (c_int, [c_vp] * 7 + [c_int] * 6 + [c_vp, c_vp, c_vp]),
+    "tgp_ball_sample": (c_int, [c_vp] * 6 + [c_int] * 6 + [c_u64, c_vp, c_vp, c_vp]),
 }
 
 ABI_VERSION = 8

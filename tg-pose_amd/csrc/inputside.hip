@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "tgp_common.h"
+#include "pixel_point.h"
 
 #define ROI_THREADS 1024
 #define ROI_WAVES (ROI_THREADS / TGP_WAVE)
@@ -111,26 +112,6 @@ __device__ __forceinline__ float wave_max(float v)
     return v;
 }
 
-// x / b for a divisor that is uniform over the launch: the refined reciprocal of the compiler's IEEE division sequence
-// (v_rcp_f32 + one Newton step) is computed once, and each quotient is that sequence's remaining five operations --
-// q = a*r; q += fma(-b,q,a)*r; q += fma(-b,q,a)*r -- i.e. exactly what `a / b` compiles to when v_div_scale / v_div_fixup
-// are no-ops (operands far from overflow / denormals: pixel coordinates x millimetres over focal lengths and 1000).
-// Correctly rounded there; the parity tests compare bit patterns with numpy's division over ~10^6 quotients.
-struct UniformDiv {
-    float b, r;
-    __device__ __forceinline__ explicit UniformDiv(float divisor) : b(divisor)
-    {
-        const float r0 = __builtin_amdgcn_rcpf(divisor);
-        r = fmaf(fmaf(-divisor, r0, 1.0f), r0, r0);
-    }
-    __device__ __forceinline__ float operator()(float a) const
-    {
-        float q = a * r;
-        q = fmaf(fmaf(-b, q, a), r, q);
-        return fmaf(fmaf(-b, q, a), r, q);
-    }
-};
-
 // A detection's geometry: everything a record needs to become a point (load_data_eval.py:451-462 then /1000.0 at :338,
 // float32 step by step, correctly rounded quotients).
 //
@@ -156,9 +137,7 @@ struct RoiGeom {
     {
         const int p = (int)(rec >> 16), x = p & ((1 << roi_log2) - 1), y = p >> roi_log2;
         const float dep = (float)(rec & 0xffffu);
-        px = div_k(div_fx(((float)src_x(x) - cx) * dep));
-        py = div_k(div_fy(((float)src_y(y) - cy) * dep));
-        pz = div_k(dep);
+        tgp_pixel_point(src_x(x), src_y(y), dep, cx, cy, div_fx, div_fy, div_k, px, py, pz);
     }
 };
 
@@ -579,25 +558,6 @@ extern "C" int tgp_cloud_select(const uint32_t *recs, const int32_t *sel, const 
 // halves), cycle-walked into [0, total), gives element i of a pseudo-random permutation of the cloud statelessly; the
 // first n_pts elements are the sample.  Same distribution family as np.random.permutation(total)[:n_pts] (a uniformly
 // chosen ordered subset), not the same draw; a cloud shorter than n_pts is tiled exactly as the reference tiles it.
-__device__ __forceinline__ uint32_t mix32(uint32_t x)
-{
-    x ^= x >> 16, x *= 0x7feb352du, x ^= x >> 15, x *= 0x846ca68bu, x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ uint32_t feistel(uint32_t v, int half_bits, uint32_t key)
-{
-    const uint32_t mask = (1u << half_bits) - 1u;
-    uint32_t l = v >> half_bits, r = v & mask;
-#pragma unroll
-    for (int round = 0; round < 4; ++round) {
-        const uint32_t f = mix32(r ^ (key + 0x9e3779b9u * (round + 1))) & mask;
-        const uint32_t nl = r;
-        r = l ^ f;
-        l = nl;
-    }
-    return (l << half_bits) | r;
-}
-
 __global__ void cloud_sample_kernel(const uint32_t *__restrict__ recs, const int *__restrict__ counts, const int *__restrict__ det_img,
                                     const int *__restrict__ window, const float *__restrict__ camk, int64_t total_out, int roi_log2, int n_pts,
                                     uint64_t seed, float *__restrict__ out)
@@ -614,7 +574,7 @@ __global__ void cloud_sample_kernel(const uint32_t *__restrict__ recs, const int
         } else {
             int half_bits = 1;
             while ((1u << (2 * half_bits)) < (uint32_t)total) ++half_bits;
-            const uint32_t key = mix32((uint32_t)seed ^ mix32((uint32_t)(seed >> 32) + 0x632be5abu * (uint32_t)(j + 1)));
+            const uint32_t key = tgp_sample_key(seed, j);
             k = feistel((uint32_t)i, half_bits, key);
             while (k >= (uint32_t)total) k = feistel(k, half_bits, key);      // a bijection of [0, 2^2h): the walk returns
         }

@@ -169,6 +169,70 @@ class myEvaluater:
         self.net1.graph_replay = was
         return results
 
+    def track(self, sequence, init, camK=lde.REAL_INTRINSICS, ratio=None, n_pts=1024, sampler=None, use_mask=True):
+        """Follow objects through a depth sequence from their previous poses: no detector result after frame 0.
+
+        sequence: iterable of frames {'depth' (H,W) uint16[, 'inst_mask' (H,W) uint8]}.  init: {'class_ids' (n,) 1-based category
+        ids, 'RTs' (n,4,4), 'scales' (n,3)[, 'inst_ids' (n,)]} -- ground truth, or what ``run`` returned for frame 0; with inst_ids
+        (and use_mask, and an 'inst_mask' in the frame) object k only sees the pixels whose mask byte is inst_ids[k].  ratio: the
+        crop ball's radius over |RT[:3,:3] @ scale| (load_data_eval.pose_balls); required.  sampler: 'device' (keyed draw, seed =
+        self.seed + frame number) or 'fps'; default: this evaluater's when it is one of the two, else 'device'.
+
+        Per frame: one ball launch for all objects (load_data_eval.clouds_from_poses), the sampling, one forward
+        (pose.infer_device).  Frame t's centres and radii are frame t-1's device outputs; nothing is read back between frames, and
+        the results are fetched on the fetch stream, frame t-1's after frame t has been enqueued (``overlap``).  An object whose
+        crop status is not 0 (1: nothing within the last radius; 2: no valid pixel) keeps its previous pose and is flagged.
+        Each forward draws its pooling samples from torch's global CPU generator, as every forward of the network does: seed it for
+        repeatable poses.
+        -> list over frames of {'pred_RTs' (n,4,4), 'pred_scales' (n,3), 'status' (n,) int32, 'tracked' (n,) bool} ndarrays."""
+        if ratio is None:
+            raise ValueError("track: ratio is required (the reference fixes none)")
+        sampler = sampler or (self.sampler if self.sampler in ("device", "fps") else "device")
+        if sampler not in ("device", "fps"):
+            raise ValueError("track: sampler must be 'device' or 'fps' (nothing is read back between frames)")
+        dev = self.device
+        ids = np.asarray(init["class_ids"]).astype(np.int64)
+        n = len(ids)
+        t = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float32)).to(dev)
+        cat = t(ids - 1).reshape(-1, 1)
+        mean = t([MEAN_SHAPE_MM[int(c)] for c in ids]).reshape(-1, 3) / 1000.0
+        sym = t([SYM_INFO[int(c)] for c in ids]).reshape(-1, 4)
+        rts, scales = t(init["RTs"]).reshape(n, 4, 4), t(init["scales"]).reshape(n, 3)
+        inst_ids = init.get("inst_ids") if use_mask else None
+        job_img = torch.zeros(n, dtype=torch.int32, device=dev)
+        results, pending = [], None
+
+        def fetch(item):
+            r, s, st, done = item
+            with torch.cuda.stream(self._fetch):
+                self._fetch.wait_event(done)
+                for x in (r, s, st):
+                    x.record_stream(self._fetch)
+                r, s, st = r.cpu().numpy(), s.cpu().numpy(), st.cpu().numpy()
+            results.append(dict(pred_RTs=r, pred_scales=s, status=st, tracked=st == 0))
+        for k, frame in enumerate(sequence):
+            masks = inst_ids if inst_ids is not None and "inst_mask" in frame else None
+            with torch.no_grad():
+                pts, ok, _, counts = lde.clouds_from_poses([frame], job_img, rts, scales, ratio, camK, n_pts=n_pts, sampler=sampler,
+                                                           masks=masks, seed=self.seed + k, fps_pool=self.fps_pool, device=dev,
+                                                           return_counts=True)
+                new_rts, new_scales = infer_device(self.net1, torch.nan_to_num(pts, nan=0.0), cat, mean, sym, self.max_batch,
+                                                   eval_outputs_only=self.eval_outputs_only)
+                rts = torch.where(ok[:, None, None], new_rts, rts)
+                scales = torch.where(ok[:, None], new_scales, scales)
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(dev))
+            item = (rts, scales, counts[:, 3].contiguous(), done)
+            if pending is not None:
+                fetch(pending)
+            pending = item
+            if not self.overlap:
+                fetch(pending)
+                pending = None
+        if pending is not None:
+            fetch(pending)
+        return results
+
 
 def calc_pose_metric(pred_results, output_path, per_obj=""):
     """:111-175 -- the mAP tables and the lines the reference logs (degree 0..60, shift 0..10 cm by 0.5, IoU 0..1 by 0.01)."""

@@ -203,3 +203,109 @@ def clouds_from_frames(frames, camK=REAL_INTRINSICS, img_size=256, n_pts=1024, s
         d += n
     out = ops.cloud_select(rc.records, torch.from_numpy(sel).to(dev))
     return [c if alive else None for c, alive in zip(out.split(rc.per_frame), keep_frame)]
+
+
+# ------------------------------------------------------------------------------------------------ clouds from poses (the ball crop)
+def pose_balls(RTs, scales, ratio):
+    """The balls crop_ball_from_depth_image (network/point_sample/pc_sample_sphere.py:350-357) crops round poses: centres = the
+    translations, radius = ratio * |RT[:3, :3] @ scale|, and the ten radii its loop tests (ops.ball_ladder).  RTs (J,4,4) or
+    (J,3,4), scales (J,3) device tensors -> (centers (J,3), ladder (J,10)); device ops only, nothing is read back."""
+    RTs, scales = RTs.float(), scales.float()
+    radius = torch.linalg.vector_norm(torch.bmm(RTs[:, :3, :3], scales[:, :, None])[:, :, 0], dim=1) * float(ratio)
+    return RTs[:, :3, 3].contiguous(), ops.ball_ladder(radius)
+
+
+def _depth_frames(frames, camK, dev):
+    """frames: a list of {'depth' (H,W) uint16[, 'inst_mask' (H,W) uint8]} host records, or one dict of device tensors {'depth'
+    (I,H,W) 16-bit[, 'inst_mask' (I,H,W) uint8]} -> (depth (I,H,W), inst (I,H,W) uint8 or None, camk (I,4)) on the device"""
+    if isinstance(frames, dict):
+        depth, inst = frames["depth"], frames.get("inst_mask")
+    else:
+        H, W = frames[0]["depth"].shape
+        for fr in frames:
+            if fr["depth"].shape != (H, W) or fr["depth"].dtype != np.uint16:
+                raise ValueError("every frame needs a uint16 depth image of one common (H,W)")
+        depth = torch.from_numpy(np.stack([fr["depth"] for fr in frames]).view(np.int16)).to(dev, non_blocking=True)
+        inst = None
+        if all("inst_mask" in fr for fr in frames):
+            inst = torch.from_numpy(np.stack([np.ascontiguousarray(fr["inst_mask"]).view(np.uint8) for fr in frames])).to(dev, non_blocking=True)
+    I = depth.shape[0]
+    if inst is not None and (inst.shape != depth.shape or inst.dtype not in (torch.uint8, torch.bool)):
+        raise ValueError("inst_mask must be a byte image per frame, of the depth's (H,W)")
+    camK = np.asarray(camK, dtype=np.float32)
+    camK = np.broadcast_to(camK, (I, 3, 3)) if camK.ndim == 2 else camK
+    camk = np.stack([camK[:, 0, 0], camK[:, 1, 1], camK[:, 0, 2], camK[:, 1, 2]], axis=1).astype(np.float32)
+    return depth, inst, torch.from_numpy(np.ascontiguousarray(camk)).to(dev, non_blocking=True)
+
+
+def _ball_fps(br, n_pts, fps_pool):
+    """sampler='fps' on ball crops, as _fps_clouds on ROI crops: the candidates are the crop's doubled list (the crop itself when it
+    holds n_pts), thinned evenly to fps_pool entries when longer, gathered by tgp_ball_select; tgp_fps with per-job counts.  On a
+    doubled list that returns the distinct points once and then the list's row 0, as the reference's farthest_points does."""
+    dev = br.recs.device
+    m = int(fps_pool)
+    n = br.counts[:, 1].long().clamp(min=0, max=br.cap)
+    ok = (br.counts[:, 3] == 0) & (n > 0)
+    total = n.clamp(min=1)
+    for _ in range(max(0, int(n_pts - 1).bit_length())):            # count * 2^m, the first >= n_pts: at most log2(n_pts) doublings
+        total = torch.where(total < n_pts, total * 2, total)
+    cand = torch.where(ok, total.clamp(max=m), torch.zeros_like(total))
+    i = torch.arange(m, device=dev, dtype=torch.int64)[None, :]
+    sel = torch.where((total > m)[:, None], (i * total[:, None]) // m, i)
+    sel = torch.where(i < cand[:, None], sel, torch.full_like(sel, -1)).int()
+    pts, pix = ops.ball_select(br, sel)        # a list doubled up to fps_pool entries holds the one doubled up to n_pts
+    idx = ops.farthest_points(pts, n_pts, counts=cand.clamp(min=1).int()).long()
+    return torch.gather(pts, 1, idx[:, :, None].expand(-1, -1, 3)), torch.gather(pix, 1, idx), ok
+
+
+def clouds_from_poses(frames, job_img, RTs, scales, ratio, camK=REAL_INTRINSICS, n_pts=1024, sampler="device", masks=None, seed=0,
+                      fps_pool=4096, device="cuda", cap=None, full_scan=False, return_counts=False):
+    """The other way into the network: job j's cloud is cut out of depth frame job_img[j] by a ball round pose (RTs[j], scales[j]) --
+    crop_ball_from_depth_image (pc_sample_sphere.py:350-371) for all jobs in one launch (ops.ball_cloud), with no detector result.
+    frames as _depth_frames takes them; RTs (J,4,4) / scales (J,3) tensors or arrays (device tensors stay there: in tracking they
+    are the previous forward's outputs); ratio: the ball's radius over |RT[:3,:3] @ scale| (the reference fixes none).
+    masks: None, or per job the instance id whose pixels of the frame's 'inst_mask' are admitted (0: any non-zero byte).
+    sampler: 'device' the keyed draw of tgp_ball_sample (seed); 'fps' farthest point sampling (fps_pool candidates at most);
+    'torch' the reference's torch.randperm draws from torch's CPU generator, job by job -- the only one that reads the counts back.
+    -> (clouds (J,n_pts,3), ok (J,) bool, pix (J,n_pts) int32 source pixels: gather image / coord rows with them)[, counts (J,4)].
+    A job whose status (counts[:, 3]) is not 0 -- nothing within the last radius, no valid pixel -- has NaN rows, pix -1, ok False;
+    the reference's fall-back to every valid point is crop_ball_from_pts' business, not this function's."""
+    if sampler not in ("device", "fps", "torch"):
+        raise ValueError("sampler must be 'device', 'fps' or 'torch'")
+    if sampler == "fps" and not n_pts <= int(fps_pool) <= ops.fps_max_points():
+        raise ValueError("fps_pool must be in [n_pts, %d] (ops.fps_max_points())" % ops.fps_max_points())
+    dev = torch.device(device)
+    depth, inst, camk = _depth_frames(frames, camK, dev)
+    I, H, W = depth.shape
+    job_img = torch.as_tensor(job_img, dtype=torch.int32).to(dev).contiguous()
+    J = job_img.numel()
+    RTs = torch.as_tensor(RTs).to(dev)
+    scales = torch.as_tensor(scales).to(dev)
+    if RTs.shape[0] != J or scales.shape != (J, 3):
+        raise ValueError("clouds_from_poses: RTs (J,4,4) and scales (J,3) are needed for the J jobs")
+    centers, ladder = pose_balls(RTs, scales, ratio)
+    kw = {}
+    if masks is not None:
+        if inst is None:
+            raise ValueError("clouds_from_poses: masks need an 'inst_mask' in every frame")
+        kw = dict(masks=inst.reshape(-1), mask_off=job_img.long() * (H * W), mask_stride=torch.ones_like(job_img),
+                  mask_val=torch.as_tensor(masks, dtype=torch.int32).to(dev).contiguous())
+    br = ops.ball_cloud(depth, job_img, centers, ladder, camk, cap=cap, full_scan=full_scan, **kw)
+    if sampler == "device":
+        out, pix = ops.ball_sample(br, n_pts, seed)
+        ok = br.counts[:, 3] == 0
+    elif sampler == "fps":
+        out, pix, ok = _ball_fps(br, n_pts, fps_pool)
+    else:
+        counts = br.counts.cpu().numpy()                     # the one read-back: 16 bytes per job
+        sel = np.full((J, n_pts), -1, dtype=np.int32)
+        for j in range(J):
+            n = min(int(counts[j, 1]), br.cap)
+            if counts[j, 3] == 0 and n > 0:
+                total = n
+                while total < n_pts:
+                    total *= 2
+                sel[j] = torch.randperm(total)[:n_pts].numpy()
+        out, pix = ops.ball_select(br, torch.from_numpy(sel).to(dev))
+        ok = br.counts[:, 3] == 0
+    return (out, ok, pix, br.counts) if return_counts else (out, ok, pix)

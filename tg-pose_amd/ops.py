@@ -2015,6 +2015,143 @@ def cloud_sample(rr, n_pts, seed, counts=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------- ball crop (depth frame + pose -> cloud)
+BALL_LEVELS, BALL_THREADS = _lib.BALL_LEVELS, _lib.BALL_THREADS
+
+
+class BallRecords:
+    """What tgp_ball_cloud leaves in HBM: ``recs`` (J, cap) int32-viewed pixel (or point) indices in row-major order, ``counts``
+    (J,4) int32 = valid pixels of the frame, the crop's true count, the ladder level L, status (0 ok, 1 nothing within the last
+    radius, 2 no valid pixel, 3 bad frame index), and what a record needs to become a point: ``job_img`` and either ``depth`` +
+    ``camk`` or the point lists ``pts`` (I,N,3)."""
+
+    def __init__(self, recs, counts, job_img, depth=None, camk=None, pts=None):
+        self.recs, self.counts, self.job_img, self.depth, self.camk, self.pts = recs, counts, job_img, depth, camk, pts
+
+    @property
+    def cap(self):
+        return self.recs.shape[1]
+
+    def _src(self):
+        """(depth, camk, pts, I, H, W) as tgp_ball_select takes them"""
+        if self.pts is not None:
+            return None, None, self.pts, self.pts.shape[0], 1, self.pts.shape[1]
+        return (self.depth, self.camk, None) + tuple(self.depth.shape)
+
+
+def ball_ladder(radius):
+    """The ten radii crop_ball_from_pts (pc_sample_sphere.py:260-265) tests, for radius (J,) float32 -> (J,10) float32, as torch
+    ops on the radius' device (no read-back).  The reference keeps a tensor radius >= 0.05 and multiplies it in place by 1.10
+    (float32 products); a smaller one becomes the Python float 0.05, whose products are doubles, rounded to float32 when compared."""
+    if not (torch.is_tensor(radius) and radius.dtype == torch.float32 and radius.dim() == 1):
+        raise TypeError("ball_ladder: radius must be a (J,) float32 tensor")
+    rungs, r = [], radius
+    for _ in range(BALL_LEVELS):
+        rungs.append(r)
+        r = r * 1.10
+    small, s = [], 0.05
+    for _ in range(BALL_LEVELS):
+        small.append(s)
+        s *= 1.10
+    small = torch.tensor(small, dtype=torch.float64).to(torch.float32).to(radius.device)
+    return torch.where((radius < 0.05)[:, None], small[None, :], torch.stack(rungs, 1)).contiguous()
+
+
+def _ball_jobs(job_img, centers, ladder, cap, who):
+    _i32(job_img, "job_img"), _f32(centers, "centers"), _f32(ladder, "ladder")
+    J = job_img.numel()
+    if J < 1 or job_img.dim() != 1 or centers.shape != (J, 3) or ladder.shape != (J, BALL_LEVELS):
+        raise ValueError("%s: job_img (J,), centers (J,3) and ladder (J,%d) are needed, J >= 1" % (who, BALL_LEVELS))
+    if not (centers.is_contiguous() and ladder.is_contiguous()):
+        raise ValueError("%s: centers and ladder must be contiguous" % who)
+    if not (isinstance(cap, int) and 1 <= cap <= 2 ** 29):
+        raise ValueError("%s: cap must be an int in [1, 2^29]" % who)
+    return J
+
+
+def ball_cloud(depth, job_img, centers, ladder, camk, cap=None, masks=None, mask_off=None, mask_stride=None, mask_val=None,
+               full_scan=False):
+    """tgp_ball_cloud: job j crops frame job_img[j] of depth (I,H,W) (int16-viewed uint16 millimetres) round centers[j] with the radii
+    ladder[j] (ball_ladder).  masks (flat uint8 / bool) with mask_off (J,) int64, mask_stride (J,) int32 and optionally mask_val (J,)
+    int32 address a mask per job as roi_cloud does; None: no mask.  cap: records kept per job (default H*W).  full_scan: evaluate
+    every pixel instead of the ball's rectangle (same result; for tests).  -> BallRecords"""
+    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in (torch.int16, torch.uint16) and depth.dim() == 3
+            and depth.is_contiguous()):
+        raise TypeError("depth must be a contiguous (I,H,W) 16-bit GPU tensor")
+    I, H, W = depth.shape
+    cap = H * W if cap is None else cap
+    J = _ball_jobs(job_img, centers, ladder, cap, "ball_cloud")
+    if _f32(camk, "camk", 2).shape != (I, 4) or not camk.is_contiguous():
+        raise ValueError("ball_cloud: camk must be a contiguous (I,4) tensor")
+    if masks is not None:
+        if not (masks.is_cuda and masks.dtype in (torch.uint8, torch.bool) and masks.is_contiguous()):
+            raise TypeError("masks must be a contiguous uint8 / bool GPU tensor")
+        if mask_off is None or mask_stride is None:
+            raise ValueError("ball_cloud: masks need mask_off and mask_stride")
+        if not (mask_off.is_cuda and mask_off.dtype == torch.int64 and mask_off.is_contiguous()):
+            raise TypeError("mask_off must be a contiguous int64 GPU tensor")
+        if mask_off.numel() != J or _i32(mask_stride, "mask_stride").numel() != J:
+            raise ValueError("ball_cloud: mask_off and mask_stride must be (J,)")
+        if mask_val is not None and _i32(mask_val, "mask_val").numel() != J:
+            raise ValueError("ball_cloud: mask_val must be (J,)")
+    elif mask_off is not None or mask_stride is not None or mask_val is not None:
+        raise ValueError("ball_cloud: mask_off / mask_stride / mask_val without masks")
+    recs = torch.empty(J, cap, device=depth.device, dtype=torch.int32)
+    counts = torch.empty(J, 4, device=depth.device, dtype=torch.int32)
+    check(_lib.lib().tgp_ball_cloud(_p(depth), _p(masks), _p(mask_off), _p(mask_stride), _p(mask_val), _p(job_img), _p(centers),
+                                    _p(ladder), _p(camk), J, I, H, W, cap, int(bool(full_scan)), _p(recs), _p(counts), _stream(depth)),
+          "tgp_ball_cloud")
+    return BallRecords(recs, counts, job_img, depth=depth, camk=camk)
+
+
+def ball_cloud_pts(pts, job_img, centers, ladder, cap=None):
+    """tgp_ball_cloud_pts: the crop of point lists pts (I,N,3) float32 (crop_ball_from_pts); records are point indices -> BallRecords"""
+    if _f32(pts, "pts", 3).shape[2] != 3 or not pts.is_contiguous() or pts.shape[1] < 1:
+        raise ValueError("ball_cloud_pts: pts must be a contiguous (I,N,3) tensor, N >= 1")
+    I, N = pts.shape[:2]
+    cap = N if cap is None else cap
+    J = _ball_jobs(job_img, centers, ladder, cap, "ball_cloud_pts")
+    recs = torch.empty(J, cap, device=pts.device, dtype=torch.int32)
+    counts = torch.empty(J, 4, device=pts.device, dtype=torch.int32)
+    check(_lib.lib().tgp_ball_cloud_pts(_p(pts), _p(job_img), _p(centers), _p(ladder), J, I, N, cap, _p(recs), _p(counts), _stream(pts)),
+          "tgp_ball_cloud_pts")
+    return BallRecords(recs, counts, job_img, pts=pts)
+
+
+def ball_select(br, sel):
+    """tgp_ball_select: sel (J,n_pts) int32 indexes the crop's doubled list (length count * 2^m >= n_pts, element e = entry
+    e mod count) -> (points (J,n_pts,3) float32, pix (J,n_pts) int32); an index outside the list gives NaNs and -1"""
+    _i32(sel, "sel")
+    J = br.recs.shape[0]
+    if sel.dim() != 2 or sel.shape[0] != J or sel.shape[1] < 1:
+        raise ValueError("ball_select: sel must be (J,n_pts)")
+    n_pts = sel.shape[1]
+    depth, camk, pts, I, H, W = br._src()
+    out = torch.empty(J, n_pts, 3, device=br.recs.device, dtype=torch.float32)
+    pix = torch.empty(J, n_pts, device=br.recs.device, dtype=torch.int32)
+    check(_lib.lib().tgp_ball_select(_p(br.recs), _p(br.counts), _p(sel), _p(br.job_img), _p(depth), _p(camk), _p(pts), J, I, H, W,
+                                     br.cap, n_pts, _p(out), _p(pix), _stream(br.recs)), "tgp_ball_select")
+    return out, pix
+
+
+def ball_sample(br, n_pts, seed, counts=None):
+    """tgp_ball_sample: the first n_pts of the keyed permutation of each crop's doubled list, drawn on the device -> (points
+    (J,n_pts,3), pix (J,n_pts)); rows of jobs whose status is not 0 are NaN / -1.  ``counts`` overrides br.counts (tests)."""
+    counts = br.counts if counts is None else _i32(counts, "counts")
+    J = br.recs.shape[0]
+    if counts.shape != (J, 4):
+        raise ValueError("ball_sample: counts must be (J,4)")
+    if not (isinstance(n_pts, int) and 1 <= n_pts <= 2 ** 29):
+        raise ValueError("ball_sample: n_pts must be an int in [1, 2^29]")
+    depth, camk, pts, I, H, W = br._src()
+    out = torch.empty(J, n_pts, 3, device=br.recs.device, dtype=torch.float32)
+    pix = torch.empty(J, n_pts, device=br.recs.device, dtype=torch.int32)
+    check(_lib.lib().tgp_ball_sample(_p(br.recs), _p(counts), _p(br.job_img), _p(depth), _p(camk),
+                                     _p(pts), J, I, H, W, br.cap, n_pts, int(seed) & (2 ** 64 - 1), _p(out), _p(pix),
+                                     _stream(br.recs)), "tgp_ball_sample")
+    return out, pix
+
+
 # ---------------------------------------------------------------------------------------------------------- the optimizer step
 def ranger_plan(table):
     """Check a host descriptor table (a ctypes array of _lib.RangerTensor) and fill its unit0 fields (tgp_ranger_plan, host only:
