@@ -3,7 +3,6 @@ contract (tests/ball_ref.py) against what the reference itself returned (tests/g
 tests/golden/make_ball_crop_golden.py), the two branches of the radius ladder, the C ABI of the new entry points, their argument
 errors (which return before any launch) and the host-only helpers."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,7 +12,6 @@ from tests import ball_ref as br
 from tests import fps_ref
 from tests.util import ROOT
 
-NEW = ("tgp_ball_cloud", "tgp_ball_cloud_pts", "tgp_ball_select", "tgp_ball_sample")
 NUM = 64
 _FX = {}
 
@@ -141,15 +139,11 @@ def test_ladder_branches_equal_the_reference():
 
 
 def test_new_symbols_are_declared_bound_and_exported():
+    """the ABI number, the ball constants against the NumPy restatement's, and the Python surface; tests/test_abi_cpu.py holds every
+    symbol, type and value against the header"""
     from tgpose_amd import _lib, ops
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tgpose.h")).read(), flags=re.S)
-    h = _lib.lib()
-    for n in NEW:
-        assert re.search(r"\b%s\s*\(" % n, text), n
-        assert n in _lib.SIGNATURES and hasattr(h, n)
-    assert h.tgp_version() == _lib.ABI_VERSION                      # additive: the ABI number stays
-    consts = dict(re.findall(r"#define (TGP_BALL_[A-Z0-9_]+) (\d+)", text))
-    assert consts == {"TGP_BALL_LEVELS": "10", "TGP_BALL_THREADS": "1024"}
+    assert _lib.lib().tgp_version() == _lib.ABI_VERSION             # additive: the ABI number stays
+    assert {k: v for k, v in _lib.CONSTANTS.items() if k.startswith("BALL_")} == {"BALL_LEVELS": 10, "BALL_THREADS": 1024}
     assert _lib.BALL_LEVELS == br.LEVELS == ops.BALL_LEVELS == 10 and _lib.BALL_THREADS == br.THREADS == 1024
     for name in ("ball_cloud", "ball_cloud_pts", "ball_select", "ball_sample", "ball_ladder", "BallRecords"):
         assert hasattr(ops, name), name

@@ -1,15 +1,13 @@
 """EMD / F-score without a GPU: the numpy restatement of the EMD contract (tests/emd_ref.py) against exact matching, the
 tie rule, fscore and the eval_recon aggregation against the reference's recorded numbers (tests/golden/emd.npz), the C ABI."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from tests import emd_ref
-from tests.util import ROOT, golden, synth_eval_results
+from tests.util import golden, synth_eval_results
 
 SYNSET = ['BG', 'bottle', 'bowl', 'camera', 'can', 'laptop', 'mug']
 
@@ -119,12 +117,8 @@ def test_recon_statistics_equal_reference():
 
 
 def test_emd_abi():
-    """the four symbols are declared in the header, bound, exported; argument errors launch nothing (no GPU is touched)"""
+    """the caps, and argument errors launch nothing (no GPU is touched); tests/test_abi_cpu.py holds the symbols against the header"""
     from tgpose_amd import _lib
-    names = ("tgp_emd_fwd", "tgp_emd_bwd", "tgp_emd_workspace_bytes", "tgp_emd_max_points")
-    header = open(os.path.join(ROOT, "include", "tgpose.h")).read()
-    for nm in names:
-        assert re.search(r"\b%s\s*\(" % nm, header) and nm in _lib.SIGNATURES
     lib = _lib.lib()
     assert lib.tgp_version() == 8 and _lib.ABI_VERSION == 8
     cap = lib.tgp_emd_max_points()
