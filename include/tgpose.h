@@ -1280,6 +1280,53 @@ int tgp_ball_sample(const uint32_t *recs, const int *counts, const int *job_img,
                     const float *pts, int J, int I, int H, int W, int cap, int n_pts, uint64_t seed, float *out, int32_t *pix,
                     tgp_stream_t stream);
 
+/* ---- ICP pose refinement (csrc/icp.hip; additive, ABI stays 8) -------------------------------------------------------------------
+ * Registration of point-and-normal models to observed clouds: J jobs in ONE launch, one workgroup per job, every iteration inside
+ * the kernel.  No reference counterpart.  DESIGN.md section 3 "ICP refinement and model-based tracking" is the contract;
+ * tests/icp_ref.py restates it in NumPy.  A job's result depends on neither the other jobs nor J; no float atomics: bit-repeatable.
+ *
+ * models (M, m_cap, 6) float32 [point, unit normal] in model units (tgp_mesh_sample's normals layout); model_count (M) int32 or NULL
+ * (= m_cap), 1 <= count <= m_cap <= TGP_ICP_MAX_POINTS.  src (J, n_cap, 3) float32 camera-frame metres; src_count (J) int32 or NULL
+ * (= n_cap), 0 <= count <= n_cap <= TGP_ICP_MAX_POINTS; a point with a non-finite coordinate is never an inlier.  job_model (J).
+ * Start pose R (J,3,3), t (J,3), s (J): the similarity x = s R y + t from model to camera.  max_dist (J): the gate in metres.
+ * mode 0 point-to-point (with_scale: Umeyama's scale), 1 point-to-plane; iters >= 1 the cap; tol_rot (radians) / tol_trans (metres):
+ * the job stops after an iteration whose update is within both (both 0: exactly `iters` iterations); min_inliers (at least 6 is
+ * enforced).  The state (R, t, s) is float64 throughout.  Per iteration:
+ *   q_i = float32(R^T (p_i - t) / s), float64 arithmetic rounded once; the nearest model point y_j by tgp_nn1's float32 arithmetic
+ *   (|q|^2, |y|^2 as three rounded products summed left to right, the inner product one product and two fmaf, (yy + qq) - 2 inner,
+ *   first index on ties); an inlier when that value <= float32((max_dist / s)^2) and p_i is finite; fewer than min_inliers: status 1,
+ *   the pose stays; mode 0: the closed-form similarity of the pairs (y_j, p_i) (Horn's quaternion of the centred cross-covariance);
+ *   mode 1: one Gauss-Newton step on sum (n_j . (q_i + w x q_i + v - y_j))^2, damping 1e-9 trace(A) / 6, Cholesky (a non-positive
+ *   pivot or a non-finite step: status 2, the pose stays), R <- R exp(w)^T, t <- t - s R v.
+ * After the last iteration one more correspondence pass runs at the final pose.
+ * -> R_out, t_out, s_out: the state rounded once; info (J,4) int32: status (0 ok, 1 too few inliers, 2 singular, 3 job_model or a
+ * count out of range: nothing is read, the pose is copied through), final inliers, iterations done, 0; rmse (J): root mean square
+ * of s |q_i - y_j| over the final inliers, NaN without any; corr (J, n_cap) int32 or NULL: the final pass's model index per source
+ * point, -1 for a non-inlier and beyond src_count.
+ * TGP_EINVAL (before any launch): a NULL required pointer, a size < 1, iters < 1, a mode outside 0 / 1, with_scale with mode 1.
+ * TGP_EUNSUPPORTED: a cap above TGP_ICP_MAX_POINTS, J > 65535. */
+#define TGP_ICP_MAX_POINTS 2048
+typedef struct tgp_icp_args {
+    const float *models;
+    const int32_t *model_count;     /* may be NULL */
+    int M, m_cap;
+    const float *src;
+    const int32_t *src_count;       /* may be NULL */
+    const int32_t *job_model;
+    int J, n_cap;
+    const float *R, *t, *s;
+    const float *max_dist;
+    int mode, with_scale, iters;
+    float tol_rot, tol_trans;
+    int min_inliers;
+    float *R_out, *t_out, *s_out;
+    int32_t *info;
+    float *rmse;
+    int32_t *corr;                  /* may be NULL */
+} tgp_icp_args;
+int tgp_icp_max_points(void);
+int tgp_icp_refine(const tgp_icp_args *args, tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

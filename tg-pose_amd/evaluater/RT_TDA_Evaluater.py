@@ -21,7 +21,7 @@ import torch
 from ..evaluation import load_data_eval as lde
 from ..evaluation.metrics import compute_degree_cm_mAP
 from ..losses.utils_v2.model_utils import calc_cd, calc_emd
-from ..pose import infer_device
+from ..pose import IcpRefine, infer_device
 
 SYNSET_NAMES = ['BG', 'bottle', 'bowl', 'camera', 'can', 'laptop', 'mug']                                   # :115
 MEAN_SHAPE_MM = {1: (87, 220, 89), 2: (165, 80, 165), 3: (88, 128, 156), 4: (68, 146, 72), 5: (346, 200, 335), 6: (146, 83, 114)}
@@ -169,7 +169,8 @@ class myEvaluater:
         self.net1.graph_replay = was
         return results
 
-    def track(self, sequence, init, camK=lde.REAL_INTRINSICS, ratio=None, n_pts=1024, sampler=None, use_mask=True):
+    def track(self, sequence, init, camK=lde.REAL_INTRINSICS, ratio=None, n_pts=1024, sampler=None, use_mask=True, refine=None,
+              init_from="net"):
         """Follow objects through a depth sequence from their previous poses: no detector result after frame 0.
 
         sequence: iterable of frames {'depth' (H,W) uint16[, 'inst_mask' (H,W) uint8]}.  init: {'class_ids' (n,) 1-based category
@@ -184,9 +185,22 @@ class myEvaluater:
         crop status is not 0 (1: nothing within the last radius; 2: no valid pixel) keeps its previous pose and is flagged.
         Each forward draws its pooling samples from torch's global CPU generator, as every forward of the network does: seed it for
         repeatable poses.
+
+        refine (a pose.IcpRefine: models, job_model, max_dist and ops.icp_refine's keywords): the frame's poses are registered to
+        the same cropped cloud by ICP (pose.refine_poses, one launch for all objects) before they become frame t+1's centres.
+        init_from='net': the poses refined are the network's.  init_from='previous' (needs refine): no forward runs at all, the
+        previous pose is refined against the new crop -- the model-based tracker; pred_scales are carried through.  An object whose
+        ICP status is not 0 (ops.ICP_STATUS) keeps its previous pose and scales; the results gain 'icp_status', 'icp_inliers'
+        (int32) and 'icp_rmse' (float32), (n,) each.  Still nothing is read back between frames.
         -> list over frames of {'pred_RTs' (n,4,4), 'pred_scales' (n,3), 'status' (n,) int32, 'tracked' (n,) bool} ndarrays."""
         if ratio is None:
             raise ValueError("track: ratio is required (the reference fixes none)")
+        if init_from not in ("net", "previous"):
+            raise ValueError("track: init_from must be 'net' or 'previous'")
+        if refine is not None and not isinstance(refine, IcpRefine):
+            raise TypeError("track: refine must be a pose.IcpRefine")
+        if init_from == "previous" and refine is None:
+            raise ValueError("track: init_from='previous' needs refine (without it nothing would move the poses)")
         sampler = sampler or (self.sampler if self.sampler in ("device", "fps") else "device")
         if sampler not in ("device", "fps"):
             raise ValueError("track: sampler must be 'device' or 'fps' (nothing is read back between frames)")
@@ -203,26 +217,37 @@ class myEvaluater:
         results, pending = [], None
 
         def fetch(item):
-            r, s, st, done = item
+            r, s, st, done = item[:4]
             with torch.cuda.stream(self._fetch):
                 self._fetch.wait_event(done)
-                for x in (r, s, st):
+                for x in (r, s, st) + item[4:]:
                     x.record_stream(self._fetch)
                 r, s, st = r.cpu().numpy(), s.cpu().numpy(), st.cpu().numpy()
+                icp = [x.cpu().numpy() for x in item[4:]]
             results.append(dict(pred_RTs=r, pred_scales=s, status=st, tracked=st == 0))
+            if icp:
+                results[-1].update(icp_status=icp[0][:, 0].copy(), icp_inliers=icp[0][:, 1].copy(), icp_rmse=icp[1])
         for k, frame in enumerate(sequence):
             masks = inst_ids if inst_ids is not None and "inst_mask" in frame else None
             with torch.no_grad():
                 pts, ok, _, counts = lde.clouds_from_poses([frame], job_img, rts, scales, ratio, camK, n_pts=n_pts, sampler=sampler,
                                                            masks=masks, seed=self.seed + k, fps_pool=self.fps_pool, device=dev,
                                                            return_counts=True)
-                new_rts, new_scales = infer_device(self.net1, torch.nan_to_num(pts, nan=0.0), cat, mean, sym, self.max_batch,
-                                                   eval_outputs_only=self.eval_outputs_only)
+                if init_from == "net":
+                    new_rts, new_scales = infer_device(self.net1, torch.nan_to_num(pts, nan=0.0), cat, mean, sym, self.max_batch,
+                                                       eval_outputs_only=self.eval_outputs_only)
+                else:
+                    new_rts, new_scales = rts, scales
+                icp = ()
+                if refine is not None:
+                    new_rts, info, rmse = refine(pts, new_rts)      # a failed crop's NaN rows are never inliers: status 1
+                    ok = ok & (info[:, 0] == 0)
+                    icp = (info, rmse)
                 rts = torch.where(ok[:, None, None], new_rts, rts)
                 scales = torch.where(ok[:, None], new_scales, scales)
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(dev))
-            item = (rts, scales, counts[:, 3].contiguous(), done)
+            item = (rts, scales, counts[:, 3].contiguous(), done) + icp
             if pending is not None:
                 fetch(pending)
             pending = item

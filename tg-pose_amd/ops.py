@@ -2152,6 +2152,110 @@ def ball_sample(br, n_pts, seed, counts=None):
     return out, pix
 
 
+# ------------------------------------------------------------------------------------------------------------ ICP pose refinement
+ICP_MAX_POINTS = _lib.ICP_MAX_POINTS
+ICP_MODES = {"point": 0, "plane": 1}
+ICP_STATUS = {1: "too few inliers", 2: "singular system", 3: "job_model or a count out of range"}
+
+
+def icp_max_points():
+    """most model points per model / source points per job that icp_refine takes"""
+    return int(_lib.lib().tgp_icp_max_points())
+
+
+class IcpModels(object):
+    """The padded model set icp_refine registers against: ``points_normals`` (M, m_cap, 6) float32 on the GPU, rows [point, unit
+    normal] in model units (what mesh_sample(..., normals=True) writes), and ``counts`` (M) int32 live rows per model (None: m_cap)."""
+
+    def __init__(self, points_normals, counts=None):
+        _f32(points_normals, "points_normals", 3)
+        if points_normals.shape[2] != 6 or not points_normals.is_contiguous() or points_normals.shape[0] < 1:
+            raise ValueError("IcpModels: points_normals must be a contiguous (M, m_cap, 6) tensor")
+        if not 1 <= points_normals.shape[1] <= ICP_MAX_POINTS:
+            raise ValueError("IcpModels: m_cap must be in [1, %d]" % ICP_MAX_POINTS)
+        if counts is not None:
+            counts = torch.as_tensor(counts, dtype=torch.int32).to(points_normals.device).contiguous()
+            if counts.shape != (points_normals.shape[0],):
+                raise ValueError("IcpModels: counts must be (M,)")
+        self.points_normals, self.counts = points_normals, counts
+
+    def __len__(self):
+        return self.points_normals.shape[0]
+
+    @property
+    def m_cap(self):
+        return self.points_normals.shape[1]
+
+    @classmethod
+    def from_meshset(cls, meshset, meshes, n, seed=0):
+        """n surface samples with normals of each of ``meshes`` (mesh indices of the set), drawn on the device: model k's draws are
+        keyed k under ``seed`` (mesh_sample)"""
+        meshes = [int(m) for m in meshes]
+        out = mesh_sample(meshset, meshes, n, keys=list(range(len(meshes))), seed=seed, normals=True, check_status=True)
+        return cls(out["points"])
+
+
+def icp_check_status(info, what="icp_refine"):
+    """one read of the (J,4) info words; raises TgpError naming the first failed job"""
+    st = info[:, 0].cpu().tolist()
+    bad = [(j, s) for j, s in enumerate(st) if s != 0]
+    if bad:
+        raise _lib.TgpError("%s: job %d failed: %s (%d of %d jobs failed)" % (what, bad[0][0], ICP_STATUS.get(bad[0][1], bad[0][1]),
+                                                                             len(bad), len(st)))
+
+
+def icp_refine(models, job_model, src, R, t, s, max_dist, *, src_count=None, mode="plane", with_scale=False, iters=30, tol_rot=1e-5,
+               tol_trans=1e-6, min_inliers=6, return_corr=False):
+    """tgp_icp_refine (csrc/icp.hip; DESIGN.md section 3 "ICP refinement and model-based tracking"): J poses made to fit J clouds in
+    one launch, every iteration on the device.  models: IcpModels; job_model (J) int32; src (J, n_cap, 3) float32 camera-frame
+    metres (NaN rows are never inliers), src_count (J) int32 or None; R (J,3,3), t (J,3), s (J): the start x = s R y + t from model
+    to camera; max_dist (J) float32 (or one number): the gate in metres.  mode 'plane' (point-to-plane Gauss-Newton) or 'point'
+    (closed form; with_scale: the scale moves too); iters the cap; tol_rot / tol_trans: stop when an update is within both (both 0:
+    exactly iters iterations).  -> (R, t, s, info (J,4) int32 = status, final inliers, iterations, 0; rmse (J)[, corr (J, n_cap)
+    int32 with return_corr]).  Nothing is read back (icp_check_status does)."""
+    if mode not in ICP_MODES:
+        raise ValueError("icp_refine: mode must be 'plane' or 'point'")
+    if with_scale and mode != "point":
+        raise ValueError("icp_refine: with_scale needs mode='point'")
+    if not (isinstance(iters, int) and iters >= 1):
+        raise ValueError("icp_refine: iters must be an int >= 1")
+    if not (tol_rot >= 0 and tol_trans >= 0 and isinstance(min_inliers, int) and min_inliers >= 0):
+        raise ValueError("icp_refine: tol_rot, tol_trans and min_inliers must not be negative")
+    _f32(src, "src", 3), _i32(job_model, "job_model"), _f32(R, "R", 3), _f32(t, "t", 2), _f32(s, "s", 1)
+    if not isinstance(models, IcpModels):
+        raise TypeError("icp_refine: models must be an ops.IcpModels")
+    J, n_cap = src.shape[0], src.shape[1]
+    dev = src.device
+    if J < 1 or not 1 <= n_cap <= ICP_MAX_POINTS or src.shape[2] != 3:
+        raise ValueError("icp_refine: src must be (J, n_cap, 3) with J >= 1 and 1 <= n_cap <= %d" % ICP_MAX_POINTS)
+    if J > 65535:
+        raise ValueError("icp_refine: at most 65535 jobs a call")
+    if job_model.shape != (J,) or R.shape != (J, 3, 3) or t.shape != (J, 3) or s.shape != (J,):
+        raise ValueError("icp_refine: job_model (J,), R (J,3,3), t (J,3) and s (J,) are needed for the %d jobs" % J)
+    if not torch.is_tensor(max_dist):
+        max_dist = torch.full((J,), float(max_dist), device=dev, dtype=torch.float32)
+    if _f32(max_dist, "max_dist", 1).shape != (J,):
+        raise ValueError("icp_refine: max_dist must be (J,)")
+    if src_count is not None and _i32(src_count, "src_count").shape != (J,):
+        raise ValueError("icp_refine: src_count must be (J,)")
+    tensors = [src, job_model, R, t, s, max_dist, models.points_normals] + [x for x in (src_count, models.counts) if x is not None]
+    if not all(x.is_contiguous() for x in tensors):
+        raise ValueError("icp_refine: every tensor must be contiguous")
+    if any(x.device != dev for x in tensors):
+        raise ValueError("icp_refine: every tensor must be on one device")
+    R_out, t_out, s_out = torch.empty_like(R), torch.empty_like(t), torch.empty_like(s)
+    info = torch.empty(J, 4, device=dev, dtype=torch.int32)
+    rmse = torch.empty(J, device=dev, dtype=torch.float32)
+    corr = torch.empty(J, n_cap, device=dev, dtype=torch.int32) if return_corr else None
+    a = _lib.IcpArgs(models=_p(models.points_normals), model_count=_p(models.counts), M=len(models), m_cap=models.m_cap, src=_p(src),
+                     src_count=_p(src_count), job_model=_p(job_model), J=J, n_cap=n_cap, R=_p(R), t=_p(t), s=_p(s), max_dist=_p(max_dist),
+                     mode=ICP_MODES[mode], with_scale=int(bool(with_scale)), iters=iters, tol_rot=float(tol_rot), tol_trans=float(tol_trans),
+                     min_inliers=min_inliers, R_out=_p(R_out), t_out=_p(t_out), s_out=_p(s_out), info=_p(info), rmse=_p(rmse), corr=_p(corr))
+    check(_lib.lib().tgp_icp_refine(ctypes.byref(a), _stream(src)), "tgp_icp_refine")
+    out = (R_out, t_out, s_out, info, rmse)
+    return out + (corr,) if return_corr else out
+
+
 # ---------------------------------------------------------------------------------------------------------- the optimizer step
 def ranger_plan(table):
     """Check a host descriptor table (a ctypes array of _lib.RangerTensor) and fill its unit0 fields (tgp_ranger_plan, host only:

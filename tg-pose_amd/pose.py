@@ -37,6 +37,55 @@ def infer_device(net, pts, cat, ms, sym, max_batch=256, eval_outputs_only=None, 
     return torch.cat(rts), torch.cat(scales)
 
 
+def split_RT(RTs):
+    """(J,4,4) [s R | t] -> (R (J,3,3), t (J,3), s (J,)) with s = cbrt(det), elementwise torch ops on RTs' device (no read-back)"""
+    A = RTs[:, :3, :3]
+    det = (A[:, 0, 0] * (A[:, 1, 1] * A[:, 2, 2] - A[:, 1, 2] * A[:, 2, 1]) - A[:, 0, 1] * (A[:, 1, 0] * A[:, 2, 2] - A[:, 1, 2] * A[:, 2, 0])
+           + A[:, 0, 2] * (A[:, 1, 0] * A[:, 2, 1] - A[:, 1, 1] * A[:, 2, 0]))
+    s = torch.sign(det) * det.abs().pow(1.0 / 3.0)
+    return (A / s[:, None, None]).contiguous(), RTs[:, :3, 3].contiguous(), s.contiguous()
+
+
+def join_RT(R, t, s):
+    """the inverse of split_RT"""
+    RTs = torch.zeros(R.shape[0], 4, 4, device=R.device, dtype=R.dtype)
+    RTs[:, :3, :3] = R * s[:, None, None]
+    RTs[:, :3, 3] = t
+    RTs[:, 3, 3] = 1.0
+    return RTs
+
+
+def refine_poses(models, job_model, clouds, RTs, max_dist, **kw):
+    """ICP refinement (ops.icp_refine) of the project's 4x4 poses [s R | t] against clouds (J,n,3) in camera-frame metres, as
+    load_data_eval.clouds_from_poses cuts them (NaN rows of failed crops are never inliers).  models: ops.IcpModels; job_model (J)
+    int32; max_dist: the gate in metres, (J,) or one number; kw: icp_refine's keywords.  The poses are taken apart and put together on
+    the device.  -> (RTs (J,4,4), info (J,4) int32, rmse (J,)); a job whose status info[:, 0] is not 0 returns the pose of its last
+    good iteration, put together again (equal to the pose it came with to rounding when that is the start)."""
+    if kw.get("return_corr"):
+        raise ValueError("refine_poses: return_corr is ops.icp_refine's")
+    R, t, s = split_RT(RTs)
+    R, t, s, info, rmse = ops.icp_refine(models, job_model, clouds, R, t, s, max_dist, **kw)
+    return join_RT(R, t, s), info, rmse
+
+
+class IcpRefine(object):
+    """What myEvaluater.track(refine=...) needs to refine its objects' poses: ``models`` (ops.IcpModels), ``job_model`` (one model
+    index per tracked object; kept as an int32 tensor on the models' device), ``max_dist`` (the gate in metres, one number or one
+    per object) and ops.icp_refine's keywords (mode, iters, tol_rot, ...)."""
+
+    def __init__(self, models, job_model, max_dist, **kw):
+        if not isinstance(models, ops.IcpModels):
+            raise TypeError("IcpRefine: models must be an ops.IcpModels")
+        dev = models.points_normals.device
+        self.models = models
+        self.job_model = torch.as_tensor(job_model, dtype=torch.int32).to(dev).contiguous()
+        self.max_dist = max_dist.to(dev).float().contiguous() if torch.is_tensor(max_dist) else float(max_dist)
+        self.kw = dict(kw)
+
+    def __call__(self, clouds, RTs):
+        return refine_poses(self.models, self.job_model, clouds, RTs, self.max_dist, **self.kw)
+
+
 def batched_inference(net, clouds, cat_ids, mean_shapes, syms, max_batch=256):
     """clouds: list over images of (n_det_i, N, 3) tensors (same N); cat_ids / mean_shapes / syms likewise.
     Returns a list over images of dicts {'pred_RTs': (n_det_i,4,4) ndarray, 'pred_scales': (n_det_i,3) ndarray}."""
