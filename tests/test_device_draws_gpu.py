@@ -57,7 +57,9 @@ def _blob_item(base, side, depth_zero=False, inst=1):
 # ------------------------------------------------------------------------------------------------------------------ 1. replay
 def test_replay_of_the_device_draws_equals_the_host_path(fx):
     """the draw buffers a draws='device' batch made, read back and fed to the host path's launches (_train_batch_from_draws), give
-    the same rows bit for bit: dzi, roi_mask_pro 0.5, an abandoned item, accepted crops and cutouts"""
+    the same rows bit for bit: dzi, roi_mask_pro 0.5, an abandoned item, accepted crops and cutouts.  _train_batch_from_draws
+    launches through load_data._records and load_data._augment_rows, the functions train_batch(draws='host') itself calls (and
+    draws='device' too): the comparison is with the host path's code, not with a copy of it"""
     from tgpose_amd import _lib
     from tgpose_amd.datasets.load_data import train_batch, _train_batch_from_draws, DRAW_KEYS
     items = _items(10)

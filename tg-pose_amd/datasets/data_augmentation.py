@@ -207,30 +207,37 @@ def default_operators():
             PcRandomDropout(p=0.9, max_dropout_ratio=0.5)]
 
 
-def view_inputs(records, n, device, operators):
-    """The kernel's second-view inputs for a batch of draw records (one per item, clouds of n points).  The crop / cutout limits
-    come from the operators of those kinds in ``operators``."""
+def view_limits(operators):
+    """the crop / cutout limits of the kernel's second view, from the operators of those kinds in ``operators`` (the defaults of
+    PcRandomCrop / PcRandomCutout without one); refuses a max_try_num the kernel's attempt table cannot hold"""
     for o in operators:
         if isinstance(o, (PcRandomCrop, PcRandomCutout)) and not 0 <= o.max_try_num < _lib.AUGMENT_MAX_TRY:
             raise ValueError("max_try_num must be in [0, %d)" % _lib.AUGMENT_MAX_TRY)
-    B = len(records)
-    noise = torch.zeros(B, n, 3)
-    drop_u = np.zeros((B, n))
-    boxes = np.zeros((B, _lib.AUGMENT_MAX_TRY, 6))
-    for i, r in enumerate(records):
-        if r['noise'] is not None:
-            noise[i] = r['noise']
-        if r['drop_u'] is not None:
-            drop_u[i] = r['drop_u']
-        if r['boxes'] is not None:
-            boxes[i] = r['boxes']
     crop = next((o for o in operators if isinstance(o, PcRandomCrop)), PcRandomCrop())
     cut = next((o for o in operators if isinstance(o, PcRandomCutout)), PcRandomCutout())
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    return dict(op=up(np.array([r['op'] for r in records], dtype=np.int32)), noise=noise.to(device),
-                drop_ratio=up(np.array([r['drop_ratio'] for r in records], dtype=np.float64)), drop_u=up(drop_u), boxes=up(boxes),
-                crop_max_try=crop.max_try_num, cutout_max_try=cut.max_try_num, crop_min_points=crop.min_num_points,
+    return dict(crop_max_try=crop.max_try_num, cutout_max_try=cut.max_try_num, crop_min_points=crop.min_num_points,
                 cutout_min_points=cut.min_num_points)
+
+
+def view_arrays(records, n):
+    """a batch of draw records (one per item, clouds of n points) as the host arrays of the kernel's second-view inputs: op int32,
+    noise float32, drop_ratio, drop_u and boxes float64"""
+    B = len(records)
+    out = dict(op=np.array([r['op'] for r in records], dtype=np.int32), noise=np.zeros((B, n, 3), np.float32),
+               drop_ratio=np.array([r['drop_ratio'] for r in records], dtype=np.float64), drop_u=np.zeros((B, n)),
+               boxes=np.zeros((B, _lib.AUGMENT_MAX_TRY, 6)))
+    for i, r in enumerate(records):
+        for k in ('noise', 'drop_u', 'boxes'):
+            if r[k] is not None:
+                out[k][i] = r[k].numpy() if torch.is_tensor(r[k]) else r[k]
+    return out
+
+
+def view_inputs(records, n, device, operators):
+    """The kernel's second-view inputs for a batch of draw records (one per item, clouds of n points).  The crop / cutout limits
+    come from the operators of those kinds in ``operators``."""
+    limits = view_limits(operators)
+    return dict({k: torch.from_numpy(v).to(device) for k, v in view_arrays(records, n).items()}, **limits)
 
 
 def defor_2D(roi_mask, rand_r=2, rand_pro=0.3, rng=np.random, draws="host", seed=None, key=0):

@@ -6,7 +6,7 @@ resampling of pixel grid / ground-truth instance mask / depth with nearest-neigh
 the cut of the points within 0.15 x the extent's diagonal of point number 25 (:276-286), the ``len(pcl_in) < 50`` test (:288) and the
 double subsample ``_sample_points(PC, 2048)`` then ``_sample_points(PC, 1024)`` (:335-336, 366-380).  A batch of items is ONE launch
 of the evaluation loader's kernel (``tgp_roi_cloud_ex``: a workgroup per item, clouds kept as 4-byte records in the reference's
-point order) plus one gather per requested cloud size (``tgp_cloud_select_ex``).
+point order) plus one gather of the 2048 selected points (``tgp_cloud_select_ex``) and a row gather of the 1024 selected among them.
 
 What differs from the evaluation loader, and how the kernel takes it:
   * the mask is the frame's instance-id image and the item is ``mask == inst_id`` (:245-247) -> ``mask_val``;
@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from . import data_augmentation as da
 from ..evaluation.load_data_eval import CAMERA_INTRINSICS, REAL_INTRINSICS, get_bbox  # noqa: F401  (re-exported)
 
 AB_BITS = 10          # OpenCV's warpAffine works in 10-bit fixed point (AB_SCALE = 1024)
@@ -240,58 +241,63 @@ def train_clouds(items, img_size=256, rng=np.random, device="cuda", min_points=5
     if not items:
         return []
     if draws == "device":
-        from . import data_augmentation as da
         return _train_batch_device(items, seed, keys, batch_size, img_size, dev, min_points, da.default_operators(), False, roi_mask_pro,
                                    roi_mask_r, dzi, clouds_only=True)
     rr, counts = _roi_records(items, img_size, dev, rng, roi_mask_pro, roi_mask_r, dzi)
-    deformed = roi_mask_pro is not None
     D = len(items)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    sel2k, sel1k = np.zeros((D, 2048), dtype=np.int32), np.zeros((D, 1024), dtype=np.int32)
+    sel2k, p1k = np.zeros((D, 2048), dtype=np.int32), np.zeros((D, 1024), dtype=np.int32)
     alive = []
     for d in range(D):
-        total = _item_total(counts[d], min_points, deformed)
-        if total is None:
-            alive.append(False)
-            continue
-        sel2k[d] = _selection(total, 2048, rng)                # PC = _sample_points(PC, 2048)
-        sel1k[d] = sel2k[d][_selection(2048, 1024, rng)]       # pcl_in = _sample_points(PC, 1024): a selection of the selection
-        alive.append(True)
-    pc2k = ops.cloud_select(rr, up(sel2k))
-    pc1k = ops.cloud_select(rr, up(sel1k))
+        total = _item_total(counts[d], min_points, roi_mask_pro is not None)
+        alive.append(total is not None)
+        if alive[d]:
+            sel2k[d] = _selection(total, 2048, rng)                # PC = _sample_points(PC, 2048)
+            p1k[d] = _selection(2048, 1024, rng)                   # pcl_in = _sample_points(PC, 1024): a selection of the selection
+    up = _pageable(dev)
+    pc2k, pc1k = _two_clouds(rr, up(sel2k), up(p1k))
+    pc1k = pc1k[..., :3].contiguous()
     return [(pc2k[d], pc1k[d]) if alive[d] else None for d in range(D)]
+
+
+def _two_clouds(rr, sel2k, p1k):
+    """PC = the records' points sel2k (D,2048), pcl_in = PC's rows p1k (D,1024) -> (D,2048,3), (D,1024,4) padded to 4 columns"""
+    pc2k = ops.cloud_select(rr, sel2k)
+    return pc2k, ops.gather_rows(torch.nn.functional.pad(pc2k, (0, 1)), p1k, torch.empty(len(p1k), 1024, 4, device=pc2k.device))
+
+
+def _pageable(dev):
+    """host array -> device tensor by a blocking copy from pageable memory (the host modes; draws='device' has _uploader)"""
+    return lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _window(it, H, W, dzi_rng=None):
+    """an item's window (bbox_center, scale): aug_bbox_dzi's draw from dzi_rng (load_data.py:238), else its own, else get_bbox's"""
+    if dzi_rng is not None:
+        return aug_bbox_dzi(it["bbox"], H, W, dzi_rng)
+    if "bbox_center" in it:
+        return it["bbox_center"], it["scale"]
+    return window_without_dzi(it["bbox"], H, W)
+
+
+def _records(items, tabs, up, H, W, img_size, defor=None):
+    """the frame upload and the items' ROI clouds as records, ONE tgp_roi_cloud_ex launch -- or, with defor = (defor_on, drop_bits) or a
+    function that makes that pair from the band launch's (D,3) device counts, tgp_roi_cloud_defor -> (RoiRecords, the pair or None)"""
+    args, tabs, mval, camk = _upload_frames(items, tabs, up, H, W)
+    if callable(defor):
+        defor = defor(ops.roi_band(*args, roi_size=img_size, tables=tabs, mask_val=mval))
+    return ops.roi_cloud(*args, camk, roi_size=img_size, tables=tabs, mask_val=mval, cut_frac=0.15, defor=defor), defor
 
 
 def _roi_records(items, img_size, dev, rng=np.random, roi_mask_pro=None, roi_mask_r=3, dzi=False):
     """the items' ROI clouds as records (one tgp_roi_cloud_ex launch) and their counts (one 12-byte read-back per item); with
     roi_mask_pro, the band launch, its read-back, the deformation draws and one tgp_roi_cloud_defor launch instead"""
     H, W = _check_items(items, roi_mask_pro, roi_mask_r, dzi)
-    tabs, camk, mval = [], [], []
-    for it in items:
-        if dzi:
-            center, scale = aug_bbox_dzi(it["bbox"], H, W, rng)                 # load_data.py:238
-        elif "bbox_center" in it:
-            center, scale = it["bbox_center"], it["scale"]
-        else:
-            center, scale = window_without_dzi(it["bbox"], H, W)
-        tabs.append(source_tables(center, scale, img_size))
-        K = np.asarray(it["camK"], dtype=np.float32)
-        camk.append([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
-        mval.append(int(it["inst_id"]))
-    D = len(items)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    depth = up(np.stack([it["depth"] for it in items]).view(np.int16))
-    masks = up(np.stack([it["mask"] for it in items]).reshape(-1))
-    args = (depth, masks, up(np.arange(D, dtype=np.int64) * (H * W)), up(np.ones(D, dtype=np.int32)), up(np.arange(D, dtype=np.int32)),
-            None)
-    tabs, mval = up(np.stack(tabs)), up(np.asarray(mval, dtype=np.int32))
+    tabs = [source_tables(*_window(it, H, W, rng if dzi else None), img_size) for it in items]
+    up = _pageable(dev)
     defor = None
-    if roi_mask_pro is not None:
-        band = ops.roi_band(*args, roi_size=img_size, tables=tabs, mask_val=mval).cpu().numpy()      # the extra read-back
-        on, bits = defor_draws(band, float(roi_mask_pro), rng)                                         # :280
-        defor = (up(on), up(bits))
-    rr = ops.roi_cloud(*args, up(np.asarray(camk, dtype=np.float32)), roi_size=img_size, tables=tabs, mask_val=mval, cut_frac=0.15,
-                       defor=defor)
+    if roi_mask_pro is not None:              # the extra read-back, then :280
+        defor = lambda band: tuple(up(a) for a in defor_draws(band.cpu().numpy(), float(roi_mask_pro), rng))
+    rr = _records(items, tabs, up, H, W, img_size, defor)[0]
     return rr, rr.counts.cpu().numpy()
 
 
@@ -377,7 +383,6 @@ def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min
     draw from ``rng`` moves up by that permutation; with draws='device' its site is simply not used and every other draw is the
     same.  persistence=True then runs on the FPS pcl_in.  In this mode only, the batch also carries PC (B,2048,3), the augmented
     cloud, and pcl_index (B,1024) int32, its rows in selection order: pcl_in == PC[pcl_index]."""
-    from . import data_augmentation as da
     if draws not in ("host", "device"):
         raise ValueError("draws must be 'host' or 'device'")
     if pcl_select not in ("random", "fps"):
@@ -395,66 +400,50 @@ def train_batch(items, rng=np.random, gen=None, img_size=256, device="cuda", min
         return _train_batch_device(items, seed, keys, batch_size, img_size, dev, min_points, ops_, persistence, roi_mask_pro, roi_mask_r,
                                    dzi, keep_draws=keep_draws, fps=fps)
     rr, counts = _roi_records(items, img_size, dev, rng, roi_mask_pro, roi_mask_r, dzi)
-    deformed = roi_mask_pro is not None
-    keep, sel2k, p1k, shuf, recs, names, defer = [], [], [], [], [], [], []
-    params, draws, defor = [], [], []
-    for d, it in enumerate(items):
-        total = _item_total(counts[d], min_points, deformed)
+    keep, names, recs, shuf, defer = [], [], [], [], []
+    h = {k: [] for k in ("aug_bb", "aug_rt_t", "aug_rt_R", "base", "defor", "p1k")}        # DRAW_KEYS buffers, a row per kept item
+    sel2k = np.zeros((len(items), 2048), dtype=np.int32)                                      # (a row per item: the records')
+    for d in range(len(items)):
+        total = _item_total(counts[d], min_points, roi_mask_pro is not None)
         if total is None:
             continue
         keep.append(d)
-        params.append(da.generate_aug_parameters(rng))                            # :318
-        dr, de = da.base_draws(1, total, "cpu", gen=gen, defor_gen=gen)           # :333 base_aug
-        draws.append(dr[0])
-        s2 = _selection(total, 2048, rng)                                         # :335
-        sel2k.append(s2)
-        defor.append(de[0][torch.from_numpy(s2.astype(np.int64))])                # the rows of the selected points only
+        for k, v in zip(("aug_bb", "aug_rt_t", "aug_rt_R"), da.generate_aug_parameters(rng)):     # :318
+            h[k].append(v)
+        base, defor = da.base_draws(1, total, "cpu", gen=gen, defor_gen=gen)      # :333 base_aug
+        sel2k[d] = _selection(total, 2048, rng)                                   # :335
+        h["base"].append(base[0].numpy())
+        h["defor"].append(defor[0].numpy()[sel2k[d]])                             # the rows of the selected points only
         if not fps:
-            p1k.append(_selection(2048, 1024, rng).astype(np.int32))              # :336
+            h["p1k"].append(_selection(2048, 1024, rng).astype(np.int32))         # :336
         k = int(rng.randint(0, len(ops_)))                                        # :346
-        rec = ops_[k].draw(2048, rng, gen)                                        # :347
-        recs.append(rec)
+        recs.append(ops_[k].draw(2048, rng, gen))                                 # :347
         names.append(da.OPERATOR_NAMES[k])
-        if rec["op"] in (da._lib.AUG_CROP, da._lib.AUG_CUTOUT):
+        if recs[-1]["op"] in (da._lib.AUG_CROP, da._lib.AUG_CUTOUT):
             shuf.append(None)                                                     # M comes from the kernel
             defer.append(len(keep) - 1)
         else:
             shuf.append(da.sampler_perm(2048, 1024, rng))                         # :348 pc_sampler
     if not keep:
         raise ValueError("train_batch: every item was abandoned")
-    B = len(keep)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    sel = np.zeros((len(items), 2048), dtype=np.int32)
-    sel[keep] = np.stack(sel2k)
-    pc2k = ops.cloud_select(rr, up(sel))
-    if B != len(items):
-        pc2k = pc2k[up(np.asarray(keep, dtype=np.int64))].contiguous()
-    lab = {k: [items[d][k] for d in keep] for k in items[0] if k not in _IMAGE_KEYS}
-    for k in _POSE_KEYS + ("mean_shape", "sym_info", "model_point", "nocs_scale", "cat_id"):
-        if k not in lab:
-            raise ValueError("train_batch: every item needs %r" % k)
-    f32 = lambda k: up(np.stack([np.asarray(v, dtype=np.float32) for v in lab[k]]))
-    stacked = {k: f32(k) for k in lab}
-    base = da._base_inputs(torch.stack(draws).to(dev), stacked["rotation"], stacked["translation"], stacked["fsnet_scale"],
-                           stacked["mean_shape"], stacked["sym_info"], up(np.stack([p[0] for p in params])),
-                           up(np.stack([p[1] for p in params])), up(np.stack([p[2] for p in params])), stacked["cat_id"],
-                           stacked["nocs_scale"], stacked["model_point"], torch.stack(defor).to(dev))
-    # padded (B, 2048, 4) outputs: tgp_gather_rows moves rows of a multiple of 4 floats
-    out = ops.augment(pc2k, base=base, view=da.view_inputs(recs, 2048, dev, ops_), ld_out=4)
-    if defer:                                                                     # the batch's one read-back of M
-        m = out["counts"][:, 0].cpu().numpy()
-        for i in defer:
-            shuf[i] = da.sampler_perm(int(m[i]), 1024, rng)
-    pcl_index = ops.farthest_points(out["pc"], 1024) if fps else up(np.stack(p1k))
-    pcl_in = ops.gather_rows(out["pc"], pcl_index, torch.empty(B, 1024, 4, device=dev))[..., :3].contiguous()
-    aug = ops.gather_rows(out["view"], up(np.stack(shuf)), torch.empty(B, 1024, 4, device=dev))[..., :3].contiguous()
-    db = {k: v for k, v in stacked.items() if k not in _POSE_KEYS}
-    db.update(pcl_in=pcl_in, aug_pcl_in=aug, rotation=out["R"], translation=out["t"], fsnet_scale=out["s"], aug_flags=out["flags"],
-              aug_counts=out["counts"], item_index=up(np.asarray(keep, dtype=np.int64)), aug_name=names)
-    if fps:
-        db.update(PC=out["pc"][..., :3].contiguous(), pcl_index=pcl_index)
+    up = _pageable(dev)
+
+    def shuffle(counts):
+        if defer:                                                                 # the batch's one read-back of M
+            m = counts[:, 0].cpu().numpy()
+            for i in defer:
+                shuf[i] = da.sampler_perm(int(m[i]), 1024, rng)
+        return up(np.stack(shuf))
+    kept = up(np.asarray(keep, dtype=np.int64))
+    lab = _stack_labels([items[d] for d in keep], up)
+    dr = {k: up(np.stack(v)) for k, v in h.items() if v}
+    dr.update({k: up(v) for k, v in da.view_arrays(recs, 2048).items()}, sel2k=up(sel2k))
+    db = _augment_rows(rr, dr, lab, ops_, shuffle, fps, rows=kept if len(keep) != len(items) else None)
+    del db["shuf"]
+    db.update({k: v for k, v in lab.items() if k not in _POSE_KEYS}, item_index=kept, aug_name=names)
+    _unpad(db)
     if persistence:
-        db["pdh1"], db["pdh2"] = ops.persistence_images(pcl_in)
+        db["pdh1"], db["pdh2"] = ops.persistence_images(db["pcl_in"])
     return db
 
 
@@ -498,7 +487,6 @@ def _stack_labels(items, up):
 
 def _keyed_record(op, st):
     """an operator's scalar draws from an item's stream; its per-point draws (noise, drop_u) are made on the device"""
-    from . import data_augmentation as da
     if isinstance(op, da.PcJitter):
         return da._record(da._lib.AUG_NONE if st.uniform() > op.p else da._lib.AUG_JITTER, 2048)
     if isinstance(op, da.PcRandomDropout):
@@ -512,20 +500,14 @@ def _item_scalars(items, seed, keys, H, W, img_size, dzi, ops_):
     """the per-item scalars of draws='device', from each item's stream (device_draws.ItemStream) -> dict of host arrays, D rows:
     tabs, forced (TGP_ITEM_WINDOW where source_tables refused the window), u_defor, aug_bb, aug_rt_t, aug_rt_R, base (the six
     PC_BasicAugment draws), op_index, op, drop_ratio, boxes"""
-    from . import data_augmentation as da, device_draws as dd
+    from . import device_draws as dd
     D = len(items)
     sc = dict(tabs=np.zeros((D, 2, img_size), np.int32), forced=np.zeros(D, np.int32), u_defor=np.zeros(D), aug_bb=np.zeros((D, 3), np.float32),
               aug_rt_t=np.zeros((D, 3), np.float32), aug_rt_R=np.zeros((D, 3, 3), np.float32), base=np.zeros((D, 6), np.float32),
               op_index=np.zeros(D, np.int32), op=np.zeros(D, np.int32), drop_ratio=np.zeros(D), boxes=np.zeros((D, da._lib.AUGMENT_MAX_TRY, 6)))
     for d, (it, st) in enumerate(zip(items, dd.item_streams(seed, keys))):
-        if dzi:
-            center, scale = aug_bbox_dzi(it["bbox"], H, W, st.seek(st.DZI))
-        elif "bbox_center" in it:
-            center, scale = it["bbox_center"], it["scale"]
-        else:
-            center, scale = window_without_dzi(it["bbox"], H, W)
         try:
-            sc["tabs"][d] = source_tables(center, scale, img_size)
+            sc["tabs"][d] = source_tables(*_window(it, H, W, st.seek(st.DZI) if dzi else None), img_size)
         except ValueError:                       # not separable: the item is abandoned (its table stays pixel (0, 0))
             sc["forced"][d] = da._lib.ITEM_WINDOW
         sc["u_defor"][d] = st.seek(st.DEFOR).rand()
@@ -539,59 +521,57 @@ def _item_scalars(items, seed, keys, H, W, img_size, dzi, ops_):
     return sc
 
 
-def _view_limits(ops_):
-    from . import data_augmentation as da
-    for o in ops_:
-        if isinstance(o, (da.PcRandomCrop, da.PcRandomCutout)) and not 0 <= o.max_try_num < da._lib.AUGMENT_MAX_TRY:
-            raise ValueError("max_try_num must be in [0, %d)" % da._lib.AUGMENT_MAX_TRY)
-    crop = next((o for o in ops_ if isinstance(o, da.PcRandomCrop)), da.PcRandomCrop())
-    cut = next((o for o in ops_ if isinstance(o, da.PcRandomCutout)), da.PcRandomCutout())
-    return dict(crop_max_try=crop.max_try_num, cutout_max_try=cut.max_try_num, crop_min_points=crop.min_num_points,
-                cutout_min_points=cut.min_num_points)
-
-
 DRAW_KEYS = ("tabs", "defor_on", "drop_bits", "aug_bb", "aug_rt_t", "aug_rt_R", "base", "op", "drop_ratio", "boxes", "sel2k", "p1k", "defor",
              "noise", "drop_u", "shuf")
 
 
-def _augment_rows(rr, dr, lab, ops_, shuffle=None, fps=False):
-    """the launches that follow the records, on every item's row, from the draws ``dr`` (device tensors under DRAW_KEYS): the 2048
+def _augment_rows(rr, dr, lab, ops_, shuffle=None, fps=False, rows=None):
+    """the launches that follow the records, the same for every mode, from the draws ``dr`` (device tensors under DRAW_KEYS): the 2048
     selected points, tgp_augment, the two row gathers.  shuffle(counts) draws 'shuf' when dr has none (it needs the launch's M).
     fps: the rows of pcl_in are the farthest point sampling of the augmented cloud instead of dr['p1k'] (not read).
-    -> dict of (D, ...) tensors: pcl_in, aug_pcl_in (padded to 4 columns), rotation, translation, fsnet_scale, aug_flags, aug_counts,
+    rows (B,) int64: the items to go on with after the selection, which runs on every item of rr with dr['sel2k']; lab and the
+    rest of dr then hold B rows, for those items (the host path's kept items: an abandoned item's points never reach tgp_augment).
+    -> dict of (B, ...) tensors: pcl_in, aug_pcl_in (padded to 4 columns), rotation, translation, fsnet_scale, aug_flags, aug_counts,
     shuf; with fps also PC (the augmented cloud, padded to 4 columns) and pcl_index"""
-    from . import data_augmentation as da
-    D, dev = rr.recs.shape[0], rr.recs.device
     pc2k = ops.cloud_select(rr, dr["sel2k"])
+    if rows is not None:
+        pc2k = pc2k[rows].contiguous()
+    B, dev = pc2k.shape[0], pc2k.device
     base = da._base_inputs(dr["base"], lab["rotation"], lab["translation"], lab["fsnet_scale"], lab["mean_shape"], lab["sym_info"],
                            dr["aug_bb"], dr["aug_rt_t"], dr["aug_rt_R"], lab["cat_id"], lab["nocs_scale"], lab["model_point"], dr["defor"])
-    view = dict(op=dr["op"], noise=dr["noise"], drop_ratio=dr["drop_ratio"], drop_u=dr["drop_u"], boxes=dr["boxes"], **_view_limits(ops_))
+    view = dict(op=dr["op"], noise=dr["noise"], drop_ratio=dr["drop_ratio"], drop_u=dr["drop_u"], boxes=dr["boxes"], **da.view_limits(ops_))
+    # padded (B, 2048, 4) outputs: tgp_gather_rows moves rows of a multiple of 4 floats
     out = ops.augment(pc2k, base=base, view=view, ld_out=4)
     shuf = dr["shuf"] if "shuf" in dr else shuffle(out["counts"])
     p1k = ops.farthest_points(out["pc"], 1024) if fps else dr["p1k"]
-    pcl = ops.gather_rows(out["pc"], p1k, torch.empty(D, 1024, 4, device=dev))
-    aug = ops.gather_rows(out["view"], shuf, torch.empty(D, 1024, 4, device=dev))
-    rows = dict(pcl_in=pcl, aug_pcl_in=aug, rotation=out["R"], translation=out["t"], fsnet_scale=out["s"], aug_flags=out["flags"],
-                aug_counts=out["counts"], shuf=shuf)
+    pcl = ops.gather_rows(out["pc"], p1k, torch.empty(B, 1024, 4, device=dev))
+    aug = ops.gather_rows(out["view"], shuf, torch.empty(B, 1024, 4, device=dev))
+    got = dict(pcl_in=pcl, aug_pcl_in=aug, rotation=out["R"], translation=out["t"], fsnet_scale=out["s"], aug_flags=out["flags"],
+               aug_counts=out["counts"], shuf=shuf)
     if fps:
-        rows.update(PC=out["pc"], pcl_index=p1k)
-    return rows
+        got.update(PC=out["pc"], pcl_index=p1k)
+    return got
+
+
+def _unpad(db):
+    """cut the clouds that _augment_rows pads to 4 columns back to 3, in place"""
+    for k in ("pcl_in", "aug_pcl_in", "PC"):
+        if k in db:
+            db[k] = db[k][..., :3].contiguous()
 
 
 def _train_batch_from_draws(items, dr, img_size=256, device="cuda", min_points=50, operators=None, pcl_select="random"):
-    """The host path's launches on GIVEN draws: ``dr`` holds host arrays under DRAW_KEYS, one row per item ('defor_on' / 'drop_bits'
-    absent: no mask deformation) -- e.g. the buffers a draws='device' batch made, read back.  The counts are read back and the
-    reference's rules applied on the host (_item_total; an item for which the host path raises counts as abandoned here).
+    """The host path's launches (_records, _augment_rows: the functions train_batch(draws='host') calls) on GIVEN draws: ``dr``
+    holds host arrays under DRAW_KEYS, one row per item ('defor_on' / 'drop_bits' absent: no mask deformation) -- e.g. the buffers a
+    draws='device' batch made, read back.  The counts are read back and the reference's rules applied on the host (_item_total; an
+    item for which the host path raises counts as abandoned here).
     -> (dict of train_batch's device tensors, one row per KEPT item, list of the kept items)"""
-    from . import data_augmentation as da
     dev = torch.device(device)
     ops_ = da.default_operators() if operators is None else list(operators)
     H, W = _check_items(items, None, 3, False)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    args, tabs, mval, camk = _upload_frames(items, dr["tabs"], up, H, W)
-    t = {k: up(np.asarray(v)) for k, v in dr.items() if k in DRAW_KEYS}
-    defor = (t["defor_on"], t["drop_bits"]) if "defor_on" in t else None
-    rr = ops.roi_cloud(*args, camk, roi_size=img_size, tables=tabs, mask_val=mval, cut_frac=0.15, defor=defor)
+    up = _pageable(dev)
+    t = {k: up(np.asarray(v)) for k, v in dr.items() if k in DRAW_KEYS and k != "tabs"}
+    rr, defor = _records(items, dr["tabs"], up, H, W, img_size, (t["defor_on"], t["drop_bits"]) if "defor_on" in t else None)
     counts = rr.counts.cpu().numpy()
     keep = []
     for d in range(len(items)):
@@ -600,18 +580,15 @@ def _train_batch_from_draws(items, dr, img_size=256, device="cuda", min_points=5
                 keep.append(d)
         except (ValueError, IndexError):
             pass
-    rows = _augment_rows(rr, t, _stack_labels(items, up), ops_, fps=pcl_select == "fps")
+    got = _augment_rows(rr, t, _stack_labels(items, up), ops_, fps=pcl_select == "fps")
     kt = up(np.asarray(keep, dtype=np.int64))
-    out = {k: v[kt].contiguous() for k, v in rows.items()}
-    for k in ("pcl_in", "aug_pcl_in", "PC"):
-        if k in out:
-            out[k] = out[k][..., :3].contiguous()
+    out = {k: v[kt].contiguous() for k, v in got.items()}
+    _unpad(out)
     return out, keep
 
 
 def _train_batch_device(items, seed, keys, batch_size, img_size, dev, min_points, ops_, persistence, roi_mask_pro, roi_mask_r, dzi,
                         keep_draws=False, clouds_only=False, fps=False):
-    from . import data_augmentation as da
     lib = da._lib
     D = len(items)
     B = D if batch_size is None else int(batch_size)
@@ -627,24 +604,21 @@ def _train_batch_device(items, seed, keys, batch_size, img_size, dev, min_points
     H, W = _check_items(items, roi_mask_pro, roi_mask_r, dzi)
     sc = _item_scalars(items, seed, keys, H, W, img_size, dzi, ops_)
     up = _uploader(dev)
-    args, tabs, mval, camk = _upload_frames(items, sc["tabs"], up, H, W)
     keys_t = up(keys.view(np.int64))
     dr = {k: up(sc[k]) for k in ("aug_bb", "aug_rt_t", "aug_rt_R", "base", "op", "drop_ratio", "boxes")}
-    dr["tabs"] = tabs
     defor = None
     if roi_mask_pro is not None:
-        band = ops.roi_band(*args, roi_size=img_size, tables=tabs, mask_val=mval)
-        defor = ops.draw_band_subset(band, up(sc["u_defor"]), float(roi_mask_pro), keys_t, seed, drop_words=_DROP_WORDS)
+        defor = lambda band: ops.draw_band_subset(band, up(sc["u_defor"]), float(roi_mask_pro), keys_t, seed, drop_words=_DROP_WORDS)
+    rr, defor = _records(items, sc["tabs"], up, H, W, img_size, defor)
+    dr["tabs"] = rr.tables
+    if defor is not None:
         dr["defor_on"], dr["drop_bits"] = defor
-    rr = ops.roi_cloud(*args, camk, roi_size=img_size, tables=tabs, mask_val=mval, cut_frac=0.15, defor=defor)
     status, slot, n_alive = ops.draw_alive(rr.counts, B, min_points, up(sc["forced"]))
     dr["sel2k"] = ops.draw_selection(rr.counts[:, 2], keys_t, seed, lib.SITE_SEL2K, 2048)
     if not fps:
         dr["p1k"] = ops.draw_selection(2048, keys_t, seed, lib.SITE_SEL1K, 1024)
     if clouds_only:
-        pc2k = ops.cloud_select(rr, dr["sel2k"])
-        pc1k = ops.gather_rows(torch.nn.functional.pad(pc2k, (0, 1)), dr["p1k"], torch.empty(D, 1024, 4, device=dev))
-        pc2k, pc1k = ops.gather_slots(slot, [pc2k, pc1k])
+        pc2k, pc1k = ops.gather_slots(slot, _two_clouds(rr, dr["sel2k"], dr["p1k"]))
         return dict(PC=pc2k, pcl_in=pc1k[..., :3].contiguous(), n_alive=n_alive.reshape(()), status=status, item_index=slot.long())
     jit = next((o for o in ops_ if isinstance(o, da.PcJitter)), None)
     dr.update(ops.draw_fill(keys_t, seed, 2048, defor=True, noise=(jit.std, jit.clip) if jit is not None else (0.0, 0.0), drop_u=True))
@@ -656,9 +630,7 @@ def _train_batch_device(items, seed, keys, batch_size, img_size, dev, min_points
     src = [rows[k] for k in rows if k != "shuf"] + [lab[k] for k in lab if k not in _POSE_KEYS] + [up(sc["op_index"])]
     got = ops.gather_slots(slot, src)
     db = dict(zip(names + ["aug_op"], got))
-    db["pcl_in"], db["aug_pcl_in"] = db["pcl_in"][..., :3].contiguous(), db["aug_pcl_in"][..., :3].contiguous()
-    if fps:
-        db["PC"] = db["PC"][..., :3].contiguous()
+    _unpad(db)
     db.update(n_alive=n_alive.reshape(()), status=status, item_index=slot.long())
     if persistence:            # no read here either: a failed cloud's images are zeros and 'pd_status' names the reason
         db["pdh1"], db["pdh2"], db["pd_status"] = ops.persistence_images(db["pcl_in"], check_status=False)
@@ -827,11 +799,7 @@ class TrainBatches(object):
         parts, at = fill_batch(indices, n, one)
         db = _merge(parts, len(indices))
         db["item_index"] = torch.as_tensor(np.asarray(at, dtype=np.int64)).to(self.device)
-        if self.tables is not None:
-            cid = db["cat_id"].reshape(-1).long()
-            for k, t in zip(CATEGORY_KEYS, self.tables):
-                db[k] = t.index_select(0, cid)
-        return db
+        return self._with_category_tables(db)
 
     def build_device(self, indices, spare_indices, epoch):
         """one draws='device' batch: the items at ``indices`` and their spares, on the current stream, nothing read back"""
@@ -842,6 +810,10 @@ class TrainBatches(object):
         pos = db["item_index"]
         idx_t = _uploader(self.device)(np.asarray(idx, dtype=np.int64))
         db["item_index"] = torch.where(pos >= 0, idx_t[pos.clamp(min=0)], pos)
+        return self._with_category_tables(db)
+
+    def _with_category_tables(self, db):
+        """adds the batch's points_category / pdh1_category / pdh2_category: the tables' rows at cat_id, gathered on the device"""
         if self.tables is not None:
             cid = db["cat_id"].reshape(-1).long()
             for k, t in zip(CATEGORY_KEYS, self.tables):
