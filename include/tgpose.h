@@ -1327,6 +1327,80 @@ typedef struct tgp_icp_args {
 int tgp_icp_max_points(void);
 int tgp_icp_refine(const tgp_icp_args *args, tgp_stream_t stream);
 
+/* ---- The supporting plane of depth frames (csrc/plane.hip; additive, ABI stays 8) ------------------------------------------------
+ * The dominant plane of S depth frames by RANSAC and total least squares (tgp_plane_fit), its removal from the frames
+ * (tgp_plane_cut), and the reference's weighted plane regression of point clouds (tgp_plane_lsq; tools/plane_utils.py).  DESIGN.md
+ * section 3 "The supporting plane" is the contract; tests/plane_ref.py restates it in NumPy.  No float atomics anywhere: every
+ * result is bit-repeatable, and a frame's (a cloud's) result depends on neither the other frames nor S.
+ *
+ * depth (S,H,W) uint16 millimetres, 0 invalid; camk (S,4) fx, fy, cx, cy; H, W < 32768, H*W < 2^24.  A valid pixel's point p is the
+ * one tgp_cloud_select / tgp_ball_select give for that pixel and depth (csrc/pixel_point.h; same bits).  A plane is (n0, n1, n2, d)
+ * float32 with n.p + d = 0, oriented so that d >= 0 (the camera, at the origin, is on the non-negative side).  The signed distance
+ * of p is dist(p) = ((n0*px + n1*py) + n2*pz) + d in float32, every product and sum rounded on its own.
+ *
+ * tgp_plane_fit, frame s:
+ *   Hypothesis h (0 <= h < hypotheses <= TGP_PLANE_MAX_HYPOTHESES): w = the Philox words of (seed, keys[s], TGP_PLANE_SITE, counter
+ *   h); pixel i_k = (uint64(w[k]) * (H*W)) >> 32 for k = 0, 1, 2, a flat index y*W + x; a, b, c their points.  The hypothesis is VOID
+ *   (count 0) when one of the three pixels is invalid, or when the cross product below has nn <= 1e-18.  Else, in float64 on the
+ *   float32 points, every product and sum rounded on its own (no fma): e = b - a, f = c - a, cr = (e_y f_z - e_z f_y, e_z f_x - e_x f_z,
+ *   e_x f_y - e_y f_x), nn = (cr_x cr_x + cr_y cr_y) + cr_z cr_z, n = cr / sqrt(nn), d = -((n_x a_x + n_y a_y) + n_z a_z); when d < 0
+ *   both are negated; n and d are then rounded once to float32.
+ *   Score: a valid pixel is an inlier of a plane when |dist(p)| <= tol.  counts[s][h] = the hypothesis's inliers over the frame
+ *   (integers, added with integer atomics); best = the largest count, the first index on ties.
+ *   Status 1 when counts[s][best] < max(min_inliers, 3) (no valid hypothesis included): plane = (0,0,0,0), final inliers 0.
+ *   Else the plane is hypothesis `best`, and refine_iters (0..TGP_PLANE_MAX_REFITS) times: over the inliers of the current plane the
+ *   float64 sums N, sum p (3) and sum p p^T (6, upper triangle) are taken in this FIXED order: the frame's flat pixels are cut into
+ *   groups of 8 consecutive indices; thread t of TGP_PLANE_FIT_THREADS adds its groups t, t + THREADS, ... in that order, the pixels
+ *   of a group in index order; the 64 lanes of a wave are joined by a shuffle tree (x += lane + 32, + 16, ... + 1), the waves in
+ *   wave order.  m = sum p / N; C_ab = sum p_a p_b - (sum p_a)(sum p_b) / N; the normal is the unit eigenvector of C's smallest
+ *   eigenvalue by cyclic Jacobi rotations in float64; d = -((n_x m_x + n_y m_y) + n_z m_z), negated with n when < 0, both rounded once
+ *   to float32.  A non-finite result: status 2, the plane of before the refit stays and the refits end.  The inliers are selected
+ *   again with the rounded plane.
+ * -> plane (S,4) float32; info (S,4) int32: status, counts[s][best], the inliers of the returned plane, the frame's valid pixels;
+ *    counts (S, hypotheses) int32: REQUIRED at this level, it is the accumulator of the scoring launch (ops.plane_fit allocates it
+ *    and returns it on request).
+ * TGP_EINVAL (before any launch): a NULL pointer, S, H or W < 1 or out of range, hypotheses outside [1, TGP_PLANE_MAX_HYPOTHESES],
+ * refine_iters outside [0, TGP_PLANE_MAX_REFITS], tol negative or not finite, min_inliers < 0.  TGP_EUNSUPPORTED: S > 65535. */
+#define TGP_PLANE_SITE 9      /* the draw site of the hypotheses (after TGP_MESH_SITE) */
+#define TGP_PLANE_MAX_HYPOTHESES 1024
+#define TGP_PLANE_MAX_REFITS 4
+#define TGP_PLANE_FIT_THREADS 1024
+typedef struct tgp_plane_fit_args {
+    const uint16_t *depth;
+    const float *camk;
+    const uint64_t *keys;           /* (S) */
+    uint64_t seed;
+    int S, H, W;
+    int hypotheses;
+    float tol;
+    int refine_iters, min_inliers;
+    float *plane;
+    int32_t *info;
+    int32_t *counts;
+} tgp_plane_fit_args;
+int tgp_plane_fit(const tgp_plane_fit_args *args, tgp_stream_t stream);
+/* out[s][y][x] = depth[s][y][x] when the pixel is valid and dist(p) > margin under plane[s], else 0: what is left is strictly
+ * above the plane's band, on the camera's side.  A frame whose info[s][0] (tgp_plane_fit's status) is not 0 is copied through.
+ * plane (S,4) and info (S,4) are DEVICE pointers: nothing visits the host between the fit and the cut.  side (S,H,W) uint8 or NULL:
+ * 0 invalid pixel, 2 dist > margin, 3 dist < -margin, 1 otherwise (within the band); it is computed from plane[s] whatever the
+ * status.  out may be depth itself.  margin >= 0.  Elementwise: bit-exact against the restatement. */
+int tgp_plane_cut(const uint16_t *depth, const float *plane, const int32_t *info, const float *camk, int S, int H, int W,
+                  float margin, uint16_t *out, uint8_t *side, tgp_stream_t stream);
+/* The weighted regression z = a x + b y + c of B clouds pc (B,n,3) float32 with weights w (B,n) float32 (tools/plane_utils.py:
+ * get_plane, get_plane_in_batch, get_plane_parameter), one workgroup per cloud.  M = sum w [x y 1]^T [x y 1] (six moments) and
+ * r = sum w z [x y 1]^T are float64 sums, each term ((w * u) * v, the first product exact) rounded on its own, in the order of
+ * tgp_plane_fit's sums with single points for groups and TGP_PLANE_LSQ_THREADS threads.  X = M^-1 r by the adjugate in float64.
+ * The system counts as SINGULAR when |det M| <= 1e-12 |M00 M11 M22| or det M is not finite (n = 1 and n = 2 always are): every
+ * output of that cloud is NaN -- the reference's torch.inverse raises on the CPU for an exactly singular matrix and returns
+ * non-finite or meaningless numbers otherwise; nothing is raised from the device.
+ * With q = ((a a + b b) + 1): dn = (a c, b c, -c) / (q + eps), normal = dn / |dn|, p2plane = c / sqrt(q), float64, rounded once.
+ * eps is 0 in get_plane and 1e-8 in get_plane_in_batch.
+ * -> X (B,3), normal (B,3), dn (B,3), p2plane (B) float32.  TGP_EINVAL: a NULL pointer, B or n < 1, eps negative or not
+ * finite. */
+#define TGP_PLANE_LSQ_THREADS 256
+int tgp_plane_lsq(const float *pc, const float *w, int B, int n, double eps, float *X, float *normal, float *dn, float *p2plane,
+                  tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

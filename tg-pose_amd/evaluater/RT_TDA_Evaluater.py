@@ -21,7 +21,7 @@ import torch
 from ..evaluation import load_data_eval as lde
 from ..evaluation.metrics import compute_degree_cm_mAP
 from ..losses.utils_v2.model_utils import calc_cd, calc_emd
-from ..pose import IcpRefine, infer_device
+from ..pose import IcpRefine, SupportPlane, infer_device
 
 SYNSET_NAMES = ['BG', 'bottle', 'bowl', 'camera', 'can', 'laptop', 'mug']                                   # :115
 MEAN_SHAPE_MM = {1: (87, 220, 89), 2: (165, 80, 165), 3: (88, 128, 156), 4: (68, 146, 72), 5: (346, 200, 335), 6: (146, 83, 114)}
@@ -170,7 +170,7 @@ class myEvaluater:
         return results
 
     def track(self, sequence, init, camK=lde.REAL_INTRINSICS, ratio=None, n_pts=1024, sampler=None, use_mask=True, refine=None,
-              init_from="net"):
+              init_from="net", support=None):
         """Follow objects through a depth sequence from their previous poses: no detector result after frame 0.
 
         sequence: iterable of frames {'depth' (H,W) uint16[, 'inst_mask' (H,W) uint8]}.  init: {'class_ids' (n,) 1-based category
@@ -192,6 +192,11 @@ class myEvaluater:
         previous pose is refined against the new crop -- the model-based tracker; pred_scales are carried through.  An object whose
         ICP status is not 0 (ops.ICP_STATUS) keeps its previous pose and scales; the results gain 'icp_status', 'icp_inliers'
         (int32) and 'icp_rmse' (float32), (n,) each.  Still nothing is read back between frames.
+
+        support (a pose.SupportPlane): the frame's dominant plane -- the table the objects stand on -- is found and cut out of the
+        depth on the device before the crop (ops.plane_fit with key = the frame's number and seed = self.seed, ops.plane_cut), so
+        that its pixels are in no crop; a frame without a plane (ops.PLANE_STATUS) is tracked uncut.  The results gain 'plane' (4,)
+        float32, 'plane_status' and 'plane_inliers' (int32 scalars).  Nothing is read back for it either.
         -> list over frames of {'pred_RTs' (n,4,4), 'pred_scales' (n,3), 'status' (n,) int32, 'tracked' (n,) bool} ndarrays."""
         if ratio is None:
             raise ValueError("track: ratio is required (the reference fixes none)")
@@ -199,6 +204,8 @@ class myEvaluater:
             raise ValueError("track: init_from must be 'net' or 'previous'")
         if refine is not None and not isinstance(refine, IcpRefine):
             raise TypeError("track: refine must be a pose.IcpRefine")
+        if support is not None and not isinstance(support, SupportPlane):
+            raise TypeError("track: support must be a pose.SupportPlane")
         if init_from == "previous" and refine is None:
             raise ValueError("track: init_from='previous' needs refine (without it nothing would move the poses)")
         sampler = sampler or (self.sampler if self.sampler in ("device", "fps") else "device")
@@ -217,20 +224,30 @@ class myEvaluater:
         results, pending = [], None
 
         def fetch(item):
-            r, s, st, done = item[:4]
+            r, s, st, done, icp, pl = item
             with torch.cuda.stream(self._fetch):
                 self._fetch.wait_event(done)
-                for x in (r, s, st) + item[4:]:
+                for x in (r, s, st) + icp + pl:
                     x.record_stream(self._fetch)
                 r, s, st = r.cpu().numpy(), s.cpu().numpy(), st.cpu().numpy()
-                icp = [x.cpu().numpy() for x in item[4:]]
+                icp = [x.cpu().numpy() for x in icp]
+                pl = [x.cpu().numpy() for x in pl]
             results.append(dict(pred_RTs=r, pred_scales=s, status=st, tracked=st == 0))
             if icp:
                 results[-1].update(icp_status=icp[0][:, 0].copy(), icp_inliers=icp[0][:, 1].copy(), icp_rmse=icp[1])
+            if pl:
+                results[-1].update(plane=pl[0][0].copy(), plane_status=pl[1][0, 0].copy(), plane_inliers=pl[1][0, 2].copy())
         for k, frame in enumerate(sequence):
             masks = inst_ids if inst_ids is not None and "inst_mask" in frame else None
             with torch.no_grad():
-                pts, ok, _, counts = lde.clouds_from_poses([frame], job_img, rts, scales, ratio, camK, n_pts=n_pts, sampler=sampler,
+                pl = ()
+                if support is not None:
+                    depth, inst, camk = lde._depth_frames([frame], camK, dev)
+                    depth, plane, pinfo = support(depth, camk, [k], self.seed)
+                    frame = dict(depth=depth) if inst is None else dict(depth=depth, inst_mask=inst)
+                    pl = (plane, pinfo)
+                frames = frame if support is not None else [frame]
+                pts, ok, _, counts = lde.clouds_from_poses(frames, job_img, rts, scales, ratio, camK, n_pts=n_pts, sampler=sampler,
                                                            masks=masks, seed=self.seed + k, fps_pool=self.fps_pool, device=dev,
                                                            return_counts=True)
                 if init_from == "net":
@@ -247,7 +264,7 @@ class myEvaluater:
                 scales = torch.where(ok[:, None], new_scales, scales)
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(dev))
-            item = (rts, scales, counts[:, 3].contiguous(), done) + icp
+            item = (rts, scales, counts[:, 3].contiguous(), done, icp, pl)
             if pending is not None:
                 fetch(pending)
             pending = item

@@ -2256,6 +2256,105 @@ def icp_refine(models, job_model, src, R, t, s, max_dist, *, src_count=None, mod
     return out + (corr,) if return_corr else out
 
 
+# ------------------------------------------------------------------------------------------------------------ the supporting plane
+PLANE_STATUS = {1: "no hypothesis reached min_inliers", 2: "a refit was not finite (the plane of before it is returned)"}
+
+
+def _plane_frames(depth, camk, who):
+    """depth (S,H,W) 16-bit and camk (S,4) float32, contiguous on one GPU -> (S, H, W); ValueError otherwise"""
+    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in (torch.int16, torch.uint16) and depth.dim() == 3
+            and depth.is_contiguous() and depth.numel() > 0):
+        raise ValueError("%s: depth must be a contiguous (S,H,W) 16-bit GPU tensor" % who)
+    S, H, W = depth.shape
+    if not (torch.is_tensor(camk) and camk.device == depth.device and camk.dtype == torch.float32 and camk.shape == (S, 4)
+            and camk.is_contiguous()):
+        raise ValueError("%s: camk must be a contiguous (S,4) float32 tensor on the depth's device" % who)
+    if S > 65535 or H >= 32768 or W >= 32768 or H * W >= 2 ** 24:
+        raise ValueError("%s: at most 65535 frames of fewer than 2^24 pixels, sides below 32768" % who)
+    return S, H, W
+
+
+def plane_fit(depth, camk, *, tol=0.004, hypotheses=256, seed=0, keys=None, refine_iters=2, min_inliers=100, return_counts=False):
+    """tgp_plane_fit (csrc/plane.hip; DESIGN.md section 3 "The supporting plane"): the dominant plane of each of the S frames of depth
+    (S,H,W) (int16-viewed uint16 millimetres, 0 invalid) with intrinsics camk (S,4) fx, fy, cx, cy, in one call.  ``hypotheses``
+    three-pixel planes per frame are drawn from the Philox words of (seed, keys[s]) (keys: (S) ints or an int64 tensor; default the
+    frame's index), scored by their count of pixels within ``tol`` metres, and the best is refitted ``refine_iters`` times by total
+    least squares over its inliers.  -> (plane (S,4) float32: unit normal and offset, n.p + d = 0, d >= 0; info (S,4) int32: status
+    (PLANE_STATUS), the best hypothesis's count, the final inliers, the valid pixels[; counts (S, hypotheses) int32]).  Nothing is
+    read back (plane_check_status does)."""
+    S, H, W = _plane_frames(depth, camk, "plane_fit")
+    if not (isinstance(hypotheses, int) and 1 <= hypotheses <= _lib.PLANE_MAX_HYPOTHESES):
+        raise ValueError("plane_fit: hypotheses must be an int in [1, %d]" % _lib.PLANE_MAX_HYPOTHESES)
+    if not (isinstance(refine_iters, int) and 0 <= refine_iters <= _lib.PLANE_MAX_REFITS):
+        raise ValueError("plane_fit: refine_iters must be an int in [0, %d]" % _lib.PLANE_MAX_REFITS)
+    if not (isinstance(min_inliers, int) and min_inliers >= 0):
+        raise ValueError("plane_fit: min_inliers must be an int >= 0")
+    if not (0.0 <= float(tol) < math.inf):
+        raise ValueError("plane_fit: tol must be a finite number >= 0")
+    dev = depth.device
+    if keys is None:
+        keys = torch.arange(S, dtype=torch.int64, device=dev)
+    elif not torch.is_tensor(keys):
+        import numpy as np
+        keys = torch.from_numpy(np.asarray([int(k) & (2 ** 64 - 1) for k in keys], dtype=np.uint64).view(np.int64)).to(dev)
+    if not (keys.dtype == torch.int64 and keys.device == dev and keys.shape == (S,) and keys.is_contiguous()):
+        raise ValueError("plane_fit: keys must be (S) = (%d) 64-bit integers on the depth's device" % S)
+    plane = torch.empty(S, 4, device=dev, dtype=torch.float32)
+    info = torch.empty(S, 4, device=dev, dtype=torch.int32)
+    counts = torch.empty(S, hypotheses, device=dev, dtype=torch.int32)
+    a = _lib.PlaneFitArgs(depth=_p(depth), camk=_p(camk), keys=_p(keys), seed=int(seed) & (2 ** 64 - 1), S=S, H=H, W=W,
+                          hypotheses=hypotheses, tol=float(tol), refine_iters=refine_iters, min_inliers=min_inliers, plane=_p(plane),
+                          info=_p(info), counts=_p(counts))
+    check(_lib.lib().tgp_plane_fit(ctypes.byref(a), _stream(depth)), "tgp_plane_fit")
+    return (plane, info, counts) if return_counts else (plane, info)
+
+
+def plane_cut(depth, plane, info, camk, margin=0.006, return_side=False):
+    """tgp_plane_cut: the frames of depth (S,H,W) without their plane: a pixel keeps its depth when its signed distance to plane[s]
+    is above ``margin`` metres (on the camera's side), else it becomes 0; a frame whose info[s, 0] is not 0 is copied through.  plane
+    (S,4) and info (S,4) are plane_fit's, read on the device.  -> out (S,H,W), the depth's dtype[, side (S,H,W) uint8: 0 invalid,
+    1 within the margin, 2 above, 3 below]."""
+    S, H, W = _plane_frames(depth, camk, "plane_cut")
+    dev = depth.device
+    if not (torch.is_tensor(plane) and plane.device == dev and plane.dtype == torch.float32 and plane.shape == (S, 4) and plane.is_contiguous()):
+        raise ValueError("plane_cut: plane must be a contiguous (S,4) float32 tensor on the depth's device")
+    if not (torch.is_tensor(info) and info.device == dev and info.dtype == torch.int32 and info.shape == (S, 4) and info.is_contiguous()):
+        raise ValueError("plane_cut: info must be a contiguous (S,4) int32 tensor on the depth's device")
+    if not (0.0 <= float(margin) < math.inf):
+        raise ValueError("plane_cut: margin must be a finite number >= 0")
+    out = torch.empty_like(depth)
+    side = torch.empty(S, H, W, device=dev, dtype=torch.uint8) if return_side else None
+    check(_lib.lib().tgp_plane_cut(_p(depth), _p(plane), _p(info), _p(camk), S, H, W, float(margin), _p(out), _p(side), _stream(depth)),
+          "tgp_plane_cut")
+    return (out, side) if return_side else out
+
+
+def plane_check_status(info, what="plane_fit"):
+    """one read of the (S,4) info words; raises TgpError naming the first frame without a plane"""
+    st = info[:, 0].cpu().tolist()
+    bad = [(j, s) for j, s in enumerate(st) if s != 0]
+    if bad:
+        raise _lib.TgpError("%s: frame %d: %s (%d of %d frames)" % (what, bad[0][0], PLANE_STATUS.get(bad[0][1], bad[0][1]), len(bad), len(st)))
+
+
+def plane_lsq(pc, w, eps=0.0):
+    """tgp_plane_lsq: the weighted regression z = a x + b y + c of the B clouds pc (B,n,3) with weights w (B,n), float32 on the GPU,
+    one launch.  -> (X (B,3) = a, b, c; normal (B,3); dn (B,3); p2plane (B)) float32, tools/plane_utils.py's formulas with its
+    ``eps`` added to the divisor of dn.  A singular system (n < 3, collinear points) gives NaN rows."""
+    if not (torch.is_tensor(pc) and pc.is_cuda and pc.dtype == torch.float32 and pc.dim() == 3 and pc.shape[2] == 3 and pc.is_contiguous()
+            and pc.shape[0] >= 1 and pc.shape[1] >= 1):
+        raise ValueError("plane_lsq: pc must be a contiguous (B,n,3) float32 GPU tensor, B, n >= 1")
+    B, n = pc.shape[:2]
+    if not (torch.is_tensor(w) and w.device == pc.device and w.dtype == torch.float32 and w.shape == (B, n) and w.is_contiguous()):
+        raise ValueError("plane_lsq: w must be a contiguous (B,n) float32 tensor on pc's device")
+    if not (0.0 <= float(eps) < math.inf):
+        raise ValueError("plane_lsq: eps must be a finite number >= 0")
+    X, normal, dn = (torch.empty(B, 3, device=pc.device, dtype=torch.float32) for _ in range(3))
+    p2 = torch.empty(B, device=pc.device, dtype=torch.float32)
+    check(_lib.lib().tgp_plane_lsq(_p(pc), _p(w), B, n, float(eps), _p(X), _p(normal), _p(dn), _p(p2), _stream(pc)), "tgp_plane_lsq")
+    return X, normal, dn, p2
+
+
 # ---------------------------------------------------------------------------------------------------------- the optimizer step
 def ranger_plan(table):
     """Check a host descriptor table (a ctypes array of _lib.RangerTensor) and fill its unit0 fields (tgp_ranger_plan, host only:

@@ -86,6 +86,23 @@ class IcpRefine(object):
         return refine_poses(self.models, self.job_model, clouds, RTs, self.max_dist, **self.kw)
 
 
+class SupportPlane(object):
+    """What myEvaluater.track(support=...) needs to take the supporting plane out of each frame before the crop: ops.plane_fit's
+    ``tol`` (the inlier band, metres), ``hypotheses`` and ``refine_iters``, and ops.plane_cut's ``margin`` (metres above the plane
+    below which a pixel goes).  __call__(depth (S,H,W), camk (S,4), keys, seed) -> (cut depth, plane (S,4), info (S,4)), device
+    tensors, nothing read back; a frame without a plane (info[:, 0] != 0) comes back uncut."""
+
+    def __init__(self, tol=0.004, margin=0.006, hypotheses=256, refine_iters=2, min_inliers=100):
+        if not (tol >= 0 and margin >= 0):
+            raise ValueError("SupportPlane: tol and margin must not be negative")
+        self.tol, self.margin, self.hypotheses, self.refine_iters, self.min_inliers = float(tol), float(margin), int(hypotheses), int(refine_iters), int(min_inliers)
+
+    def __call__(self, depth, camk, keys, seed):
+        plane, info = ops.plane_fit(depth, camk, tol=self.tol, hypotheses=self.hypotheses, seed=seed, keys=keys, refine_iters=self.refine_iters,
+                                    min_inliers=self.min_inliers)
+        return ops.plane_cut(depth, plane, info, camk, self.margin), plane, info
+
+
 def batched_inference(net, clouds, cat_ids, mean_shapes, syms, max_batch=256):
     """clouds: list over images of (n_det_i, N, 3) tensors (same N); cat_ids / mean_shapes / syms likewise.
     Returns a list over images of dicts {'pred_RTs': (n_det_i,4,4) ndarray, 'pred_scales': (n_det_i,3) ndarray}."""
