@@ -1401,6 +1401,50 @@ int tgp_plane_cut(const uint16_t *depth, const float *plane, const int32_t *info
 int tgp_plane_lsq(const float *pc, const float *w, int B, int n, double eps, float *X, float *normal, float *dn, float *p2plane,
                   tgp_stream_t stream);
 
+/* ---- Segments of depth frames (csrc/segment.hip; additive, ABI stays 8) ------------------------------------------------------------
+ * Connected-component labelling of S depth frames in one call: after tgp_plane_cut what is left of a frame are the objects on the
+ * table, and this says which pixels belong to which.  No reference counterpart.  DESIGN.md section 3 "Segments of a depth frame" is
+ * the contract; tests/segment_ref.py restates it in NumPy.  Every sum is an integer sum (integer atomics): the result is unique
+ * whatever order the workgroups run in, equal to the restatement bit for bit, and a frame's result depends on neither the other
+ * frames nor S.
+ *
+ * depth (S,H,W) uint16 millimetres, a pixel is valid when its depth is not 0 (tgp_plane_fit's rule); H, W < 32768, H*W < 2^24.
+ * Two valid pixels that are neighbours (connectivity 4: left / right / up / down; 8: the diagonals too) are JOINED when
+ * |z_p - z_q| <= max_step, on the millimetre values as ints (0 <= max_step <= 65535; 1 against 65535 is 65534 apart).  The
+ * components are the classes of that relation.  A component's root is its smallest flat index y*W + x; it QUALIFIES with at least
+ * min_pixels (>= 1) pixels; the qualifying components are ranked by ascending root; rank r < max_segments gets label r + 1, every
+ * other pixel label 0.
+ * -> labels (S,H,W) uint8;
+ *    info (S,4) int32: status (1: more components qualified than max_segments, the first max_segments in root order are kept),
+ *    segments kept, components that qualified, valid pixels;
+ *    stats (S, max_segments, TGP_SEG_STAT_COLS) int64, row l - 1 for label l, rows past the kept count zero: pixels, y1, x1, y2, x2
+ *    (the box, ends exclusive), root, sum x, sum y, sum z, sum x*z, sum y*z, min z (z in millimetres);
+ *    centers (S, max_segments, 3) float32 or NULL (needs camk (S,4) fx, fy, cx, cy, else camk may be NULL): the centroid of the
+ *    segment's points in metres, float64 on the integer sums with the float32 camk values widened, every operation rounded on its
+ *    own, rounded once to float32: Z = sum z / n / 1000, X = (sum x*z - cx * sum z) / (fx * n) / 1000, Y likewise with cy, fy;
+ *    rows past the kept count are NaN.
+ * workspace: tgp_segment_workspace_bytes(S,H,W) bytes of device memory, 16-byte aligned (two words per pixel plus counters);
+ * nothing in it needs initialising and nothing is kept between calls.
+ * TGP_EINVAL (before any launch): a NULL required pointer, centers without camk, S, H or W < 1 or out of range, max_step outside
+ * [0, 65535], connectivity not 4 or 8, min_pixels < 1, max_segments outside [1, TGP_SEG_MAX_SEGMENTS], workspace_bytes too small.
+ * TGP_EUNSUPPORTED: S > 65535.  tgp_segment_workspace_bytes returns TGP_EINVAL / TGP_EUNSUPPORTED by the same rule. */
+#define TGP_SEG_MAX_SEGMENTS 255
+#define TGP_SEG_STAT_COLS 12
+typedef struct tgp_segment_args {
+    const uint16_t *depth;
+    const float *camk;              /* may be NULL when centers is */
+    int S, H, W;
+    int max_step, connectivity, min_pixels, max_segments;
+    uint8_t *labels;
+    int32_t *info;
+    int64_t *stats;
+    float *centers;                 /* may be NULL */
+    void *workspace;
+    int64_t workspace_bytes;
+} tgp_segment_args;
+int64_t tgp_segment_workspace_bytes(int S, int H, int W);
+int tgp_segment_depth(const tgp_segment_args *args, tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,7 @@ import torch
 from ..evaluation import load_data_eval as lde
 from ..evaluation.metrics import compute_degree_cm_mAP
 from ..losses.utils_v2.model_utils import calc_cd, calc_emd
-from ..pose import IcpRefine, SupportPlane, infer_device
+from ..pose import IcpRefine, Segmenter, SupportPlane, infer_device
 
 SYNSET_NAMES = ['BG', 'bottle', 'bowl', 'camera', 'can', 'laptop', 'mug']                                   # :115
 MEAN_SHAPE_MM = {1: (87, 220, 89), 2: (165, 80, 165), 3: (88, 128, 156), 4: (68, 146, 72), 5: (346, 200, 335), 6: (146, 83, 114)}
@@ -168,6 +168,61 @@ class myEvaluater:
             results.extend(self._finish(pending))
         self.net1.graph_replay = was
         return results
+
+    def acquire(self, frame, class_ids, camK=lde.REAL_INTRINSICS, support=None, segmenter=None, n_pts=1024, sampler=None):
+        """The ``init`` that ``track`` takes, from one depth frame and a category: no detector result, no ground truth.
+
+        frame: {'depth' (H,W) uint16}.  class_ids: one 1-based category id for every segment, or a sequence with one id per kept
+        segment, in label order.  support (a pose.SupportPlane): the supporting plane is cut out first, with key 0 and seed =
+        self.seed as ``track`` cuts frame 0.  segmenter (a pose.Segmenter; default Segmenter()): the frame's connected components
+        (ops.segment_depth) are the objects.  sampler: 'device' (keyed draw, seed = self.seed) or 'fps'; default as in ``track``.
+
+        Everything is enqueued without a read-back: the cut, the segmentation, load_data_eval.clouds_from_segments over the
+        segmenter's max_segments slots, and ONE pose.infer_device forward over all of these slots (an empty slot's NaN cloud is zeroed;
+        objects are independent in eval mode) -- how many segments were kept is only known on the device.  Then everything is read
+        back once and cut down to the n kept segments.
+        -> {'class_ids' (n,), 'RTs' (n,4,4), 'scales' (n,3), 'inst_ids' (n,) = the labels 1..n, 'inst_mask' (H,W) uint8 = the label
+        image, 'boxes' (n,4) y1, x1, y2, x2 (ends exclusive), 'pixels' (n,), 'centers' (n,3) metres, 'ok' (n,) bool (False: the ROI
+        path found the segment's cloud invalid, its pose is meaningless), 'info' (4,) int32 = ops.segment_depth's}; n = 0 for a
+        frame without a segment."""
+        if support is not None and not isinstance(support, SupportPlane):
+            raise TypeError("acquire: support must be a pose.SupportPlane")
+        segmenter = Segmenter() if segmenter is None else segmenter
+        if not isinstance(segmenter, Segmenter):
+            raise TypeError("acquire: segmenter must be a pose.Segmenter")
+        sampler = sampler or (self.sampler if self.sampler in ("device", "fps") else "device")
+        if sampler not in ("device", "fps"):
+            raise ValueError("acquire: sampler must be 'device' or 'fps' (nothing is read back before the forward)")
+        one = np.ndim(class_ids) == 0
+        ids = np.asarray(class_ids).astype(np.int64).reshape(-1)
+        if not all(int(c) in MEAN_SHAPE_MM for c in ids):
+            raise ValueError("acquire: class_ids must be 1-based category ids in [1, %d]" % len(MEAN_SHAPE_MM))
+        dev, M = self.device, segmenter.max_segments
+        if not one and len(ids) > M:
+            raise ValueError("acquire: %d class_ids for at most %d segments" % (len(ids), M))
+        slot_ids = np.full(M, ids[0] if len(ids) else 1, dtype=np.int64)
+        if not one:
+            slot_ids[:len(ids)] = ids
+        t = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float32)).to(dev)
+        cat = t(slot_ids - 1).reshape(-1, 1)
+        mean = t([MEAN_SHAPE_MM[int(c)] for c in slot_ids]).reshape(-1, 3) / 1000.0
+        sym = t([SYM_INFO[int(c)] for c in slot_ids]).reshape(-1, 4)
+        with torch.no_grad():
+            depth, _, camk = lde._depth_frames([frame], camK, dev)
+            if support is not None:
+                depth = support(depth, camk, [0], self.seed)[0]
+            seg = segmenter(depth, camk)
+            pts, ok = lde.clouds_from_segments(depth, seg, camk, n_pts=n_pts, sampler=sampler, seed=self.seed, fps_pool=self.fps_pool)
+            rts, scales = infer_device(self.net1, torch.nan_to_num(pts, nan=0.0), cat, mean, sym, self.max_batch,
+                                       eval_outputs_only=self.eval_outputs_only)
+        info = seg.info[0].cpu().numpy()                                                     # the read-back
+        n = int(info[1])
+        if not one and len(ids) != n:
+            raise ValueError("acquire: %d class_ids for %d segments" % (len(ids), n))
+        stats = seg.stats[0, :n].cpu().numpy()
+        return dict(class_ids=slot_ids[:n].copy(), RTs=rts[:n].cpu().numpy(), scales=scales[:n].cpu().numpy(),
+                    inst_ids=np.arange(1, n + 1, dtype=np.int32), inst_mask=seg.labels[0].cpu().numpy(), boxes=stats[:, 1:5].copy(),
+                    pixels=stats[:, 0].copy(), centers=seg.centers[0, :n].cpu().numpy(), ok=ok[:n].cpu().numpy(), info=info)
 
     def track(self, sequence, init, camK=lde.REAL_INTRINSICS, ratio=None, n_pts=1024, sampler=None, use_mask=True, refine=None,
               init_from="net", support=None):

@@ -205,6 +205,63 @@ def clouds_from_frames(frames, camK=REAL_INTRINSICS, img_size=256, n_pts=1024, s
     return [c if alive else None for c, alive in zip(out.split(rc.per_frame), keep_frame)]
 
 
+# ------------------------------------------------------------------------------------------- clouds from segments (no detector)
+def _segment_windows(boxes, H, W):
+    """get_bbox and _windows for (..., 4) int64 boxes (y1, x1, y2, x2) on the device -> (..., 3) int32 {cmin+cmax, rmin+rmax, s}:
+    the same integers, step by step (every quantity is non-negative where Python's and torch's integer division could differ)"""
+    y1, x1, y2, x2 = boxes.unbind(-1)
+    size = (((torch.maximum(y2 - y1, x2 - x1) // 40) + 1) * 40).clamp(max=440)
+    half = size // 2
+    cy, cx = (y1 + y2) // 2, (x1 + x2) // 2
+    rmin, rmax, cmin, cmax = cy - half, cy + half, cx - half, cx + half
+    zero = torch.zeros_like(rmin)
+    rmax, rmin = torch.where(rmin < 0, rmax - rmin, rmax), torch.where(rmin < 0, zero, rmin)
+    cmax, cmin = torch.where(cmin < 0, cmax - cmin, cmax), torch.where(cmin < 0, zero, cmin)
+    rmin, rmax = torch.where(rmax > 480, rmin - (rmax - 480), rmin), rmax.clamp(max=480)
+    cmin, cmax = torch.where(cmax > 640, cmin - (cmax - 640), cmin), cmax.clamp(max=640)
+    s = torch.maximum(rmax - rmin, cmax - cmin).clamp(max=max(H, W))
+    return torch.stack([cmin + cmax, rmin + rmax, s], dim=-1).int()
+
+
+def clouds_from_segments(depth, segments, camK=REAL_INTRINSICS, img_size=256, n_pts=1024, sampler="device", seed=0, fps_pool=4096):
+    """The ROI path of clouds_from_frames fed from a label image instead of a detector's masks and boxes: slot m of frame s
+    (``segments`` = ops.segment_depth's result for ``depth`` (S,H,W), M = segments.max_segments slots per frame) is detection
+    s * M + m, its mask the pixels labelled m + 1, its box the segment's (stats columns 1..4), its window get_bbox's of that box --
+    all of it device arithmetic, nothing is read back.  camK: one (3,3) matrix, one per frame, or the (S,4) fx, fy, cx, cy tensor
+    on the device.  sampler 'device' (the keyed draw of tgp_cloud_sample under ``seed``) or 'fps'.
+    -> (clouds (S*M, n_pts, 3), ok (S*M,) bool).  An empty slot (and a segment the ROI path finds invalid) has NaN rows and ok
+    False.  The clouds equal clouds_from_frames' for M mask channels per frame holding the same masks and boxes, bit for bit."""
+    if sampler not in ("device", "fps"):
+        raise ValueError("sampler must be 'device' or 'fps'")
+    if sampler == "fps" and not 1 <= int(fps_pool) <= ops.fps_max_points():
+        raise ValueError("fps_pool must be in [1, %d] (ops.fps_max_points())" % ops.fps_max_points())
+    if not isinstance(segments, ops.Segments):
+        raise TypeError("clouds_from_segments: segments must be an ops.Segments")
+    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dim() == 3 and depth.shape == segments.labels.shape
+            and depth.device == segments.labels.device):
+        raise ValueError("clouds_from_segments: depth must be the (S,H,W) GPU tensor the segments were made from")
+    dev = depth.device
+    S, H, W = depth.shape
+    M = segments.max_segments
+    if torch.is_tensor(camK) and camK.is_cuda:
+        camk = camK
+    else:
+        camK = np.asarray(camK, dtype=np.float32)
+        camK = np.broadcast_to(camK, (S, 3, 3)) if camK.ndim == 2 else camK
+        camk = np.stack([camK[:, 0, 0], camK[:, 1, 1], camK[:, 0, 2], camK[:, 1, 2]], axis=1).astype(np.float32)
+        camk = torch.from_numpy(np.ascontiguousarray(camk)).to(dev, non_blocking=True)
+    det_img = torch.arange(S, device=dev, dtype=torch.int32).repeat_interleave(M)
+    mask_val = torch.arange(1, M + 1, device=dev, dtype=torch.int32).repeat(S)
+    window = _segment_windows(segments.stats[:, :, 1:5], H, W).reshape(S * M, 3).contiguous()     # an empty slot: the box (0,0,0,0)'s
+    rr = ops.roi_cloud(depth, segments.labels.reshape(-1), det_img.long() * (H * W), torch.ones_like(det_img), det_img, window, camk,
+                       roi_size=img_size, mask_val=mask_val)
+    if sampler == "fps":
+        return _fps_clouds(RoiClouds(rr, [M] * S), n_pts, fps_pool)
+    out = ops.cloud_sample(rr, n_pts, seed)
+    ok = (rr.counts[:, 2] > 0) & (rr.counts[:, 0] > 1) & (rr.counts[:, 1] > 1)
+    return out, ok
+
+
 # ------------------------------------------------------------------------------------------------ clouds from poses (the ball crop)
 def pose_balls(RTs, scales, ratio):
     """The balls crop_ball_from_depth_image (network/point_sample/pc_sample_sphere.py:350-357) crops round poses: centres = the

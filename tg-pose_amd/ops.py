@@ -2355,6 +2355,74 @@ def plane_lsq(pc, w, eps=0.0):
     return X, normal, dn, p2
 
 
+# --------------------------------------------------------------------------------------------------------- segments of depth frames
+SEG_MAX_SEGMENTS, SEG_STAT_COLS = _lib.SEG_MAX_SEGMENTS, _lib.SEG_STAT_COLS
+SEG_STATUS = {1: "more components qualified than max_segments (the first max_segments in root order are kept)"}
+
+
+class Segments(object):
+    """What segment_depth returns, all on the depth's device: ``labels`` (S,H,W) uint8 (0: no segment, l: segment l), ``info`` (S,4)
+    int32 (status, segments kept, components that qualified, valid pixels), ``stats`` (S, max_segments, 12) int64 (row l - 1 for label
+    l: pixels, y1, x1, y2, x2 with exclusive ends, root, sum x, sum y, sum z, sum x z, sum y z, min z; rows past the kept count zero),
+    ``centers`` (S, max_segments, 3) float32 metres or None (rows past the kept count NaN), and the parameters of the call."""
+
+    def __init__(self, labels, info, stats, centers, max_step, connectivity, min_pixels, max_segments):
+        self.labels, self.info, self.stats, self.centers = labels, info, stats, centers
+        self.max_step, self.connectivity, self.min_pixels, self.max_segments = max_step, connectivity, min_pixels, max_segments
+
+    def by_size(self):
+        """(S, max_segments) int64: per frame the rows of ``stats`` by descending pixel count, equal counts (the empty rows among
+        them) by ascending label -- a stable sort on the device, nothing is read back"""
+        return torch.sort(self.stats[:, :, 0], dim=1, descending=True, stable=True).indices
+
+
+def segment_depth(depth, *, max_step=10, connectivity=4, min_pixels=50, max_segments=32, camk=None):
+    """tgp_segment_depth (csrc/segment.hip; DESIGN.md section 3 "Segments of a depth frame"): the connected components of each of the
+    S frames of depth (S,H,W) (int16-viewed uint16 millimetres, 0 invalid), in one call.  Neighbouring valid pixels (``connectivity``
+    4 or 8) are joined when their depths differ by at most ``max_step`` millimetres; components of at least ``min_pixels`` pixels are
+    numbered 1, 2, ... by their smallest flat index, ``max_segments`` (at most SEG_MAX_SEGMENTS) of them at most.  camk (S,4) fx,
+    fy, cx, cy: the segments' centroids are returned too.  -> Segments.  Nothing is read back (seg_check_status does)."""
+    if not (isinstance(max_step, int) and 0 <= max_step <= 65535):
+        raise ValueError("segment_depth: max_step must be an int in [0, 65535]")
+    if connectivity not in (4, 8):
+        raise ValueError("segment_depth: connectivity must be 4 or 8")
+    if not (isinstance(min_pixels, int) and min_pixels >= 1):
+        raise ValueError("segment_depth: min_pixels must be an int >= 1")
+    if not (isinstance(max_segments, int) and 1 <= max_segments <= SEG_MAX_SEGMENTS):
+        raise ValueError("segment_depth: max_segments must be an int in [1, %d]" % SEG_MAX_SEGMENTS)
+    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in (torch.int16, torch.uint16) and depth.dim() == 3
+            and depth.is_contiguous() and depth.numel() > 0):
+        raise ValueError("segment_depth: depth must be a contiguous (S,H,W) 16-bit GPU tensor")
+    S, H, W = depth.shape
+    if S > 65535 or H >= 32768 or W >= 32768 or H * W >= 2 ** 24:
+        raise ValueError("segment_depth: at most 65535 frames of fewer than 2^24 pixels, sides below 32768")
+    if camk is not None and not (torch.is_tensor(camk) and camk.device == depth.device and camk.dtype == torch.float32
+                                 and camk.shape == (S, 4) and camk.is_contiguous()):
+        raise ValueError("segment_depth: camk must be a contiguous (S,4) float32 tensor on the depth's device")
+    dev = depth.device
+    nbytes = _lib.lib().tgp_segment_workspace_bytes(S, H, W)
+    if nbytes < 0:
+        check(nbytes, "tgp_segment_workspace_bytes")
+    work = torch.empty(nbytes // 4, device=dev, dtype=torch.int32)
+    labels = torch.empty(S, H, W, device=dev, dtype=torch.uint8)
+    info = torch.empty(S, 4, device=dev, dtype=torch.int32)
+    stats = torch.empty(S, max_segments, SEG_STAT_COLS, device=dev, dtype=torch.int64)
+    centers = torch.empty(S, max_segments, 3, device=dev, dtype=torch.float32) if camk is not None else None
+    a = _lib.SegmentArgs(depth=_p(depth), camk=_p(camk), S=S, H=H, W=W, max_step=max_step, connectivity=int(connectivity),
+                         min_pixels=min(min_pixels, 2 ** 31 - 1), max_segments=max_segments, labels=_p(labels), info=_p(info),
+                         stats=_p(stats), centers=_p(centers), workspace=_p(work), workspace_bytes=nbytes)
+    check(_lib.lib().tgp_segment_depth(ctypes.byref(a), _stream(depth)), "tgp_segment_depth")
+    return Segments(labels, info, stats, centers, max_step, int(connectivity), min_pixels, max_segments)
+
+
+def seg_check_status(info, what="segment_depth"):
+    """one read of the (S,4) info words; raises TgpError naming the first frame whose segments were cut off at max_segments"""
+    st = info[:, 0].cpu().tolist()
+    bad = [(j, s) for j, s in enumerate(st) if s != 0]
+    if bad:
+        raise _lib.TgpError("%s: frame %d: %s (%d of %d frames)" % (what, bad[0][0], SEG_STATUS.get(bad[0][1], bad[0][1]), len(bad), len(st)))
+
+
 # ---------------------------------------------------------------------------------------------------------- the optimizer step
 def ranger_plan(table):
     """Check a host descriptor table (a ctypes array of _lib.RangerTensor) and fill its unit0 fields (tgp_ranger_plan, host only:

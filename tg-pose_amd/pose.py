@@ -103,6 +103,27 @@ class SupportPlane(object):
         return ops.plane_cut(depth, plane, info, camk, self.margin), plane, info
 
 
+class Segmenter(object):
+    """What myEvaluater.acquire(segmenter=...) needs to split a (cut) depth frame into objects: ops.segment_depth's ``max_step``
+    (millimetres between joined neighbours), ``connectivity`` (4 or 8), ``min_pixels`` (smaller components are dropped) and
+    ``max_segments``.  __call__(depth (S,H,W), camk (S,4)) -> ops.Segments with centroids, device tensors, nothing read back."""
+
+    def __init__(self, max_step=10, connectivity=4, min_pixels=50, max_segments=32):
+        if not (isinstance(max_step, int) and 0 <= max_step <= 65535):
+            raise ValueError("Segmenter: max_step must be an int in [0, 65535]")
+        if connectivity not in (4, 8):
+            raise ValueError("Segmenter: connectivity must be 4 or 8")
+        if not (isinstance(min_pixels, int) and min_pixels >= 1):
+            raise ValueError("Segmenter: min_pixels must be an int >= 1")
+        if not (isinstance(max_segments, int) and 1 <= max_segments <= ops.SEG_MAX_SEGMENTS):
+            raise ValueError("Segmenter: max_segments must be an int in [1, %d]" % ops.SEG_MAX_SEGMENTS)
+        self.max_step, self.connectivity, self.min_pixels, self.max_segments = max_step, int(connectivity), min_pixels, max_segments
+
+    def __call__(self, depth, camk):
+        return ops.segment_depth(depth, max_step=self.max_step, connectivity=self.connectivity, min_pixels=self.min_pixels,
+                                 max_segments=self.max_segments, camk=camk)
+
+
 def batched_inference(net, clouds, cat_ids, mean_shapes, syms, max_batch=256):
     """clouds: list over images of (n_det_i, N, 3) tensors (same N); cat_ids / mean_shapes / syms likewise.
     Returns a list over images of dicts {'pred_RTs': (n_det_i,4,4) ndarray, 'pred_scales': (n_det_i,3) ndarray}."""
