@@ -36,13 +36,17 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float *__restrict
         partial[(int64_t)blockIdx.y * C + c] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
-__global__ void bn_finish_kernel(const float *__restrict__ partial, int chunks, int C, float inv_rows, float *__restrict__ out)
+// out[c] = shift[c] + sum / rows (shift == NULL: 0).  The mean pass sums x - K with K = the column's first row and adds K back here: a
+// constant column then has mean == the constant and variance == 0 exactly, as the one-pass form gives (summing the raw values did
+// not: 0.1 over 1025 rows came back 2.4e-7 off, and the variance 5.7e-14 instead of 0).
+__global__ void bn_finish_kernel(const float *__restrict__ partial, int chunks, int C, float inv_rows, const float *__restrict__ shift,
+                                 float *__restrict__ out)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     float s = 0.f;
     for (int k = 0; k < chunks; ++k) s += partial[(int64_t)k * C + c];
-    out[c] = s * inv_rows;
+    out[c] = shift ? shift[c] + s * inv_rows : s * inv_rows;
 }
 
 // ---- round 3: the statistics in ONE pass of 16-byte loads --------------------------------------------------------------------
@@ -50,9 +54,14 @@ __global__ void bn_finish_kernel(const float *__restrict__ partial, int chunks, 
 // BatchNorm passes of the trainer's step ran at ~1.8 TB/s.  Here a workgroup owns 256 columns x one chunk of BNV_CHUNK rows,
 // a thread a column quad (float4 loads: 1 KB per wave instruction) and every fourth row; it accumulates the sums of d and d^2 with
 // d = x - K, K = the chunk's first row -- shifted sums: the cancellation in S2 - S1^2 / n is relative to (mean - K)^2 ~ var,
-// not to mean^2, so a single pass stays well conditioned however far the column's mean is from zero.  The chunks' (n, mean, M2)
-// are merged IN CHUNK ORDER by one thread per column with the parallel-variance update (Chan et al.): deterministic,
-// bit-repeatable, no float atomics; agrees with the two-pass values to ~1e-7 relative (test_bn_train_kernels_vs_torch).
+// not to mean^2.  The chunks' (n, mean, M2) are merged IN CHUNK ORDER by one thread per column with the parallel-variance update
+// (Chan et al.): deterministic, bit-repeatable, no float atomics.  Conditioning as measured on the float32 restatement of exactly this
+// algorithm (tests/bn_ref.py, test_bn_kernels_cpu.py::test_conditioning_table; 2049 rows, relative error of the variance against
+// float64, this pass / the two-pass kernels above): benign columns 7e-8 / 7e-8; mean = 1e3 std 1.6e-6 / 2.5e-7 -- the shift removes
+// the cancellation, but the merge still forms mean_b = K + s1 / n_b at the magnitude of the mean, so the pass is NOT indifferent to
+// how far the mean is from zero; a K that is itself an outlier of 1e3 std 9.4e-6 / 1.9e-7 (the cancellation is then relative to
+// (mean - K)^2 >> var); a constant column exactly 0 in both.  DESIGN.md, "Training-mode forward", has the table;
+// tests/test_bn_kernels_gpu.py holds the kernels to four times those figures, column kind by column kind.
 #define BNV_CHUNK 256      // rows per workgroup: enough workgroups (C / 256 x rows / 256) to hide HBM latency -- with 1024-row chunks the
                            // 16-byte kernels were SLOWER than the 4-byte ones (a quarter of the workgroups: 8 waves per CU)
 
@@ -195,10 +204,11 @@ extern "C" int tgp_bn_stats_running(const float *x, int ld, int64_t rows, int C,
     const int chunks = tgp_cdiv(rows, BN_CHUNK);
     const dim3 grid(tgp_cdiv(C, 64), chunks), block(256);
     const float inv = (float)(1.0 / (double)rows);
-    hipLaunchKernelGGL(bn_partial_kernel<false>, grid, block, 0, tgp_hs(stream), x, ld, rows, C, (const float *)nullptr, workspace);
-    hipLaunchKernelGGL(bn_finish_kernel, dim3(tgp_cdiv(C, 256)), dim3(256), 0, tgp_hs(stream), workspace, chunks, C, inv, mean);
+    hipLaunchKernelGGL(bn_partial_kernel<false>, grid, block, 0, tgp_hs(stream), x, ld, rows, C, x /* center[c] = row 0 */, workspace);
+    hipLaunchKernelGGL(bn_finish_kernel, dim3(tgp_cdiv(C, 256)), dim3(256), 0, tgp_hs(stream), workspace, chunks, C, inv, x, mean);
     hipLaunchKernelGGL(bn_partial_kernel<true>, grid, block, 0, tgp_hs(stream), x, ld, rows, C, (const float *)mean, workspace);
-    hipLaunchKernelGGL(bn_finish_kernel, dim3(tgp_cdiv(C, 256)), dim3(256), 0, tgp_hs(stream), workspace, chunks, C, inv, var);
+    hipLaunchKernelGGL(bn_finish_kernel, dim3(tgp_cdiv(C, 256)), dim3(256), 0, tgp_hs(stream), workspace, chunks, C, inv,
+                       (const float *)nullptr, var);
     if (run_mean)
         hipLaunchKernelGGL(bn_running_update_kernel, dim3(tgp_cdiv(C, 256)), dim3(256), 0, tgp_hs(stream), mean, var, C, run_mean, run_var,
                            momentum, unbias, batches);
