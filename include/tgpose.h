@@ -1445,6 +1445,56 @@ typedef struct tgp_segment_args {
 int64_t tgp_segment_workspace_bytes(int S, int H, int W);
 int tgp_segment_depth(const tgp_segment_args *args, tgp_stream_t stream);
 
+/* ---- Pose verification against depth frames (csrc/verify.hip; additive, ABI stays 8) -------------------------------------------------
+ * Render-and-compare: J jobs in one call, job j = (frame job_img[j], mesh job_mesh[j], pose job_pose[j] (3,4) fp32 [s R | t]).  The
+ * rendered surface of a job is what tgp_render_depth gives for a scene of that one instance -- the same vertex arithmetic, snapping,
+ * drop rules, coverage, z and winner, d_r = rint(1000 z), 0 above 65535 -- but only inside the job's own projected box, and no
+ * frame of it is written: every pixel the job covers is compared with the frame's d_o = depth[job_img[j], y, x] in registers and
+ * falls in exactly one class, in this order:
+ *    nodata     d_o == 0 or d_r == 0
+ *    occluded   d_o + tau < d_r            (something stands in front; not held against the pose)
+ *    match      |d_o - d_r| <= tau
+ *    violation  d_o > d_r + tau            (the sensor saw through the model)
+ * DESIGN.md section 3 "Pose verification" is the contract; tests/verify_ref.py restates it in NumPy on tests/render_ref.py.
+ * depth (S,H,W) uint16 millimetres, camk (S,4) fp32 fx, fy, cx, cy, the mesh set as tgp_render_depth takes it, job_img / job_mesh
+ * (J) int32, mask (S,H,W) uint8 with job_mask_val (J) uint8, or both NULL: all in device memory, read on the device only.
+ * -> counts (J, TGP_VERIFY_COLS) int32: rendered (pixels covered), match, violation, occluded, nodata, in_mask (covered pixels whose
+ *    mask byte is job_mask_val[j]; 0 without a mask), abs_sum (sum of |d_o - d_r| over the match pixels), dropped (triangles dropped
+ *    by the near rule and by the guard band, summed); rendered == match + violation + occluded + nodata.
+ *    score (J) fp32 = (float)match / (float)(rendered - occluded), correctly rounded; 0 when the denominator is 0.
+ * A job whose job_img is outside [0,S) or whose mesh renders nothing by the renderer's rules gives a row of zeros.  Integer atomics
+ * only: two calls give identical bytes.  workspace: tgp_verify_workspace_bytes(J, max_verts, max_faces) bytes, 16-byte aligned,
+ * nothing in it needs initialising.  Four kernels on the caller's stream, nothing read by the host; graph-capturable.
+ * TGP_EINVAL (before any launch): a NULL required pointer (with J > 0: the job arrays and the workspace), mask without job_mask_val,
+ * S, M, H, W, n_verts, n_faces, max_verts or max_faces < 1, J < 0, tau < 0, near <= 0 or not finite, workspace_bytes too small.
+ * TGP_EUNSUPPORTED: J > TGP_VERIFY_MAX_JOBS, tau > TGP_VERIFY_MAX_TAU (abs_sum <= tau * rendered stays below 2^31), H*W >= 2^24
+ * (the conversions to fp32 stay exact), H or W > 16384, max_faces >= tgp_render_max_faces().  tgp_verify_workspace_bytes returns
+ * TGP_EINVAL / TGP_EUNSUPPORTED by the same rule.  J == 0 launches nothing and returns 0. */
+#define TGP_VERIFY_COLS 8
+#define TGP_VERIFY_MAX_JOBS 65535
+#define TGP_VERIFY_MAX_TAU 1000
+typedef struct tgp_verify_args {
+    const uint16_t *depth;
+    const float *camk;
+    const float *verts;
+    const int32_t *faces;
+    const int32_t *vptr, *fptr;
+    int M, n_verts, n_faces, max_verts, max_faces;
+    const int32_t *job_img, *job_mesh;
+    const float *job_pose;
+    const uint8_t *mask;            /* may be NULL */
+    const uint8_t *job_mask_val;    /* required with mask, not read without */
+    int S, H, W, J;
+    int tau;
+    float near;
+    int32_t *counts;
+    float *score;
+    void *workspace;
+    int64_t workspace_bytes;
+} tgp_verify_args;
+int64_t tgp_verify_workspace_bytes(int J, int max_verts, int max_faces);
+int tgp_pose_verify(const tgp_verify_args *args, tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

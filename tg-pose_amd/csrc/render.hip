@@ -11,26 +11,15 @@
 //   render_bbox_kernel     one thread per instance: the min / max accumulators -> (y1, x1, y2, x2)
 //
 // Integer add / min / max (visible, bbox, dropped) are the only atomics: order-independent, so two calls give identical bytes.
-#include "tgp_common.h"
+// The per-vertex, per-triangle and per-record arithmetic is raster.h's, shared with pose verification (verify.hip).
+#include "raster.h"
 
 #define RENDER_MAX_FACES (1 << 24)
 #define RENDER_MAX_INSTANCES 255
 #define RENDER_MAX_SIDE 16384
-#define RENDER_GUARD 4194304.f // 2^22 sub-pixel units
-#define RENDER_TILE 16
-#define RENDER_THREADS (RENDER_TILE * RENDER_TILE)
-#define RENDER_CAP (2 * RENDER_THREADS) // records held before a raster sweep: one chunk always fits behind a sweep's threshold
-
-struct RenderRec {
-    long long e[3]; // edge functions at the tile's first sample point
-    int dx[3], dy[3];
-    float iz[3];
-    float area;
-    uint32_t lo;   // slot << 24 | face
-    uint32_t open; // bit k: edge k is a top or left edge (E_k == 0 is inside)
-    int pad[2];
-};
-static_assert(sizeof(RenderRec) == 80, "RenderRec");
+#define RENDER_TILE RASTER_TILE
+#define RENDER_THREADS RASTER_THREADS
+#define RENDER_CAP RASTER_CAP
 
 struct RenderMesh {
     int vbase, nv, fbase, nf;
@@ -89,28 +78,8 @@ __global__ __launch_bounds__(256) void render_vertex_kernel(const tgp_render_arg
     if (inst >= a.I) return;
     RenderMesh m;
     if (!render_mesh(a, inst, m) || v >= m.nv) return;
-    const float *p = a.verts + (size_t)(m.vbase + v) * 3;
-    const float *T = a.inst_pose + (size_t)inst * 12;
-    const float *K = a.camk + (size_t)render_scene_of(a, inst) * 4;
-    const float x = p[0], y = p[1], z = p[2];
-    const float px = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
-    const float py = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
-    const float pz = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
-    int4 r = make_int4(0, 0, 0, 1);
-    if (pz > a.near) { // false for a NaN too
-        const float u = (K[0] * (px / pz) + K[2]) * 256.f;
-        const float w = (K[1] * (py / pz) + K[3]) * 256.f;
-        if (fabsf(u) <= RENDER_GUARD && fabsf(w) <= RENDER_GUARD) // false for a NaN too
-            r = make_int4((int)rintf(u), (int)rintf(w), __float_as_int(1.f / pz), 0);
-        else
-            r.w = 2;
-    }
-    render_vrec(a)[(size_t)inst * a.max_verts + v] = r;
-}
-
-__device__ __forceinline__ long long render_orient(int ax, int ay, int bx, int by, int cx, int cy)
-{
-    return (long long)(bx - ax) * (cy - ay) - (long long)(by - ay) * (cx - ax);
+    render_vrec(a)[(size_t)inst * a.max_verts + v] = raster_vertex(a.verts + (size_t)(m.vbase + v) * 3, a.inst_pose + (size_t)inst * 12,
+                                                                    a.camk + (size_t)render_scene_of(a, inst) * 4, a.near);
 }
 
 __global__ __launch_bounds__(256) void render_box_kernel(const tgp_render_args a, int blocks_per_inst)
@@ -124,24 +93,15 @@ __global__ __launch_bounds__(256) void render_box_kernel(const tgp_render_args a
     short4 box = make_short4(0x7fff, -1, 0x7fff, -1); // x first, x last, y first, y last: empty, it meets no tile
     if (f0 >= 0 && f0 < m.nv && f1 >= 0 && f1 < m.nv && f2 >= 0 && f2 < m.nv) {
         const int4 *vr = render_vrec(a) + (size_t)inst * a.max_verts;
-        const int4 v0 = vr[f0], v1 = vr[f1], v2 = vr[f2];
-        if (v0.w == 1 || v1.w == 1 || v2.w == 1) {
-            atomicAdd(a.dropped + (size_t)render_scene_of(a, inst) * 2, 1);
-        } else if (v0.w | v1.w | v2.w) {
-            atomicAdd(a.dropped + (size_t)render_scene_of(a, inst) * 2 + 1, 1);
-        } else if (render_orient(v0.x, v0.y, v1.x, v1.y, v2.x, v2.y) != 0) {
-            // samples sit at multiples of 256: the first at or after the least coordinate, the last at or before the greatest
-            const int x0 = max((min(min(v0.x, v1.x), v2.x) + 255) >> 8, 0), x1 = min(max(max(v0.x, v1.x), v2.x) >> 8, a.W - 1);
-            const int y0 = max((min(min(v0.y, v1.y), v2.y) + 255) >> 8, 0), y1 = min(max(max(v0.y, v1.y), v2.y) >> 8, a.H - 1);
-            if (x0 <= x1 && y0 <= y1) box = make_short4((short)x0, (short)x1, (short)y0, (short)y1);
-        }
+        const int rule = raster_box(vr[f0], vr[f1], vr[f2], a.W, a.H, box);
+        if (rule) atomicAdd(a.dropped + (size_t)render_scene_of(a, inst) * 2 + (rule - 1), 1);
     }
     render_boxes(a)[(size_t)inst * a.max_faces + t] = box;
 }
 
 __global__ __launch_bounds__(RENDER_THREADS) void render_tile_kernel(const tgp_render_args a, int tiles_x, int tiles_y)
 {
-    __shared__ RenderRec s_rec[RENDER_CAP];
+    __shared__ RasterRec s_rec[RENDER_CAP];
     __shared__ int s_n;
     __shared__ int s_vis[RENDER_MAX_INSTANCES + 1];
     __shared__ int s_bb[RENDER_MAX_INSTANCES + 1][4];
@@ -167,24 +127,7 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_tile_kernel(const tgp_r
 
     unsigned long long key = ~0ull;
 
-    auto sweep = [&](int n) {
-        for (int r = 0; r < n; ++r) {
-            const RenderRec &q = s_rec[r];
-            const long long e0 = q.e[0] + (long long)(lj * q.dx[0] - li * q.dy[0]) * 256;
-            const long long e1 = q.e[1] + (long long)(lj * q.dx[1] - li * q.dy[1]) * 256;
-            const long long e2 = q.e[2] + (long long)(lj * q.dx[2] - li * q.dy[2]) * 256;
-            const uint32_t open = q.open;
-            const bool in = (e0 > 0 || (e0 == 0 && (open & 1))) && (e1 > 0 || (e1 == 0 && (open & 2))) &&
-                            (e2 > 0 || (e2 == 0 && (open & 4)));
-            if (in) {
-                const float w0 = (float)e0 / q.area, w1 = (float)e1 / q.area, w2 = (float)e2 / q.area;
-                const float invz = (w0 * q.iz[0] + w1 * q.iz[1]) + w2 * q.iz[2];
-                const float z = 1.f / invz;
-                const unsigned long long k64 = ((unsigned long long)__float_as_uint(z) << 32) | q.lo;
-                key = min(key, k64);
-            }
-        }
-    };
+    auto sweep = [&](int n) { raster_sweep(s_rec, n, li, lj, key); };
 
     for (int slot = 0; slot < ninst; ++slot) {
         const int inst = s0 + slot;
@@ -198,30 +141,8 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_tile_kernel(const tgp_r
                 const short4 b = boxes[t];
                 if (b.x <= tx1 && b.y >= tx0 && b.z <= ty1 && b.w >= ty0) { // false for an empty box
                     const int32_t *f = a.faces + (size_t)(m.fbase + t) * 3;
-                    const int4 v0 = vr[f[0]];
-                    int4 v1 = vr[f[1]], v2 = vr[f[2]];
-                    long long area = render_orient(v0.x, v0.y, v1.x, v1.y, v2.x, v2.y);
-                    if (area < 0) { // both windings render: the second and third vertex change places
-                        const int4 tmp = v1;
-                        v1 = v2, v2 = tmp;
-                        area = -area;
-                    }
-                    RenderRec &q = s_rec[atomicAdd(&s_n, 1)]; // at most RENDER_CAP - 256 held + 256 of this chunk
-                    const int ox = tx0 * 256, oy = ty0 * 256;
-                    q.e[0] = render_orient(v1.x, v1.y, v2.x, v2.y, ox, oy);
-                    q.e[1] = render_orient(v2.x, v2.y, v0.x, v0.y, ox, oy);
-                    q.e[2] = render_orient(v0.x, v0.y, v1.x, v1.y, ox, oy);
-                    q.dx[0] = v2.x - v1.x, q.dy[0] = v2.y - v1.y;
-                    q.dx[1] = v0.x - v2.x, q.dy[1] = v0.y - v2.y;
-                    q.dx[2] = v1.x - v0.x, q.dy[2] = v1.y - v0.y;
-                    uint32_t open = 0;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k)
-                        if (q.dy[k] < 0 || (q.dy[k] == 0 && q.dx[k] > 0)) open |= 1u << k;
-                    q.open = open;
-                    q.iz[0] = __int_as_float(v0.z), q.iz[1] = __int_as_float(v1.z), q.iz[2] = __int_as_float(v2.z);
-                    q.area = (float)area;
-                    q.lo = ((uint32_t)slot << 24) | (uint32_t)t;
+                    // at most RENDER_CAP - 256 records held + 256 of this chunk
+                    raster_setup(s_rec[atomicAdd(&s_n, 1)], vr[f[0]], vr[f[1]], vr[f[2]], tx0, ty0, ((uint32_t)slot << 24) | (uint32_t)t);
                 }
             }
             __syncthreads();
@@ -248,8 +169,7 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_tile_kernel(const tgp_r
         } else {
             const float z = __uint_as_float((uint32_t)(key >> 32));
             const int slot = (int)((uint32_t)key >> 24), face = (int)((uint32_t)key & 0xffffffu);
-            const float mm = rintf(z * 1000.f);
-            a.depth[o] = mm <= 65535.f ? (uint16_t)mm : (uint16_t)0;
+            a.depth[o] = (uint16_t)raster_depth_mm(z);
             a.mask[o] = a.inst_id[s0 + slot];
             if (a.z) a.z[o] = z;
             if (a.face) a.face[o] = face;

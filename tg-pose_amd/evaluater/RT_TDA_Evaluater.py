@@ -21,7 +21,7 @@ import torch
 from ..evaluation import load_data_eval as lde
 from ..evaluation.metrics import compute_degree_cm_mAP
 from ..losses.utils_v2.model_utils import calc_cd, calc_emd
-from ..pose import IcpRefine, Segmenter, SupportPlane, infer_device
+from ..pose import IcpRefine, Segmenter, SupportPlane, Verify, infer_device
 
 SYNSET_NAMES = ['BG', 'bottle', 'bowl', 'camera', 'can', 'laptop', 'mug']                                   # :115
 MEAN_SHAPE_MM = {1: (87, 220, 89), 2: (165, 80, 165), 3: (88, 128, 156), 4: (68, 146, 72), 5: (346, 200, 335), 6: (146, 83, 114)}
@@ -185,6 +185,20 @@ class myEvaluater:
         image, 'boxes' (n,4) y1, x1, y2, x2 (ends exclusive), 'pixels' (n,), 'centers' (n,3) metres, 'ok' (n,) bool (False: the ROI
         path found the segment's cloud invalid, its pose is meaningless), 'info' (4,) int32 = ops.segment_depth's}; n = 0 for a
         frame without a segment."""
+        return self._acquire(frame, class_ids, camK, support, segmenter, n_pts, sampler, None)
+
+    def acquire_verified(self, frame, class_ids, verify, camK=lde.REAL_INTRINSICS, support=None, segmenter=None, n_pts=1024, sampler=None):
+        """``acquire`` with its poses checked against the frame they came from.  verify (a pose.Verify; its job_mesh holds one mesh
+        index for every segment, or one per kept segment in label order): the poses of all the segmenter's slots are verified in the
+        same enqueue, before the one read-back -- against the cut depth when ``support`` is given, with the label image as the mask
+        and each segment's label as its mask byte -- and the result gains 'verify_counts' (n,8) int32 (ops.VERIFY_COUNTS),
+        'verify_score' (n,) float32 and 'verified' (n,) bool = score >= verify.min_score; n = 0 gives them with no row.
+        (A method of its own: ``acquire``'s parameter list is part of what its callers and tests rely on.)"""
+        if not isinstance(verify, Verify):
+            raise TypeError("acquire_verified: verify must be a pose.Verify")
+        return self._acquire(frame, class_ids, camK, support, segmenter, n_pts, sampler, verify)
+
+    def _acquire(self, frame, class_ids, camK, support, segmenter, n_pts, sampler, verify):
         if support is not None and not isinstance(support, SupportPlane):
             raise TypeError("acquire: support must be a pose.SupportPlane")
         segmenter = Segmenter() if segmenter is None else segmenter
@@ -215,17 +229,29 @@ class myEvaluater:
             pts, ok = lde.clouds_from_segments(depth, seg, camk, n_pts=n_pts, sampler=sampler, seed=self.seed, fps_pool=self.fps_pool)
             rts, scales = infer_device(self.net1, torch.nan_to_num(pts, nan=0.0), cat, mean, sym, self.max_batch,
                                        eval_outputs_only=self.eval_outputs_only)
+            vf = None
+            if verify is not None:
+                # every slot is a job (how many are kept is only known on the device); an empty slot's row is cut off below
+                vmesh = verify.job_mesh
+                if vmesh.numel() != 1:                       # one per kept segment: the slots behind them take the first
+                    vmesh = torch.cat([vmesh, vmesh[:1].expand(max(M - vmesh.numel(), 0))])[:M].contiguous()
+                vf = verify.on(vmesh)(depth, camk, rts, scales, mask=seg.labels,
+                                      job_mask_val=torch.arange(1, M + 1, device=dev).to(torch.uint8))
         info = seg.info[0].cpu().numpy()                                                     # the read-back
         n = int(info[1])
         if not one and len(ids) != n:
             raise ValueError("acquire: %d class_ids for %d segments" % (len(ids), n))
+        if vf is not None and verify.job_mesh.numel() not in (1, n):
+            raise ValueError("acquire_verified: %d mesh indices for %d segments" % (verify.job_mesh.numel(), n))
         stats = seg.stats[0, :n].cpu().numpy()
-        return dict(class_ids=slot_ids[:n].copy(), RTs=rts[:n].cpu().numpy(), scales=scales[:n].cpu().numpy(),
+        out = {} if vf is None else dict(verify_counts=vf["counts"][:n].cpu().numpy(), verify_score=vf["score"][:n].cpu().numpy(),
+                                         verified=vf["verified"][:n].cpu().numpy())
+        return dict(out, class_ids=slot_ids[:n].copy(), RTs=rts[:n].cpu().numpy(), scales=scales[:n].cpu().numpy(),
                     inst_ids=np.arange(1, n + 1, dtype=np.int32), inst_mask=seg.labels[0].cpu().numpy(), boxes=stats[:, 1:5].copy(),
                     pixels=stats[:, 0].copy(), centers=seg.centers[0, :n].cpu().numpy(), ok=ok[:n].cpu().numpy(), info=info)
 
     def track(self, sequence, init, camK=lde.REAL_INTRINSICS, ratio=None, n_pts=1024, sampler=None, use_mask=True, refine=None,
-              init_from="net", support=None):
+              init_from="net", support=None, verify=None):
         """Follow objects through a depth sequence from their previous poses: no detector result after frame 0.
 
         sequence: iterable of frames {'depth' (H,W) uint16[, 'inst_mask' (H,W) uint8]}.  init: {'class_ids' (n,) 1-based category
@@ -252,6 +278,13 @@ class myEvaluater:
         depth on the device before the crop (ops.plane_fit with key = the frame's number and seed = self.seed, ops.plane_cut), so
         that its pixels are in no crop; a frame without a plane (ops.PLANE_STATUS) is tracked uncut.  The results gain 'plane' (4,)
         float32, 'plane_status' and 'plane_inliers' (int32 scalars).  Nothing is read back for it either.
+
+        verify (a pose.Verify: a mesh set, one mesh index per object, tau, min_score): once the frame's poses are final -- after
+        ``refine`` when given -- each is rendered and compared with that frame's depth (ops.pose_verify, one call for all objects on
+        the same stream; the cut depth when ``support`` is given; the frame's 'inst_mask' with inst_ids as the mask when both are
+        there).  The results gain 'verify_counts' (n,8) int32 (ops.VERIFY_COUNTS), 'verify_score' (n,) float32 and 'verified' (n,)
+        bool = score >= verify.min_score, fetched with the others.  Verification reports and does not gate: the poses carried to
+        the next frame, and every other result, are those of the same call without ``verify``.
         -> list over frames of {'pred_RTs' (n,4,4), 'pred_scales' (n,3), 'status' (n,) int32, 'tracked' (n,) bool} ndarrays."""
         if ratio is None:
             raise ValueError("track: ratio is required (the reference fixes none)")
@@ -261,6 +294,8 @@ class myEvaluater:
             raise TypeError("track: refine must be a pose.IcpRefine")
         if support is not None and not isinstance(support, SupportPlane):
             raise TypeError("track: support must be a pose.SupportPlane")
+        if verify is not None and not isinstance(verify, Verify):
+            raise TypeError("track: verify must be a pose.Verify")
         if init_from == "previous" and refine is None:
             raise ValueError("track: init_from='previous' needs refine (without it nothing would move the poses)")
         sampler = sampler or (self.sampler if self.sampler in ("device", "fps") else "device")
@@ -269,6 +304,8 @@ class myEvaluater:
         dev = self.device
         ids = np.asarray(init["class_ids"]).astype(np.int64)
         n = len(ids)
+        if verify is not None:
+            verify.jobs(n)                                   # one mesh index per object, or one for all: refused here, before any launch
         t = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float32)).to(dev)
         cat = t(ids - 1).reshape(-1, 1)
         mean = t([MEAN_SHAPE_MM[int(c)] for c in ids]).reshape(-1, 3) / 1000.0
@@ -279,29 +316,34 @@ class myEvaluater:
         results, pending = [], None
 
         def fetch(item):
-            r, s, st, done, icp, pl = item
+            r, s, st, done, icp, pl, vf = item
             with torch.cuda.stream(self._fetch):
                 self._fetch.wait_event(done)
-                for x in (r, s, st) + icp + pl:
+                for x in (r, s, st) + icp + pl + vf:
                     x.record_stream(self._fetch)
                 r, s, st = r.cpu().numpy(), s.cpu().numpy(), st.cpu().numpy()
                 icp = [x.cpu().numpy() for x in icp]
                 pl = [x.cpu().numpy() for x in pl]
+                vf = [x.cpu().numpy() for x in vf]
             results.append(dict(pred_RTs=r, pred_scales=s, status=st, tracked=st == 0))
             if icp:
                 results[-1].update(icp_status=icp[0][:, 0].copy(), icp_inliers=icp[0][:, 1].copy(), icp_rmse=icp[1])
             if pl:
                 results[-1].update(plane=pl[0][0].copy(), plane_status=pl[1][0, 0].copy(), plane_inliers=pl[1][0, 2].copy())
+            if vf:
+                results[-1].update(verify_counts=vf[0], verify_score=vf[1], verified=vf[2])
         for k, frame in enumerate(sequence):
             masks = inst_ids if inst_ids is not None and "inst_mask" in frame else None
             with torch.no_grad():
                 pl = ()
-                if support is not None:
+                on_device = support is not None or verify is not None
+                if on_device:                                # the frame is uploaded here, once: the crop reads the same tensors
                     depth, inst, camk = lde._depth_frames([frame], camK, dev)
-                    depth, plane, pinfo = support(depth, camk, [k], self.seed)
+                    if support is not None:
+                        depth, plane, pinfo = support(depth, camk, [k], self.seed)
+                        pl = (plane, pinfo)
                     frame = dict(depth=depth) if inst is None else dict(depth=depth, inst_mask=inst)
-                    pl = (plane, pinfo)
-                frames = frame if support is not None else [frame]
+                frames = frame if on_device else [frame]
                 pts, ok, _, counts = lde.clouds_from_poses(frames, job_img, rts, scales, ratio, camK, n_pts=n_pts, sampler=sampler,
                                                            masks=masks, seed=self.seed + k, fps_pool=self.fps_pool, device=dev,
                                                            return_counts=True)
@@ -317,9 +359,15 @@ class myEvaluater:
                     icp = (info, rmse)
                 rts = torch.where(ok[:, None, None], new_rts, rts)
                 scales = torch.where(ok[:, None], new_scales, scales)
+                vf = ()
+                if verify is not None:
+                    vmask = inst.view(torch.uint8) if masks is not None else None
+                    vids = torch.as_tensor(np.asarray(masks), dtype=torch.uint8).to(dev) if masks is not None else None
+                    v = verify(depth, camk, rts, scales, job_img=job_img, mask=vmask, job_mask_val=vids)
+                    vf = (v["counts"], v["score"], v["verified"])
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(dev))
-            item = (rts, scales, counts[:, 3].contiguous(), done, icp, pl)
+            item = (rts, scales, counts[:, 3].contiguous(), done, icp, pl, vf)
             if pending is not None:
                 fetch(pending)
             pending = item

@@ -1321,6 +1321,70 @@ def render_depth(meshset, scene_ptr, inst_mesh, inst_id, inst_pose, camk, H, W, 
     return out
 
 
+# the columns of pose_verify's counts
+VERIFY_COUNTS = ("rendered", "match", "violation", "occluded", "nodata", "in_mask", "abs_sum", "dropped")
+VERIFY_MAX_JOBS, VERIFY_MAX_TAU = _lib.VERIFY_MAX_JOBS, _lib.VERIFY_MAX_TAU
+
+
+def pose_verify(meshset, depth, camk, job_img, job_mesh, job_pose, tau=5, near=0.01, mask=None, job_mask_val=None):
+    """Render-and-compare of J poses against depth frames in one call (tgp_pose_verify, csrc/verify.hip; DESIGN.md section 3 "Pose
+    verification").  Job j renders mesh job_mesh[j] of the set at job_pose[j] -- exactly render_depth's surface for that one instance
+    -- inside its own projected box only, and compares it with frame job_img[j] pixel by pixel; no frame is written.  All tensors on
+    the mesh set's GPU: depth (S,H,W) 16-bit millimetres (0: no data), camk (S,4) float32 = fx, fy, cx, cy, job_img and job_mesh (J)
+    int32, job_pose (J,3,4) float32 [s R | t] (model -> camera, metres), mask (S,H,W) uint8 with job_mask_val (J) uint8, or neither.
+    tau: the tolerance in millimetres, an int in [0, VERIFY_MAX_TAU].
+    -> dict: counts (J,8) int32 in the order of VERIFY_COUNTS -- with d_r the rendered and d_o the frame's depth a covered pixel is
+    nodata (d_o or d_r is 0), else occluded (d_o + tau < d_r), else match (|d_o - d_r| <= tau), else violation; in_mask: covered
+    pixels whose mask byte is the job's; abs_sum: the sum of |d_o - d_r| over the match pixels; dropped: triangles the near rule and
+    the guard band dropped -- and score (J) float32 = match / (rendered - occluded), 0 where nothing is left to compare.  A job whose
+    frame or mesh index is out of range gives zeros.  Nothing synchronises."""
+    if not isinstance(meshset, MeshSet):
+        raise TypeError("pose_verify: meshset must be an ops.MeshSet")
+    dev = meshset.verts.device
+    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in (torch.int16, torch.uint16) and depth.is_contiguous()):
+        raise TypeError("pose_verify: depth must be a contiguous 16-bit GPU tensor")
+    given = [(depth, "depth", None), (camk, "camk", torch.float32), (job_img, "job_img", torch.int32), (job_mesh, "job_mesh", torch.int32),
+             (job_pose, "job_pose", torch.float32)]
+    if (mask is None) != (job_mask_val is None):
+        raise ValueError("pose_verify: mask and job_mask_val come together")
+    if mask is not None:
+        given += [(mask, "mask", torch.uint8), (job_mask_val, "job_mask_val", torch.uint8)]
+    for t, name, dt in given:
+        if dt is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise TypeError("pose_verify: %s must be a contiguous %s GPU tensor" % (name, str(dt).replace("torch.", "")))
+        if t.device != dev:
+            raise ValueError("pose_verify: %s is not on the mesh set's device" % name)
+    if depth.dim() != 3 or depth.numel() == 0:
+        raise ValueError("pose_verify: depth must be (S,H,W)")
+    S, H, W = depth.shape
+    J = job_img.numel()
+    if camk.shape != (S, 4) or job_img.dim() != 1 or job_mesh.shape != (J,) or job_pose.shape != (J, 3, 4):
+        raise ValueError("pose_verify: camk (S,4), job_img (J), job_mesh (J), job_pose (J,3,4) are expected")
+    if mask is not None and (mask.shape != (S, H, W) or job_mask_val.shape != (J,)):
+        raise ValueError("pose_verify: mask (S,H,W) and job_mask_val (J) are expected")
+    if not (isinstance(tau, int) and 0 <= tau <= VERIFY_MAX_TAU):
+        raise ValueError("pose_verify: tau must be an int in [0, %d] (millimetres)" % VERIFY_MAX_TAU)
+    if not float(near) > 0.0:
+        raise ValueError("pose_verify: near must be positive")
+    if J > VERIFY_MAX_JOBS or H * W >= 2 ** 24:
+        raise ValueError("pose_verify: at most %d jobs and frames of fewer than 2^24 pixels" % VERIFY_MAX_JOBS)
+    out = {"counts": torch.empty(J, len(VERIFY_COUNTS), device=dev, dtype=torch.int32), "score": torch.empty(J, device=dev, dtype=torch.float32)}
+    if J == 0:
+        return out
+    max_v, max_f = max(meshset.n_verts), max(meshset.n_faces)
+    nbytes = _lib.lib().tgp_verify_workspace_bytes(J, max_v, max_f)
+    if nbytes < 0:
+        check(nbytes, "tgp_verify_workspace_bytes")
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    a = _lib.VerifyArgs(depth=_p(depth), camk=_p(camk), verts=_p(meshset.verts), faces=_p(meshset.faces), vptr=_p(meshset.vptr),
+                        fptr=_p(meshset.fptr), M=len(meshset), n_verts=meshset.verts.shape[0], n_faces=meshset.faces.shape[0],
+                        max_verts=max_v, max_faces=max_f, job_img=_p(job_img), job_mesh=_p(job_mesh), job_pose=_p(job_pose), mask=_p(mask),
+                        job_mask_val=_p(job_mask_val), S=S, H=H, W=W, J=J, tau=tau, near=float(near), counts=_p(out["counts"]),
+                        score=_p(out["score"]), workspace=_p(ws), workspace_bytes=nbytes)
+    check(_lib.lib().tgp_pose_verify(ctypes.byref(a), _stream(job_pose)), "tgp_pose_verify")
+    return out
+
+
 def canonicalize(points, gR, p_g, f_g, p_r, f_r, p_t, p_s, sym):
     """R_DCD pose normalisation -> (points_re_n (B,n,3), R (B,3,3))"""
     c = lambda t: _f32(t.contiguous(), "arg")

@@ -124,6 +124,68 @@ class Segmenter(object):
                                  max_segments=self.max_segments, camk=camk)
 
 
+def verify_job_pose(RTs, scales=None):
+    """The (J,3,4) float32 pose ops.pose_verify renders a mesh at, from the project's 4x4 poses, on their device.  scales None: the
+    mesh is in the model's units and RTs = [s R | t] takes it to the camera in metres as it stands -- the convention of
+    IcpRefine's models (refine_poses applies s R m + t to the model's points).  scales (J,3): the mesh is NORMALISED, each axis
+    spanning one unit about the origin, and the object's size along its axes is carried by ``scales`` as in pose_balls: the
+    linear part becomes RTs[:3,:3] @ diag(scales)."""
+    P = RTs[:, :3, :4].float()
+    if scales is not None:
+        P = torch.cat([P[:, :, :3] * scales.float()[:, None, :], P[:, :, 3:]], dim=2)
+    return P.contiguous()
+
+
+def verify_poses(meshset, job_mesh, depth, camk, RTs, job_img=None, scales=None, tau=5, near=0.01, mask=None, job_mask_val=None):
+    """Render-and-compare (ops.pose_verify) of the project's 4x4 poses [s R | t] against depth frames (S,H,W) in millimetres with
+    intrinsics camk (S,4), as refine_poses is ops.icp_refine's 4x4 form.  job_mesh (J) int32: each pose's mesh in ``meshset``;
+    job_img (J) int32: its frame (default: frame 0 for every job); scales: see verify_job_pose.  The job poses are built on the
+    device; nothing is read back.  -> {'counts' (J,8) int32 in ops.VERIFY_COUNTS' order, 'score' (J,) float32}."""
+    if job_img is None:
+        job_img = torch.zeros(RTs.shape[0], dtype=torch.int32, device=RTs.device)
+    return ops.pose_verify(meshset, depth, camk, job_img, job_mesh, verify_job_pose(RTs, scales), tau=tau, near=near, mask=mask,
+                           job_mask_val=job_mask_val)
+
+
+class Verify(object):
+    """What myEvaluater.track(verify=...) and acquire_verified need to check their poses against the frame they came from:
+    ``meshset`` (ops.MeshSet), ``job_mesh`` (one mesh index per object; kept as an int32 tensor on the set's device; a single
+    index serves every object), ops.pose_verify's ``tau`` (millimetres) and ``near``, and ``min_score``: an object is 'verified'
+    when its score reaches it.  The meshes are in the model's units and are posed by RTs = [s R | t] as they stand -- the models of
+    IcpRefine built from the same set (ops.IcpModels.from_meshset) follow the same convention; with ``normalised`` the meshes span
+    one unit per axis and the poses' linear part is RTs[:3,:3] @ diag(scales) (verify_job_pose).
+    __call__(depth (S,H,W), camk (S,4), RTs (J,4,4), scales (J,3), job_img, mask, job_mask_val) -> {'counts', 'score', 'verified'
+    (J,) bool}, device tensors, nothing read back.  Verification reports; it changes no pose."""
+
+    def __init__(self, meshset, job_mesh, tau=5, min_score=0.5, near=0.01, normalised=False):
+        self.job_mesh = ops._mesh_jobs(meshset, job_mesh, "Verify")
+        if not (isinstance(tau, int) and 0 <= tau <= ops.VERIFY_MAX_TAU):
+            raise ValueError("Verify: tau must be an int in [0, %d] (millimetres)" % ops.VERIFY_MAX_TAU)
+        if not 0.0 <= float(min_score) <= 1.0:
+            raise ValueError("Verify: min_score must be in [0, 1]")
+        if not float(near) > 0.0:
+            raise ValueError("Verify: near must be positive")
+        self.meshset, self.tau, self.min_score, self.near, self.normalised = meshset, tau, float(min_score), float(near), bool(normalised)
+
+    def on(self, job_mesh):
+        """the same check for other objects"""
+        return Verify(self.meshset, job_mesh, self.tau, self.min_score, self.near, self.normalised)
+
+    def jobs(self, n):
+        """job_mesh for n objects: as given, or the single index n times"""
+        if self.job_mesh.numel() == 1 and n != 1:
+            return self.job_mesh.expand(n).contiguous()
+        if self.job_mesh.numel() != n:
+            raise ValueError("Verify: %d mesh indices for %d objects" % (self.job_mesh.numel(), n))
+        return self.job_mesh
+
+    def __call__(self, depth, camk, RTs, scales=None, job_img=None, mask=None, job_mask_val=None):
+        out = verify_poses(self.meshset, self.jobs(RTs.shape[0]), depth, camk, RTs, job_img, scales if self.normalised else None, self.tau,
+                           self.near, mask, job_mask_val)
+        out["verified"] = out["score"] >= self.min_score
+        return out
+
+
 def batched_inference(net, clouds, cat_ids, mean_shapes, syms, max_batch=256):
     """clouds: list over images of (n_det_i, N, 3) tensors (same N); cat_ids / mean_shapes / syms likewise.
     Returns a list over images of dicts {'pred_RTs': (n_det_i,4,4) ndarray, 'pred_scales': (n_det_i,3) ndarray}."""
