@@ -1495,6 +1495,109 @@ typedef struct tgp_verify_args {
 int64_t tgp_verify_workspace_bytes(int J, int max_verts, int max_faces);
 int tgp_pose_verify(const tgp_verify_args *args, tgp_stream_t stream);
 
+/* ---- BOP pose errors: the point-based errors (csrc/poseerr.hip; additive, ABI stays 8) -------------------------------------------
+ * ADD, ADD-S (ADI), MSSD and MSPD of J (estimate, ground truth) pose pairs in one call.  DESIGN.md section 3 "BOP pose errors" is
+ * the contract; tests/bop_ref.py restates it in NumPy.  Job j: the P vertices p_i of mesh job_mesh[j] of the packed mesh set (verts
+ * (n_verts,3) float32, vptr (M+1) int32: tgp_render_depth's), the poses E = pose_est[j] and G = pose_gt[j], (3,4) float32 [s R | t],
+ * model to camera in metres, the Q transforms S of symmetry group job_sym[j] of the packed table sym (n_syms,3,4) float32 [R | t] in
+ * model units with sptr (G+1) int32, and camk[j] (4) float32 fx, fy, cx, cy (one row per JOB).  Everything is read on the device.
+ *    add  = mean_i |E p_i - G p_i|
+ *    adi  = mean_i min_k |E p_i - G p_k|
+ *    mssd = min_S max_i |E p_i - G S p_i|
+ *    mspd = min_S max_i |pi(E p_i) - pi(G S p_i)| in pixels, pi(x) = (fx x/z + cx, fy y/z + cy)
+ * The float32 inputs are widened to float64 and every operation is float64, each product and sum rounded on its own; T p =
+ * ((T0 x + T1 y) + T2 z) + T3 per row, G S p = G (S p); a distance is sqrt((dx dx + dy dy) + dz dz).  A job is spread over
+ * TGP_POSEERR_SPLIT workgroups of 256 threads: workgroup b takes the points [b c, (b+1) c) with c = ceil(P / TGP_POSEERR_SPLIT) for
+ * add and adi -- thread t adds its points b c + t, b c + t + 256, ... in that order, the threads are joined by a tree in LDS
+ * (x[t] += x[t + 128], + 64, ... + 1), and the finishing launch adds the workgroups' sums in index order and divides by P -- and
+ * wave w of workgroup b takes the symmetries 4 b + w, + 4 TGP_POSEERR_SPLIT, ...; max and min are exact in any order.  The
+ * ground-truth points of adi pass through LDS in tiles of TGP_POSEERR_TILE points: no P x P matrix exists anywhere.  No
+ * floating-point atomics: two calls give identical bytes, and a job's result depends on neither the other jobs nor J.
+ * -> err (J,4) float64 = add, adi, mssd, mspd; sym_best (J,2) int32: the group-local index of the S that attains mssd and mspd,
+ *    the lowest among equal computed values; status (J) int32, a bit set:
+ *      1  job_mesh[j] or job_sym[j] out of range, rows of vptr / sptr that leave the arrays or are empty, or a group of more than
+ *         max_syms transforms: nothing is read further, err is NaN and sym_best -1;
+ *      2  a projected point (E p_i or a G S p_i) does not have z > near: mspd = +inf, sym_best[j][1] = -1, the rest is valid;
+ *      4  (alone) a transformed point E p_i, G p_i or G S p_i, or an entry of camk[j], is not finite -- a pose, a transform, a vertex
+ *         or an intrinsic holds an infinity or a NaN: err is NaN and sym_best -1, so no threshold counts the job as correct.
+ * workspace: tgp_pose_errors_workspace_bytes(J) bytes, 16-byte aligned, nothing in it needs initialising.  Two kernels on the
+ * caller's stream, nothing read by the host; graph-capturable.
+ * TGP_EINVAL (before any launch): a NULL required pointer (with J > 0: the job arrays, the outputs and the workspace), M, n_verts,
+ * G, n_syms or max_syms < 1, J < 0, near <= 0 or not finite, workspace_bytes too small.  TGP_EUNSUPPORTED: J > TGP_POSEERR_MAX_JOBS,
+ * max_syms (the host's bound on a group's size) > TGP_POSEERR_MAX_SYMS.  J == 0 launches nothing and returns 0. */
+#define TGP_POSEERR_COLS 4
+#define TGP_POSEERR_MAX_JOBS 65535
+#define TGP_POSEERR_MAX_SYMS 1024
+#define TGP_POSEERR_SPLIT 32
+#define TGP_POSEERR_TILE 1024
+typedef struct tgp_poseerr_args {
+    const float *verts;
+    const int32_t *vptr;
+    int M, n_verts;
+    const float *sym;
+    const int32_t *sptr;
+    int G, n_syms, max_syms;
+    const int32_t *job_mesh, *job_sym;
+    const float *pose_est, *pose_gt;
+    const float *camk;
+    int J;
+    float near;
+    double *err;
+    int32_t *sym_best;
+    int32_t *status;
+    void *workspace;
+    int64_t workspace_bytes;
+} tgp_poseerr_args;
+int64_t tgp_pose_errors_workspace_bytes(int J);
+int tgp_pose_errors(const tgp_poseerr_args *args, tgp_stream_t stream);
+
+/* ---- BOP pose errors: two-pose VSD (csrc/vsd.hip on csrc/raster.h; additive, ABI stays 8) ------------------------------------------
+ * Visible surface discrepancy of J jobs (frame job_img[j], mesh job_mesh[j], pose_est[j], pose_gt[j]) in one call.  The two
+ * surfaces of a job, d_e and d_g in millimetres, are exactly what tgp_render_depth gives for a scene of that one instance at each
+ * pose (tgp_pose_verify's sentence: the same vertex arithmetic, snapping, drop rules, coverage, z and winner, d = rint(1000 z), 0
+ * above 65535); 0 -- nothing rendered, or over range -- means "not rendered".  No frame is written.  With d_o = depth[job_img[j], y,
+ * x] (0: no data) and delta in millimetres, per pixel:
+ *    vis(d)    = d > 0 and (d_o == 0 or d - d_o <= delta)
+ *    visib_gt  = vis(d_g)
+ *    visib_est = vis(d_e) or (visib_gt and d_e > 0)
+ *    inter, union = visib_gt and / or visib_est
+ *    within_k  = inter and |d_g - d_e| < job_tau[j][k]     for the job's n_tau integer thresholds (millimetres)
+ * This is BOP's vsd with visib_mode 'bop19' and cost_type 'step', on depth along the optical axis instead of distance from the
+ * camera centre (the deviation DESIGN.md "Pose verification" documents).
+ * -> counts (J, TGP_VSD_COLS) int32: rendered_gt, rendered_est, visib_gt, visib_est, inter, union (pixel counts), dropped_gt,
+ *    dropped_est (triangles dropped by the near rule and the guard band); within (J, n_tau) int32;
+ *    err (J, n_tau) float32 = (float)(union - within_k) / (float)union, one correctly rounded division; 1 when union == 0.
+ * A job whose job_img or job_mesh is out of range gives zeros and err 1.  All-integer up to the division, integer atomics only:
+ * equal to the restatement (tests/bop_ref.py) bit for bit.  workspace: tgp_vsd_workspace_bytes(J, max_verts, max_faces) bytes,
+ * 16-byte aligned, nothing in it needs initialising.  Four kernels on the caller's stream; graph-capturable.
+ * TGP_EINVAL (before any launch): a NULL required pointer (with J > 0: the job arrays, the outputs and the workspace), S, M, H, W,
+ * n_verts, n_faces, max_verts, max_faces or n_tau < 1, J < 0, delta < 0, near <= 0 or not finite, workspace_bytes too small.
+ * TGP_EUNSUPPORTED: J > TGP_VERIFY_MAX_JOBS, n_tau > TGP_VSD_MAX_TAUS, delta > 65535, H*W >= 2^24, H or W > 16384, max_faces >=
+ * tgp_render_max_faces().  A threshold is compared as the int it is; every useful one is in [0, 65535].  J == 0 returns 0. */
+#define TGP_VSD_COLS 8
+#define TGP_VSD_MAX_TAUS 16
+typedef struct tgp_vsd_args {
+    const uint16_t *depth;
+    const float *camk;
+    const float *verts;
+    const int32_t *faces;
+    const int32_t *vptr, *fptr;
+    int M, n_verts, n_faces, max_verts, max_faces;
+    const int32_t *job_img, *job_mesh;
+    const float *pose_est, *pose_gt;
+    const int32_t *job_tau;         /* (J, n_tau) */
+    int S, H, W, J;
+    int n_tau, delta;
+    float near;
+    int32_t *counts;
+    int32_t *within;
+    float *err;
+    void *workspace;
+    int64_t workspace_bytes;
+} tgp_vsd_args;
+int64_t tgp_vsd_workspace_bytes(int J, int max_verts, int max_faces);
+int tgp_pose_vsd(const tgp_vsd_args *args, tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

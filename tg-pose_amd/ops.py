@@ -1141,6 +1141,7 @@ class MeshSet(object):
         self.vptr = up(np.concatenate([[0], np.cumsum(self.n_verts)]).astype(np.int32))
         self.fptr = up(np.concatenate([[0], np.cumsum(self.n_faces)]).astype(np.int32))
         self._area_cdf = None
+        self._diameter = None            # (M) float64, each mesh's largest vertex-to-vertex distance: evaluation.bop.diameter fills it
 
     def __len__(self):
         return len(self.n_verts)
@@ -1382,6 +1383,149 @@ def pose_verify(meshset, depth, camk, job_img, job_mesh, job_pose, tau=5, near=0
                         job_mask_val=_p(job_mask_val), S=S, H=H, W=W, J=J, tau=tau, near=float(near), counts=_p(out["counts"]),
                         score=_p(out["score"]), workspace=_p(ws), workspace_bytes=nbytes)
     check(_lib.lib().tgp_pose_verify(ctypes.byref(a), _stream(job_pose)), "tgp_pose_verify")
+    return out
+
+
+# the columns of pose_errors' err and of pose_vsd's counts
+POSE_ERRORS = ("add", "adi", "mssd", "mspd")
+VSD_COUNTS = ("rendered_gt", "rendered_est", "visib_gt", "visib_est", "inter", "union", "dropped_gt", "dropped_est")
+POSEERR_MAX_JOBS, POSEERR_MAX_SYMS, VSD_MAX_TAUS = _lib.POSEERR_MAX_JOBS, _lib.POSEERR_MAX_SYMS, _lib.VSD_MAX_TAUS
+POSEERR_STATUS = {1: "mesh or symmetry index out of range", 2: "a projected point at or behind near (mspd is +inf)",
+                  4: "a transformed point or an intrinsic is not finite (err is NaN)"}
+
+
+class SymmetrySet(object):
+    """Symmetry groups packed once for ops.pose_errors (tgp_pose_errors' table): ``groups`` is a list of (Q,3,4) arrays [R | t] in
+    model units, 1 <= Q <= POSEERR_MAX_SYMS.  Group 0 is conventionally the identity alone (SymmetrySet.identity()).  Holds sym
+    (sum Q,3,4) float32 and the prefix sums sptr (G+1) int32 on ``device``, and on the host the sizes."""
+
+    def __init__(self, groups, device="cuda"):
+        import numpy as np
+        if not len(groups):
+            raise ValueError("SymmetrySet: at least one group")
+        gs = []
+        for i, g in enumerate(groups):
+            g = np.ascontiguousarray(g, dtype=np.float32)
+            if g.ndim != 3 or g.shape[1:] != (3, 4) or not len(g):
+                raise ValueError("SymmetrySet: group %d must be (Q,3,4) with Q >= 1" % i)
+            if len(g) > POSEERR_MAX_SYMS:
+                raise ValueError("SymmetrySet: group %d has %d transforms; the cap is %d" % (i, len(g), POSEERR_MAX_SYMS))
+            gs.append(g)
+        self.sizes = [len(g) for g in gs]
+        self.device = torch.device(device)
+        self.sym = torch.from_numpy(np.concatenate(gs)).to(self.device)
+        self.sptr = torch.from_numpy(np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int32)).to(self.device)
+
+    def __len__(self):
+        return len(self.sizes)
+
+    @staticmethod
+    def identity():
+        import numpy as np
+        return np.concatenate([np.eye(3), np.zeros((3, 1))], 1)[None].astype(np.float32)
+
+
+def _gpu_args(who, dev, given):
+    for t, name, dt in given:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise TypeError("%s: %s must be a contiguous %s GPU tensor" % (who, name, str(dt).replace("torch.", "")))
+        if t.device != dev:
+            raise ValueError("%s: %s is not on the mesh set's device" % (who, name))
+
+
+def pose_errors(meshset, job_mesh, pose_est, pose_gt, symset, job_sym, camk, near=0.01):
+    """The point-based BOP pose errors of J (estimate, ground truth) pairs in one call (tgp_pose_errors, csrc/poseerr.hip;
+    DESIGN.md section 3 "BOP pose errors").  Job j: the vertices of mesh job_mesh[j] of the set, pose_est[j] and pose_gt[j]
+    (3,4) float32 [s R | t] (model -> camera, metres), group job_sym[j] of ``symset`` (ops.SymmetrySet) and camk[j] (4) float32
+    = fx, fy, cx, cy -- one row per job.  All tensors on the mesh set's GPU; job_mesh, job_sym (J) int32.
+    -> dict: err (J,4) float64 in the order of POSE_ERRORS -- add = mean |E p - G p|, adi = mean of the distance to the nearest
+    ground-truth point, mssd = min over the group's S of max |E p - G S p|, mspd the same of the projections, in pixels;
+    sym_best (J,2) int32: the group-local index that attains mssd and mspd; status (J) int32 bits: 1 an index out of range (NaN
+    and -1), 2 a projected point without z > near (mspd = +inf); or 4 alone: a pose, a transform, a vertex or an intrinsic is not
+    finite (NaN and -1: no threshold counts such a job as correct).  float64 throughout, fixed summation order, no atomics: two calls
+    give identical bytes.  Nothing synchronises."""
+    if not isinstance(meshset, MeshSet):
+        raise TypeError("pose_errors: meshset must be an ops.MeshSet")
+    if not isinstance(symset, SymmetrySet):
+        raise TypeError("pose_errors: symset must be an ops.SymmetrySet")
+    dev = meshset.verts.device
+    _gpu_args("pose_errors", dev, [(job_mesh, "job_mesh", torch.int32), (pose_est, "pose_est", torch.float32), (pose_gt, "pose_gt", torch.float32),
+                                   (job_sym, "job_sym", torch.int32), (camk, "camk", torch.float32), (symset.sym, "symset", torch.float32)])
+    J = job_mesh.numel()
+    if job_mesh.dim() != 1 or job_sym.shape != (J,) or pose_est.shape != (J, 3, 4) or pose_gt.shape != (J, 3, 4) or camk.shape != (J, 4):
+        raise ValueError("pose_errors: job_mesh (J), job_sym (J), pose_est (J,3,4), pose_gt (J,3,4), camk (J,4) are expected")
+    if not 0.0 < float(near) < float("inf"):
+        raise ValueError("pose_errors: near must be positive and finite")
+    if J > POSEERR_MAX_JOBS:
+        raise ValueError("pose_errors: at most %d jobs" % POSEERR_MAX_JOBS)
+    out = {"err": torch.empty(J, len(POSE_ERRORS), device=dev, dtype=torch.float64), "sym_best": torch.empty(J, 2, device=dev, dtype=torch.int32),
+           "status": torch.empty(J, device=dev, dtype=torch.int32)}
+    if J == 0:
+        return out
+    nbytes = _lib.lib().tgp_pose_errors_workspace_bytes(J)
+    if nbytes < 0:
+        check(nbytes, "tgp_pose_errors_workspace_bytes")
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    a = _lib.PoseerrArgs(verts=_p(meshset.verts), vptr=_p(meshset.vptr), M=len(meshset), n_verts=meshset.verts.shape[0], sym=_p(symset.sym),
+                         sptr=_p(symset.sptr), G=len(symset), n_syms=symset.sym.shape[0], max_syms=max(symset.sizes), job_mesh=_p(job_mesh),
+                         job_sym=_p(job_sym), pose_est=_p(pose_est), pose_gt=_p(pose_gt), camk=_p(camk), J=J, near=float(near),
+                         err=_p(out["err"]), sym_best=_p(out["sym_best"]), status=_p(out["status"]), workspace=_p(ws), workspace_bytes=nbytes)
+    check(_lib.lib().tgp_pose_errors(ctypes.byref(a), _stream(pose_est)), "tgp_pose_errors")
+    return out
+
+
+def pose_vsd(meshset, depth, camk, job_img, job_mesh, pose_est, pose_gt, job_tau, delta=15, near=0.01):
+    """Two-pose visible surface discrepancy of J jobs in one call (tgp_pose_vsd, csrc/vsd.hip; DESIGN.md section 3 "BOP pose
+    errors").  Job j renders mesh job_mesh[j] at pose_est[j] and at pose_gt[j] -- each exactly render_depth's surface for that one
+    instance, d_e and d_g in millimetres, 0 = not rendered -- and compares both with frame job_img[j]; no frame is written.  All
+    tensors on the mesh set's GPU: depth (S,H,W) 16-bit millimetres (0: no data), camk (S,4) float32, job_img, job_mesh (J) int32,
+    the poses (J,3,4) float32 [s R | t], job_tau (J,n_tau) int32 millimetres with 1 <= n_tau <= VSD_MAX_TAUS; delta: an int in
+    [0, 65535], millimetres.
+    -> dict: counts (J,8) int32 in the order of VSD_COUNTS -- vis(d) = d > 0 and (d_o == 0 or d - d_o <= delta); visib_gt =
+    vis(d_g); visib_est = vis(d_e) or (visib_gt and d_e > 0); inter / union their AND / OR; dropped_*: triangles the near rule and
+    the guard band dropped -- within (J,n_tau) int32: the inter pixels with |d_g - d_e| < tau; err (J,n_tau) float32 =
+    (union - within) / union, 1 when union is 0.  BOP's vsd with visib_mode 'bop19' and cost_type 'step', on depth along the
+    optical axis.  A job whose frame or mesh index is out of range gives zeros and err 1.  Nothing synchronises."""
+    if not isinstance(meshset, MeshSet):
+        raise TypeError("pose_vsd: meshset must be an ops.MeshSet")
+    dev = meshset.verts.device
+    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in (torch.int16, torch.uint16) and depth.is_contiguous()):
+        raise TypeError("pose_vsd: depth must be a contiguous 16-bit GPU tensor")
+    if depth.device != dev:
+        raise ValueError("pose_vsd: depth is not on the mesh set's device")
+    _gpu_args("pose_vsd", dev, [(camk, "camk", torch.float32), (job_img, "job_img", torch.int32), (job_mesh, "job_mesh", torch.int32),
+                                (pose_est, "pose_est", torch.float32), (pose_gt, "pose_gt", torch.float32), (job_tau, "job_tau", torch.int32)])
+    if depth.dim() != 3 or depth.numel() == 0:
+        raise ValueError("pose_vsd: depth must be (S,H,W)")
+    S, H, W = depth.shape
+    J = job_img.numel()
+    if job_tau.dim() != 2 or not 1 <= job_tau.shape[1] <= VSD_MAX_TAUS:
+        raise ValueError("pose_vsd: job_tau must be (J, n_tau) with n_tau in [1, %d]" % VSD_MAX_TAUS)
+    n_tau = job_tau.shape[1]
+    if camk.shape != (S, 4) or job_img.dim() != 1 or job_mesh.shape != (J,) or pose_est.shape != (J, 3, 4) or pose_gt.shape != (J, 3, 4) or \
+            job_tau.shape[0] != J:
+        raise ValueError("pose_vsd: camk (S,4), job_img (J), job_mesh (J), pose_est (J,3,4), pose_gt (J,3,4), job_tau (J,n_tau) are expected")
+    if not (isinstance(delta, int) and 0 <= delta <= 65535):
+        raise ValueError("pose_vsd: delta must be an int in [0, 65535] (millimetres)")
+    if not 0.0 < float(near) < float("inf"):
+        raise ValueError("pose_vsd: near must be positive and finite")
+    if J > VERIFY_MAX_JOBS or H * W >= 2 ** 24:
+        raise ValueError("pose_vsd: at most %d jobs and frames of fewer than 2^24 pixels" % VERIFY_MAX_JOBS)
+    out = {"counts": torch.empty(J, len(VSD_COUNTS), device=dev, dtype=torch.int32), "within": torch.empty(J, n_tau, device=dev, dtype=torch.int32),
+           "err": torch.empty(J, n_tau, device=dev, dtype=torch.float32)}
+    if J == 0:
+        return out
+    max_v, max_f = max(meshset.n_verts), max(meshset.n_faces)
+    nbytes = _lib.lib().tgp_vsd_workspace_bytes(J, max_v, max_f)
+    if nbytes < 0:
+        check(nbytes, "tgp_vsd_workspace_bytes")
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    a = _lib.VsdArgs(depth=_p(depth), camk=_p(camk), verts=_p(meshset.verts), faces=_p(meshset.faces), vptr=_p(meshset.vptr),
+                     fptr=_p(meshset.fptr), M=len(meshset), n_verts=meshset.verts.shape[0], n_faces=meshset.faces.shape[0], max_verts=max_v,
+                     max_faces=max_f, job_img=_p(job_img), job_mesh=_p(job_mesh), pose_est=_p(pose_est), pose_gt=_p(pose_gt),
+                     job_tau=_p(job_tau), S=S, H=H, W=W, J=J, n_tau=n_tau, delta=delta, near=float(near), counts=_p(out["counts"]),
+                     within=_p(out["within"]), err=_p(out["err"]), workspace=_p(ws), workspace_bytes=nbytes)
+    check(_lib.lib().tgp_pose_vsd(ctypes.byref(a), _stream(pose_est)), "tgp_pose_vsd")
     return out
 
 
