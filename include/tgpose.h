@@ -1598,6 +1598,70 @@ typedef struct tgp_vsd_args {
 int64_t tgp_vsd_workspace_bytes(int J, int max_verts, int max_faces);
 int tgp_pose_vsd(const tgp_vsd_args *args, tgp_stream_t stream);
 
+/* ---- Distance-field pose search (csrc/search.hip; additive, ABI stays 8) -----------------------------------------------------------
+ * An exhaustive search of R rotations x D lattice translations per job against a quantised distance field of the job's model, held
+ * in LDS.  DESIGN.md section 3 "Model-based acquisition" is the contract; tests/search_ref.py restates it in NumPy, bit for bit.
+ *
+ * tgp_field_build: models (M, m_cap, 6) float32 rows [point, normal] with model_count (M) int32 or NULL (= m_cap): tgp_icp_refine's
+ * model set.  meta (M, 4) float32 = the cube's centre ctr (3) and the voxel edge: made by the host.  thresholds (M, cap) float32,
+ * increasing, made by the host: T_l = ((l + 1) voxel / 4)^2.  -> field (M, G, G, G) uint8, voxel (ix, iy, iz) at (ix G + iy) G + iz:
+ * with c_a = ctr_a + (i_a - G/2 + 0.5) voxel (float32, product and sum rounded on their own) and dv the least of tgp_nn1's float32
+ * value (|y|^2 + |c|^2) - 2 fmaf(c_z, y_z, fmaf(c_y, y_y, c_x y_x)) over the model's points (a NaN value is skipped; no point: +inf),
+ * the byte is the number of l with dv >= T_l.  One thread per voxel, the model in tiles through LDS; no square root, no division.
+ *
+ * tgp_pose_search: job j = (model job_model[j], cloud clouds[j] (n_cap, 3) float32 of which the first counts[j] rows are live (NULL:
+ * n_cap) and a row with a non-finite coordinate contributes nothing, anchor anchors[j] (3), scale scales[j] metres per model unit).
+ * rotations (R, 3, 3) float32 row-major, shared.  With inv = float32(1 / ((double)scale (double)voxel)) and, per rotation and point,
+ *    e = p - anchor;  u_a = (R[0][a] e_0 + R[1][a] e_1) + R[2][a] e_2;  w_a = u_a inv + G/2;  b_a = floor(min(max(w_a, -512), 511))
+ * -- float32, every product and sum rounded on its own, a NaN w_a giving -512 -- the cost of (rotation r, shift d) is the int32 sum
+ * over the points of field[b + d], or cap where b + d leaves the grid; d = stride (a, b, c), a, b, c in [-K, K], shift index
+ * ((a+K)(2K+1) + (b+K))(2K+1) + (c+K).  Per rotation the least cost and its shift (ties: the smaller index) go to the table
+ * (J, R, 2) int32 = the workspace; per job the top rotations of least (cost, r) go to cost / rot / shift (J, top) int32 and poses
+ * (J, top, 3, 4) float32 [R | t], t_i = anchor_i - s ((R_i0 m_0 + R_i1 m_1) + R_i2 m_2), m_a = ctr_a + (double)d_a voxel, float64
+ * rounded once.  Rows beyond R, and every row of a job whose job_model is outside [0, M) or whose count is outside [0, n_cap], are
+ * cost = INT32_MAX, rot = shift = -1 and a NaN pose (the table's rows of such a job are INT32_MAX, -1).  Integer arithmetic after
+ * the floor, no atomics: two calls give identical bytes.  Two kernels on the caller's stream, nothing read by the host;
+ * graph-capturable.  workspace: tgp_pose_search_workspace_bytes(J, R) bytes, 16-byte aligned, nothing in it needs initialising.
+ * TGP_EINVAL: a NULL required pointer, M, J, R, n_cap or top < 1, K < 0, stride < 1, cap outside [1, 255], workspace_bytes too small.
+ * TGP_EUNSUPPORTED: G not 16, 32 or 48, n_cap > TGP_SEARCH_MAX_POINTS, R > TGP_SEARCH_MAX_ROTATIONS, top > TGP_SEARCH_MAX_TOP,
+ * K > TGP_SEARCH_MAX_K, K stride > TGP_SEARCH_MAX_REACH, J > 65535, m_cap > TGP_ICP_MAX_POINTS. */
+#define TGP_SEARCH_MAX_POINTS 1024
+#define TGP_SEARCH_MAX_ROTATIONS 4096
+#define TGP_SEARCH_MAX_TOP 64
+#define TGP_SEARCH_MAX_K 16
+#define TGP_SEARCH_MAX_REACH 200
+#define TGP_SEARCH_ROT_BLOCK 8
+typedef struct tgp_field_args {
+    const float *models;
+    const int32_t *model_count;     /* may be NULL */
+    int M, m_cap;
+    const float *meta;
+    const float *thresholds;
+    int G, cap;
+    uint8_t *field;
+} tgp_field_args;
+int tgp_field_build(const tgp_field_args *args, tgp_stream_t stream);
+typedef struct tgp_pose_search_args {
+    const uint8_t *field;
+    const float *meta;
+    int M, G, cap;
+    const int32_t *job_model;
+    const float *clouds;
+    const int32_t *counts;          /* may be NULL */
+    const float *anchors;
+    const float *scales;
+    int J, n_cap;
+    const float *rotations;
+    int R;
+    int K, stride, top;
+    int32_t *cost, *rot, *shift;
+    float *poses;
+    void *workspace;
+    int64_t workspace_bytes;
+} tgp_pose_search_args;
+int64_t tgp_pose_search_workspace_bytes(int J, int R);
+int tgp_pose_search(const tgp_pose_search_args *args, tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

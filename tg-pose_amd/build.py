@@ -13,7 +13,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["knn.hip", "gemm.hip", "gemm_pp.hip", "gconv.hip", "chamfer.hip", "dcd.hip", "emd.hip", "fps.hip", "render.hip", "meshsample.hip", "ballcrop.hip", "icp.hip", "plane.hip", "segment.hip", "verify.hip", "poseerr.hip", "vsd.hip", "bn.hip", "backward.hip", "gconv_bwd.hip", "evalmetrics.hip", "tdaloss.hip", "inputside.hip", "rowsort.hip", "heads_fused.hip", "dec_fused.hip", "hs_chain.hip", "segsum.hip", "graph_bwd.hip", "poserot.hip", "gemm_tn_split.hip", "ranger.hip", "augment.hip", "persistence.hip", "xyz_bwd.hip", "draws.hip", "version.hip"]
+SOURCES = ["knn.hip", "gemm.hip", "gemm_pp.hip", "gconv.hip", "chamfer.hip", "dcd.hip", "emd.hip", "fps.hip", "render.hip", "meshsample.hip", "ballcrop.hip", "icp.hip", "plane.hip", "segment.hip", "verify.hip", "poseerr.hip", "vsd.hip", "search.hip", "bn.hip", "backward.hip", "gconv_bwd.hip", "evalmetrics.hip", "tdaloss.hip", "inputside.hip", "rowsort.hip", "heads_fused.hip", "dec_fused.hip", "hs_chain.hip", "segsum.hip", "graph_bwd.hip", "poserot.hip", "gemm_tn_split.hip", "ranger.hip", "augment.hip", "persistence.hip", "xyz_bwd.hip", "draws.hip", "version.hip"]
 DEV_SOURCES = ["gemm_variants.hip"]     # development build only (--dev): micro-benchmark kernels + the tgp_debug_* switches
 LIB = os.path.join(HERE, "libtgpose_hip.so")
 DEV_LIB = os.path.join(HERE, "libtgpose_hip_dev.so")
@@ -37,6 +37,8 @@ def build(force=False, verbose=True, dev=False):
         return _build(os.path.join(HERE, "libtgpose_hip_bnscalar.so"), SOURCES, ["-DTGP_BN_SCALAR"], ".bs.o", verbose)
     if dev == "predbig":       # A/B measurement build: predicated (repair) launches on the large tile shapes, as before round 4
         return _build(os.path.join(HERE, "libtgpose_hip_predbig.so"), SOURCES, ["-DTGP_PRED_BIG"], ".pb.o", verbose)
+    if dev == "searchpad":     # A/B measurement build: the pose search's field rows padded by 4 bytes in LDS (scripts/search_pad_ab.py)
+        return _build(os.path.join(HERE, "libtgpose_hip_searchpad.so"), SOURCES, ["-DTGP_SEARCH_PAD=4"], ".sp.o", verbose)
     if dev == "noguard":       # A/B measurement build: the product library without the fp16 range guard of the split GEMM
         return _build(os.path.join(HERE, "libtgpose_hip_noguard.so"), SOURCES, ["-DTGP_NO_RANGE_GUARD"], ".ng.o", verbose)
     if dev:
@@ -74,4 +76,4 @@ def _build(LIB, sources, extra, suffix, verbose):
 
 
 if __name__ == "__main__":
-    build(force="--force" in sys.argv, dev="predbig" if "--predbig" in sys.argv else "noguard" if "--noguard" in sys.argv else "bnscalar" if "--bnscalar" in sys.argv else "--dev" in sys.argv)
+    build(force="--force" in sys.argv, dev="searchpad" if "--searchpad" in sys.argv else "predbig" if "--predbig" in sys.argv else "noguard" if "--noguard" in sys.argv else "bnscalar" if "--bnscalar" in sys.argv else "--dev" in sys.argv)

@@ -18,10 +18,11 @@ import os
 import numpy as np
 import torch
 
+from .. import ops
 from ..evaluation import load_data_eval as lde
 from ..evaluation.metrics import compute_degree_cm_mAP
 from ..losses.utils_v2.model_utils import calc_cd, calc_emd
-from ..pose import IcpRefine, Segmenter, SupportPlane, Verify, infer_device
+from ..pose import IcpRefine, ModelSearch, Segmenter, SupportPlane, Verify, infer_device
 
 SYNSET_NAMES = ['BG', 'bottle', 'bowl', 'camera', 'can', 'laptop', 'mug']                                   # :115
 MEAN_SHAPE_MM = {1: (87, 220, 89), 2: (165, 80, 165), 3: (88, 128, 156), 4: (68, 146, 72), 5: (346, 200, 335), 6: (146, 83, 114)}
@@ -197,6 +198,79 @@ class myEvaluater:
         if not isinstance(verify, Verify):
             raise TypeError("acquire_verified: verify must be a pose.Verify")
         return self._acquire(frame, class_ids, camK, support, segmenter, n_pts, sampler, verify)
+
+    def acquire_models(self, frame, search, job_model, job_scale, camK=lde.REAL_INTRINSICS, support=None, segmenter=None, n_pts=128,
+                       sampler=None):
+        """The ``init`` that ``track`` takes, from one depth frame and mesh models alone: no network forward, no detector result, no
+        ground truth (DESIGN.md section 3 "Model-based acquisition").  The constructor still wants a network (it reads the device
+        from it); this method never touches it.
+
+        frame, camK, support, segmenter, sampler: as ``acquire``.  search (a pose.ModelSearch: the distance fields, the rotation
+        table, and optionally ICP and the render-and-compare check).  job_model: one model index for every segment, or a sequence
+        with one per kept segment in label order; job_scale: metres per model unit, likewise.  n_pts (at most
+        ops.SEARCH_MAX_POINTS): the points drawn per segment for the search and ICP.
+
+        Everything is enqueued without a read-back, over the segmenter's max_segments slots: the cut, the segmentation,
+        load_data_eval.clouds_from_segments, the search, ONE ICP call and ONE verify call over all slots x top candidates (against
+        the cut depth when ``support`` is given, with the label image as the mask).  Then everything is read back once and cut down
+        to the n kept segments.
+        -> ``acquire``'s dict -- 'RTs' (n,4,4) = [s R | t] with s = job_scale, 'scales' (n,3) = the model's extent in model units
+        (its points' bounding box; what ``track`` sizes its crop balls with), 'class_ids' (n,) all 1 (``track`` reads them for the
+        network alone; init_from='previous' never does) -- plus 'search_cost' and 'search_rank' (n,) int32 (which candidate won),
+        with ICP 'icp_status', 'icp_inliers' (n,) int32 and 'icp_rmse' (n,), with verify 'verify_score' (n,) and 'verify_counts'
+        (n,8).  'ok' is False for a segment whose cloud the ROI path found invalid or that got no candidate."""
+        if not isinstance(search, ModelSearch):
+            raise TypeError("acquire_models: search must be a pose.ModelSearch")
+        if support is not None and not isinstance(support, SupportPlane):
+            raise TypeError("acquire_models: support must be a pose.SupportPlane")
+        segmenter = Segmenter() if segmenter is None else segmenter
+        if not isinstance(segmenter, Segmenter):
+            raise TypeError("acquire_models: segmenter must be a pose.Segmenter")
+        sampler = sampler or (self.sampler if self.sampler in ("device", "fps") else "device")
+        if sampler not in ("device", "fps"):
+            raise ValueError("acquire_models: sampler must be 'device' or 'fps' (nothing is read back before the search)")
+        if not 1 <= int(n_pts) <= ops.SEARCH_MAX_POINTS:
+            raise ValueError("acquire_models: n_pts must be in [1, %d]" % ops.SEARCH_MAX_POINTS)
+        dev, M = self.device, segmenter.max_segments
+        one_m, one_s = np.ndim(job_model) == 0, np.ndim(job_scale) == 0
+        jm, js = np.asarray(job_model).astype(np.int64).reshape(-1), np.asarray(job_scale).astype(np.float32).reshape(-1)
+        if len(jm) == 0 or len(js) == 0 or not all(0 <= int(m) < len(search.models) for m in jm) or not (js > 0).all():
+            raise ValueError("acquire_models: job_model must index the search's %d models and job_scale be positive" % len(search.models))
+        if max(len(jm), len(js)) > M:
+            raise ValueError("acquire_models: more models or scales than the segmenter's %d slots" % M)
+        slot_m, slot_s = np.full(M, jm[0], dtype=np.int32), np.full(M, js[0], dtype=np.float32)
+        if not one_m:
+            slot_m[:len(jm)] = jm
+        if not one_s:
+            slot_s[:len(js)] = js
+        with torch.no_grad():
+            depth, _, camk = lde._depth_frames([frame], camK, dev)
+            if support is not None:
+                depth = support(depth, camk, [0], self.seed)[0]
+            seg = segmenter(depth, camk)
+            pts, ok = lde.clouds_from_segments(depth, seg, camk, n_pts=n_pts, sampler=sampler, seed=self.seed, fps_pool=self.fps_pool)
+            model_t = torch.from_numpy(slot_m).to(dev)
+            found = search(pts.contiguous(), model_t, torch.from_numpy(slot_s).to(dev), depth=depth, camk=camk, mask=seg.labels,
+                           job_mask_val=torch.arange(1, M + 1, device=dev).to(torch.uint8))
+            ok = ok & (found["search_cost"] != 2 ** 31 - 1)
+            meta = search.models.points_normals[:, :, :3]
+            if search.models.counts is None:
+                extent = meta.amax(1) - meta.amin(1)
+            else:
+                live = torch.arange(meta.shape[1], device=dev)[None, :, None] < search.models.counts[:, None, None]
+                extent = torch.where(live, meta, -torch.inf).amax(1) - torch.where(live, meta, torch.inf).amin(1)
+            scales = extent[model_t.long()]
+        info = seg.info[0].cpu().numpy()                                                     # the read-back
+        n = int(info[1])
+        for what, given, one in (("job_model", jm, one_m), ("job_scale", js, one_s)):
+            if not one and len(given) != n:
+                raise ValueError("acquire_models: %d entries of %s for %d segments" % (len(given), what, n))
+        stats = seg.stats[0, :n].cpu().numpy()
+        out = {k: found[k][:n].cpu().numpy() for k in ("search_cost", "search_rank", "icp_status", "icp_inliers", "icp_rmse", "verify_score",
+                                                       "verify_counts") if k in found}
+        return dict(out, class_ids=np.ones(n, dtype=np.int64), RTs=found["RTs"][:n].cpu().numpy(), scales=scales[:n].cpu().numpy(),
+                    inst_ids=np.arange(1, n + 1, dtype=np.int32), inst_mask=seg.labels[0].cpu().numpy(), boxes=stats[:, 1:5].copy(),
+                    pixels=stats[:, 0].copy(), centers=seg.centers[0, :n].cpu().numpy(), ok=ok[:n].cpu().numpy(), info=info)
 
     def _acquire(self, frame, class_ids, camK, support, segmenter, n_pts, sampler, verify):
         if support is not None and not isinstance(support, SupportPlane):

@@ -2464,6 +2464,123 @@ def icp_refine(models, job_model, src, R, t, s, max_dist, *, src_count=None, mod
     return out + (corr,) if return_corr else out
 
 
+# ------------------------------------------------------------------------------------------------------------ distance-field pose search
+SEARCH_MAX_POINTS, SEARCH_MAX_ROTATIONS, SEARCH_MAX_TOP, SEARCH_MAX_K = (_lib.SEARCH_MAX_POINTS, _lib.SEARCH_MAX_ROTATIONS,
+                                                                          _lib.SEARCH_MAX_TOP, _lib.SEARCH_MAX_K)
+SEARCH_MAX_REACH = _lib.SEARCH_MAX_REACH
+SEARCH_GRIDS = (16, 32, 48)
+SEARCH_REFUSED = 2 ** 31 - 1        # the cost of a row beyond R, and of every row of a refused job
+
+
+def field_meta(points, G, cap):
+    """The host's part of one model's distance field, from its (m,3) float32 points: (meta (4,) float32 = the cube's centre and the
+    voxel edge, thresholds (cap,) float32).  centre = the midpoint of the bounding box, half edge = 0.575 x the largest extent,
+    voxel = 2 half / G, T_l = (l voxel / 4)^2 for l = 1..cap: float64 on the float32 inputs, each rounded to float32 once."""
+    import numpy as np
+    pts = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    lo, hi = pts.min(0).astype(np.float64), pts.max(0).astype(np.float64)
+    ctr = ((lo + hi) * 0.5).astype(np.float32)
+    half = np.float32(0.575 * (hi - lo).max())
+    voxel = np.float32(2.0 * float(half) / G)
+    edge = np.arange(1, cap + 1, dtype=np.float64) * float(voxel) / 4.0
+    return np.concatenate([ctr, [voxel]]).astype(np.float32), (edge * edge).astype(np.float32)
+
+
+class DistanceFields(object):
+    """The quantised distance fields pose_search looks poses up in (tgp_field_build, csrc/search.hip; DESIGN.md section 3
+    "Model-based acquisition"): one cube of G^3 voxels per model of an ops.IcpModels, byte (ix G + iy) G + iz = how many of the
+    thresholds (l voxel / 4)^2, l = 1..cap, the squared distance from the voxel's centre to the nearest model point reaches
+    (tgp_nn1's float32 arithmetic).  ``field`` (M,G,G,G) uint8, ``meta`` (M,4) float32 = centre, voxel edge (model units), both on
+    the models' device; ``meta_host`` is the same on the host.  The model's points are read back once, here, for the cube."""
+
+    def __init__(self, models, G=32, cap=32):
+        import numpy as np
+        if not isinstance(models, IcpModels):
+            raise TypeError("DistanceFields: models must be an ops.IcpModels")
+        if G not in SEARCH_GRIDS:
+            raise ValueError("DistanceFields: G must be one of %s" % (SEARCH_GRIDS,))
+        if not (isinstance(cap, int) and 1 <= cap <= 255):
+            raise ValueError("DistanceFields: cap must be an int in [1, 255]")
+        pn = models.points_normals
+        M, dev = len(models), pn.device
+        counts = [models.m_cap] * M if models.counts is None else models.counts.cpu().tolist()
+        if not all(1 <= c <= models.m_cap for c in counts):
+            raise ValueError("DistanceFields: every model needs between 1 and m_cap points")
+        pts = pn[:, :, :3].cpu().numpy()
+        if not all(np.isfinite(pts[m, :c]).all() for m, c in enumerate(counts)):
+            raise ValueError("DistanceFields: a model point is not finite")
+        made = [field_meta(pts[m, :c], G, cap) for m, c in enumerate(counts)]
+        self.meta_host = np.stack([m for m, _ in made])
+        self.meta = torch.from_numpy(self.meta_host).to(dev)
+        self.thresholds = torch.from_numpy(np.stack([t for _, t in made])).to(dev)
+        self.G, self.cap, self.models = G, cap, models
+        self.field = torch.empty(M, G, G, G, device=dev, dtype=torch.uint8)
+        a = _lib.FieldArgs(models=_p(pn), model_count=_p(models.counts), M=M, m_cap=models.m_cap, meta=_p(self.meta),
+                           thresholds=_p(self.thresholds), G=G, cap=cap, field=_p(self.field))
+        check(_lib.lib().tgp_field_build(ctypes.byref(a), _stream(pn)), "tgp_field_build")
+
+    def __len__(self):
+        return self.field.shape[0]
+
+
+def search_shifts(K, stride):
+    """the (D,3) int64 lattice shifts of pose_search in voxels, in shift-index order, on the host"""
+    r = torch.arange(-K, K + 1, dtype=torch.int64) * stride
+    return torch.stack(torch.meshgrid(r, r, r, indexing="ij"), -1).reshape(-1, 3)
+
+
+def pose_search(fields, job_model, clouds, counts, anchors, scales, rotations, K=5, stride=2, top=16, return_table=False):
+    """tgp_pose_search (csrc/search.hip; DESIGN.md section 3 "Model-based acquisition"): for each of J clouds, every one of R rotations
+    x (2K+1)^3 lattice translations is scored against the distance field of the job's model, and the ``top`` rotations of least cost
+    come back, each with its best translation.  fields: ops.DistanceFields; job_model (J) int32; clouds (J, n_cap <= 1024, 3)
+    float32 camera-frame metres (non-finite rows and rows at or beyond counts[j] contribute nothing); counts (J) int32 or None;
+    anchors (J,3) float32: the point of each cloud tried at the cube's centre; scales (J) float32 metres per model unit; rotations
+    (R,3,3) float32.  The shifts are stride x {-K..K}^3 voxels (search_shifts).
+    -> dict: cost, rot, shift (J, top) int32 and poses (J, top, 3, 4) float32 [R | t] (model units to metres takes the scale:
+    x = s R y + t); rows beyond R, and a job whose model index or count is out of range, give cost = SEARCH_REFUSED, rot = shift = -1
+    and a NaN pose.  return_table adds table (J, R, 2) int32 = each rotation's least cost and its shift.  Nothing synchronises."""
+    if not isinstance(fields, DistanceFields):
+        raise TypeError("pose_search: fields must be an ops.DistanceFields")
+    _f32(clouds, "clouds", 3), _i32(job_model, "job_model"), _f32(anchors, "anchors", 2), _f32(scales, "scales", 1), _f32(rotations, "rotations", 3)
+    J, n_cap = clouds.shape[0], clouds.shape[1]
+    if J < 1 or not 1 <= n_cap <= SEARCH_MAX_POINTS or clouds.shape[2] != 3:
+        raise ValueError("pose_search: clouds must be (J, n_cap, 3) with J >= 1 and 1 <= n_cap <= %d" % SEARCH_MAX_POINTS)
+    if J > 65535:
+        raise ValueError("pose_search: at most 65535 jobs a call")
+    R = rotations.shape[0]
+    if rotations.shape[1:] != (3, 3) or not 1 <= R <= SEARCH_MAX_ROTATIONS:
+        raise ValueError("pose_search: rotations must be (R,3,3) with 1 <= R <= %d" % SEARCH_MAX_ROTATIONS)
+    if job_model.shape != (J,) or anchors.shape != (J, 3) or scales.shape != (J,):
+        raise ValueError("pose_search: job_model (J,), anchors (J,3) and scales (J,) are needed for the %d jobs" % J)
+    if counts is not None and _i32(counts, "counts").shape != (J,):
+        raise ValueError("pose_search: counts must be (J,)")
+    if not (isinstance(K, int) and 0 <= K <= SEARCH_MAX_K and isinstance(stride, int) and stride >= 1 and K * stride <= SEARCH_MAX_REACH):
+        raise ValueError("pose_search: K must be an int in [0, %d], stride an int >= 1 and K * stride <= %d" % (SEARCH_MAX_K, SEARCH_MAX_REACH))
+    if not (isinstance(top, int) and 1 <= top <= SEARCH_MAX_TOP):
+        raise ValueError("pose_search: top must be an int in [1, %d]" % SEARCH_MAX_TOP)
+    dev = clouds.device
+    tensors = [clouds, job_model, anchors, scales, rotations, fields.field] + ([] if counts is None else [counts])
+    if not all(x.is_contiguous() for x in tensors):
+        raise ValueError("pose_search: every tensor must be contiguous")
+    if any(x.device != dev for x in tensors):
+        raise ValueError("pose_search: every tensor must be on one device")
+    out = {"cost": torch.empty(J, top, device=dev, dtype=torch.int32), "rot": torch.empty(J, top, device=dev, dtype=torch.int32),
+           "shift": torch.empty(J, top, device=dev, dtype=torch.int32), "poses": torch.empty(J, top, 3, 4, device=dev, dtype=torch.float32)}
+    nbytes = _lib.lib().tgp_pose_search_workspace_bytes(J, R)
+    if nbytes < 0:
+        check(nbytes, "tgp_pose_search_workspace_bytes")
+    table = torch.empty(J, R, 2, device=dev, dtype=torch.int32)
+    assert table.numel() * 4 == nbytes
+    a = _lib.PoseSearchArgs(field=_p(fields.field), meta=_p(fields.meta), M=len(fields), G=fields.G, cap=fields.cap, job_model=_p(job_model),
+                            clouds=_p(clouds), counts=_p(counts), anchors=_p(anchors), scales=_p(scales), J=J, n_cap=n_cap,
+                            rotations=_p(rotations), R=R, K=K, stride=stride, top=top, cost=_p(out["cost"]), rot=_p(out["rot"]),
+                            shift=_p(out["shift"]), poses=_p(out["poses"]), workspace=_p(table), workspace_bytes=nbytes)
+    check(_lib.lib().tgp_pose_search(ctypes.byref(a), _stream(clouds)), "tgp_pose_search")
+    if return_table:
+        out["table"] = table
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------ the supporting plane
 PLANE_STATUS = {1: "no hypothesis reached min_inliers", 2: "a refit was not finite (the plane of before it is returned)"}
 

@@ -186,6 +186,121 @@ class Verify(object):
         return out
 
 
+def cloud_anchors(clouds, counts=None):
+    """The mean of each cloud's finite rows (of the first counts[j] rows): float64 sums on the device, rounded once -> (J,3) float32;
+    a cloud without a finite row gives 0."""
+    fin = torch.isfinite(clouds).all(-1)
+    if counts is not None:
+        fin = fin & (torch.arange(clouds.shape[1], device=clouds.device)[None, :] < counts[:, None])
+    total = torch.where(fin[:, :, None], clouds.double(), torch.zeros((), dtype=torch.float64, device=clouds.device)).sum(1)
+    return (total / fin.sum(1).clamp(min=1)[:, None]).float().contiguous()
+
+
+def search_poses(fields, job_model, clouds, scales, rotations, counts=None, **kw):
+    """ops.pose_search with each cloud's mean (cloud_anchors) as its anchor: the point tried at the centre of the model's cube and,
+    through K and stride, around it.  fields: ops.DistanceFields; job_model (J) int32; clouds (J,n,3) float32 camera-frame metres
+    (NaN rows count for nothing); scales (J) float32 metres per model unit; rotations (R,3,3) float32; kw: K, stride, top,
+    return_table.  -> ops.pose_search's dict plus 'anchors' (J,3).  Nothing is read back."""
+    anchors = cloud_anchors(clouds, counts)
+    out = ops.pose_search(fields, job_model, clouds, counts, anchors, scales, rotations, **kw)
+    out["anchors"] = anchors
+    return out
+
+
+def _first_where(mask):
+    """(J, top) bool -> (J,) the first True column (top where none)"""
+    top = mask.shape[1]
+    cols = torch.arange(top, device=mask.device)[None, :].expand_as(mask)
+    return torch.where(mask, cols, torch.full_like(cols, top)).min(1).values
+
+
+class ModelSearch(object):
+    """Poses from mesh models alone (DESIGN.md section 3 "Model-based acquisition"): for each cloud the ``top`` rotations of least
+    distance-field cost with their translations (search_poses), all J * top candidates refined in ONE ops.icp_refine call, all
+    checked against the frame in ONE ops.pose_verify call, one candidate kept per job.
+
+    fields: ops.DistanceFields built from ``models`` (ops.IcpModels); rotations (R,3,3) float32 (a tensor on the models' device, or
+    an array: tools.lynne_lib.view_sampler.rotation_grid); K, stride, top: ops.pose_search's.  refine (a pose.IcpRefine; its models,
+    gate and keywords are used, its job_model is not: the candidates' models are the call's) or None; verify (a pose.Verify; its
+    meshes are in the models' units; its job_mesh holds one mesh index per job, or one for all) or None.
+    Kept per job: with verify the candidate of the highest score, ties to the lower search rank; without it the one with the most
+    ICP inliers, then the least rmse, then the lower rank; without refine rank 0.
+
+    __call__(clouds (J,n,3), job_model (J) int32, scales (J) float32, depth, camk, job_img, mask, job_mask_val, counts) -> dict of
+    device tensors: RTs (J,4,4) [s R | t], search_cost, search_rank (J) int32, candidates (J,top,4,4) (after ICP where it ran) and
+    cand_cost (J,top); with refine icp_status, icp_inliers (J) int32, icp_rmse (J); with verify verify_score (J) and verify_counts
+    (J,8).  A job without a candidate (ops.SEARCH_REFUSED) has search_rank 0 and a NaN pose.  Nothing is read back."""
+
+    def __init__(self, fields, models, rotations, K=5, stride=2, top=16, refine=None, verify=None):
+        if not isinstance(fields, ops.DistanceFields):
+            raise TypeError("ModelSearch: fields must be an ops.DistanceFields")
+        if not isinstance(models, ops.IcpModels) or fields.models is not models:
+            raise ValueError("ModelSearch: models must be the ops.IcpModels the fields were built from")
+        if refine is not None and not isinstance(refine, IcpRefine):
+            raise TypeError("ModelSearch: refine must be a pose.IcpRefine")
+        if verify is not None and not isinstance(verify, Verify):
+            raise TypeError("ModelSearch: verify must be a pose.Verify")
+        if verify is not None and verify.normalised:
+            raise ValueError("ModelSearch: verify's meshes must be in the models' units (normalised=False)")
+        dev = models.points_normals.device
+        rotations = torch.as_tensor(rotations, dtype=torch.float32).to(dev).contiguous()
+        if rotations.dim() != 3 or rotations.shape[1:] != (3, 3) or not 1 <= rotations.shape[0] <= ops.SEARCH_MAX_ROTATIONS:
+            raise ValueError("ModelSearch: rotations must be (R,3,3) with 1 <= R <= %d" % ops.SEARCH_MAX_ROTATIONS)
+        if not (isinstance(K, int) and 0 <= K <= ops.SEARCH_MAX_K and isinstance(stride, int) and stride >= 1 and K * stride <= ops.SEARCH_MAX_REACH):
+            raise ValueError("ModelSearch: K must be an int in [0, %d], stride an int >= 1 and K * stride <= %d" % (ops.SEARCH_MAX_K, ops.SEARCH_MAX_REACH))
+        if not (isinstance(top, int) and 1 <= top <= ops.SEARCH_MAX_TOP):
+            raise ValueError("ModelSearch: top must be an int in [1, %d]" % ops.SEARCH_MAX_TOP)
+        self.fields, self.models, self.rotations, self.K, self.stride, self.top = fields, models, rotations, K, stride, top
+        self.refine, self.verify = refine, verify
+
+    def __call__(self, clouds, job_model, scales, depth=None, camk=None, job_img=None, mask=None, job_mask_val=None, counts=None):
+        J, top, dev = clouds.shape[0], self.top, clouds.device
+        if self.verify is not None and (depth is None or camk is None):
+            raise ValueError("ModelSearch: verify needs the depth frames and their intrinsics")
+        found = search_poses(self.fields, job_model, clouds, scales, self.rotations, counts, K=self.K, stride=self.stride, top=top)
+        valid = found["rot"] >= 0                                                     # (J, top)
+        R = found["poses"][:, :, :, :3].reshape(J * top, 3, 3).contiguous()
+        t = found["poses"][:, :, :, 3].reshape(J * top, 3).contiguous()
+        s = scales.repeat_interleave(top).contiguous()
+        out = {}
+        if self.refine is not None:
+            ref = self.refine
+            gate = ref.max_dist.repeat_interleave(top).contiguous() if torch.is_tensor(ref.max_dist) else ref.max_dist
+            Rn, tn, sn, info, rmse = ops.icp_refine(ref.models, job_model.repeat_interleave(top).contiguous(),
+                                                    clouds.repeat_interleave(top, dim=0).contiguous(), R, t, s, gate,
+                                                    src_count=None if counts is None else counts.repeat_interleave(top).contiguous(), **ref.kw)
+            good = (info[:, 0] == 0) & valid.reshape(-1)
+            R, t, s = torch.where(good[:, None, None], Rn, R), torch.where(good[:, None], tn, t), torch.where(good, sn, s)
+            info, rmse = info.reshape(J, top, 4), rmse.reshape(J, top)
+        cand = join_RT(R, t, s)
+        if self.verify is not None:
+            vmesh = self.verify.jobs(J)
+            rep = lambda x: None if x is None else x.repeat_interleave(top).contiguous()
+            img = torch.zeros(J, dtype=torch.int32, device=dev) if job_img is None else job_img
+            vf = self.verify.on(rep(vmesh))(depth, camk, torch.nan_to_num(cand, nan=0.0), None, job_img=rep(img), mask=mask,
+                                            job_mask_val=rep(job_mask_val))
+            score = torch.where(valid, vf["score"].reshape(J, top), torch.full((), -1.0, device=dev))
+            rank = _first_where(score == score.max(1, keepdim=True).values)
+        elif self.refine is not None:
+            inl = torch.where(valid & (info[:, :, 0] == 0), info[:, :, 1], torch.full((), -1, dtype=torch.int32, device=dev))
+            most = inl == inl.max(1, keepdim=True).values
+            err = torch.where(most, torch.nan_to_num(rmse, nan=float("inf")), torch.full((), float("inf"), device=dev))
+            rank = _first_where(most & (err == err.min(1, keepdim=True).values))
+        else:
+            rank = torch.zeros(J, dtype=torch.int64, device=dev)
+        rank = rank.clamp(max=top - 1)
+        pick = lambda x: x[torch.arange(J, device=dev), rank].contiguous()           # x is (J, top, ...)
+        cand = cand.reshape(J, top, 4, 4)
+        out.update(RTs=pick(cand), search_cost=pick(found["cost"]), search_rank=rank.to(torch.int32), candidates=cand,
+                   cand_cost=found["cost"], anchors=found["anchors"])
+        if self.refine is not None:
+            chosen = pick(info)
+            out.update(icp_status=chosen[:, 0].contiguous(), icp_inliers=chosen[:, 1].contiguous(), icp_rmse=pick(rmse))
+        if self.verify is not None:
+            out.update(verify_score=pick(vf["score"].reshape(J, top)), verify_counts=pick(vf["counts"].reshape(J, top, -1)))
+        return out
+
+
 def batched_inference(net, clouds, cat_ids, mean_shapes, syms, max_batch=256):
     """clouds: list over images of (n_det_i, N, 3) tensors (same N); cat_ids / mean_shapes / syms likewise.
     Returns a list over images of dicts {'pred_RTs': (n_det_i,4,4) ndarray, 'pred_scales': (n_det_i,3) ndarray}."""
