@@ -113,6 +113,15 @@ __global__ __launch_bounds__(256, 1) void dec_fused_kernel(DecParams p)
     float4 e_b, e_sc, e_sh, e_v;
     uint32_t e_hi[8], e_lo[8];                                   // the block's packed halves: [2 g] = channels 0, 1 of group g, [2 g + 1] = 2, 3
     float e_l4[4];
+    // fp16 range guard of the INNER activations (they never leave the registers, so nobody else can look): the lane's largest activation of
+    // the layer being converted, over all its channels.  The layer's 32 x C block is out of range as an operand block of the tile kernels
+    // would be (TGP_FP16_OUT_OF_RANGE): something at or beyond 65504, or nothing at or above 2^-4 and not all zero.
+    float e_am = 0.f;
+    const bool live = m0 + r < p.M;                              // (rows past the end were never written: whatever they hold does not count)
+    auto block_bad = [&](const float am) {                       // wave-uniform
+        const bool big = __ballot(live && !(am < 65504.f)) != 0ull;
+        return big || (__ballot(live && am >= 0.0625f) == 0ull && __ballot(live && am > 0.f) != 0ull);
+    };
     auto epi = [&](f32x16 &acc, const float *vec, const int C, const int blk, const int sl) {
         const int g = sl >> 3, ph = sl & 7;
         const float *pv = vec + 32 * blk + 4 * h + 8 * g;
@@ -128,8 +137,11 @@ __global__ __launch_bounds__(256, 1) void dec_fused_kernel(DecParams p)
         } else if (ph == 4) {
             e_v.x += e_sh.x, e_v.y += e_sh.y, e_v.z += e_sh.z, e_v.w += e_sh.w;
         } else if (ph == 5) {
-            // ReLU as max(v, -0): what `v > 0 ? v : v * 0` gives for every number (a NaN becomes -0; non-finite sums are caught at the end)
+            // ReLU as max(v, -0): what `v > 0 ? v : v * 0` gives for every number.  A NaN becomes -0 and leaves no trace -- but with a
+            // finite operand block, finite weights and vectors, a NaN sum can only follow an activation that fp16 turned into hi = +inf,
+            // lo = -inf one layer earlier, and that one is seen here, as a number at or beyond 65504, before it is converted
             e_v.x = fmaxf(e_v.x, -0.f), e_v.y = fmaxf(e_v.y, -0.f), e_v.z = fmaxf(e_v.z, -0.f), e_v.w = fmaxf(e_v.w, -0.f);
+            e_am = fmaxf(e_am, fmaxf(fmaxf(e_v.x, e_v.y), fmaxf(e_v.z, e_v.w)));
         } else if (ph == 6) {
             const f32x4 x = {e_v.x, e_v.y, e_v.z, e_v.w};
             const uint2 hh = __builtin_bit_cast(uint2, __builtin_convertvector(x, f16x4));
@@ -200,6 +212,8 @@ __global__ __launch_bounds__(256, 1) void dec_fused_kernel(DecParams p)
         }
     }
 #undef DF_L3
+    bool bad = block_bad(e_am);                                  // layer 2's activations (both halves) are all converted
+    e_am = 0.f;
     // layer 3's first four blocks become fragments before layer 4 starts (its first unit reads them); the other four inside that unit
 #pragma unroll
     for (int blk = 0; blk < 4; ++blk)
@@ -216,6 +230,7 @@ __global__ __launch_bounds__(256, 1) void dec_fused_kernel(DecParams p)
             { epi(acc3[4 + (q >> 3)], v3, DF_C3, 4 + (q >> 3), 4 * (q & 7) + 2); epi(acc3[4 + (q >> 3)], v3, DF_C3, 4 + (q >> 3), 4 * (q & 7) + 3); })
     DF_BODY(2 * DF_U2H + 2 * DF_U3H + 1, acc4, 4, frag(acc3[4 + (s >> 1)], s & 1, 0), frag(acc3[4 + (s >> 1)], s & 1, 1), false, , , )
 #undef DF_BODY
+    bad |= block_bad(e_am);                                      // ... and layer 3's
 
     // ================================================================= layer 4's epilogue and the last conv (128 -> 3)
     // lane (point r, half h) holds channels 32 j + 4 h + (e & 3) + 8 (e >> 2) of block j
@@ -245,8 +260,12 @@ __global__ __launch_bounds__(256, 1) void dec_fused_kernel(DecParams p)
                 o3[o] = fmaf(x[3], w.w, fmaf(x[2], w.z, fmaf(x[1], w.y, fmaf(x[0], w.x, o3[o]))));
             }
         }
-    // a magnitude beyond fp16's range (or a NaN) anywhere in the chain makes the point's sums non-finite: the predicated fp32 chain redoes it
-    if (__ballot(!finite) != 0ull && lane == 0) atomicOr(p.flag, 1);
+    // The flag's contract: while it stays 0, every live row is the chain's result to the split's accuracy.  The operand block's range is
+    // checked on its magnitude word (above), layer 2's and layer 3's activations on their running maxima (`bad`); layer 4's activation is
+    // never split (the last conv reads it in fp32), so it has no range to leave: this test of it sees a NaN or an infinity that layer 4's
+    // own sums, vectors or weights brought (its ReLU keeps a NaN; the vectors and weights of layers 2 and 3 are taken to be finite -- a
+    // NaN of theirs ends as -0 in the ReLU).  The predicated fp32 chain of the caller redoes a flagged launch.
+    if ((bad || __ballot(!finite) != 0ull) && lane == 0) atomicOr(p.flag, 1);
 #pragma unroll
     for (int o = 0; o < 3; ++o) o3[o] += __shfl_xor(o3[o], 32, 64);
     const int row = m0 + r;
@@ -284,6 +303,9 @@ struct DecL1Params {
     int M, tiles;
     int main_tiles;                        // tiles [0, main_tiles) are one workgroup each; the others one workgroup per 32-channel block
 };
+
+// IEEE 754-2019 maximum (v_maximum3_f32): a NaN operand gives a NaN, where fmaxf (maxNum) gives the other operand
+__device__ __forceinline__ float dl_maximum(const float a, const float b) { return __builtin_elementwise_maximum(a, b); }
 
 struct DlG {                               // a block's gathered terms of the lane's four channel groups
     float4 g1[4], g2[4], rb[4];
@@ -391,8 +413,11 @@ __global__ __launch_bounds__(256, 1) void dec_l1_kernel(DecL1Params p)
             e_v.x += e_sh.x, e_v.y += e_sh.y;
         } else if (ph == 6) {
             e_v.z += e_sh.z, e_v.w += e_sh.w;
+            // the block's magnitude on the values BEFORE the ReLU, with the maximum that keeps a NaN (v_maximum3_f32): amax starts at 0, so
+            // for numbers this is the largest activation; a NaN pre-activation (a gathered addend's, say), which the ReLU below stores as a
+            // zero, stays in amax from here on
+            amax = dl_maximum(dl_maximum(amax, dl_maximum(dl_maximum(e_v.x, e_v.y), e_v.z)), e_v.w);
             e_v.x = fmaxf(e_v.x, -0.f), e_v.y = fmaxf(e_v.y, -0.f), e_v.z = fmaxf(e_v.z, -0.f), e_v.w = fmaxf(e_v.w, -0.f);   // ReLU as max(v, -0)
-            amax = fmaxf(amax, fmaxf(fmaxf(e_v.x, e_v.y), fmaxf(e_v.z, e_v.w)));
         } else {
             uint2 hh, ll;
             tgp_split4(e_v, hh, ll);
@@ -464,12 +489,16 @@ __global__ __launch_bounds__(256, 1) void dec_l1_kernel(DecL1Params p)
         DL_ITER(DL_NCB + 1, 1, false, false, true, true)
     }
 #undef DL_ITER
-    // the block's largest activation for the consumer's range guard (bits of a non-negative float order as the floats do)
-    if (m0 < p.M && p.h1_amax) {
+    // the block's largest activation for the consumer's range guard (bits of a non-negative float order as the floats do, an infinity's
+    // and a NaN's above every number's).  A block that met a NaN stored zeros in its place: its word becomes a NaN's bits -- out of range
+    // for every consumer -- and the chain's flag is raised here as well
+    if (m0 < p.M) {
         float m = amax;
 #pragma unroll
-        for (int o = 1; o < 64; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        if (lane == 0 && m > 0.f) atomicMax(p.h1_amax + rb, __float_as_uint(m));
+        for (int o = 1; o < 64; o <<= 1) m = dl_maximum(m, __shfl_xor(m, o, 64));
+        const bool nan = m != m;
+        if (lane == 0 && p.h1_amax && (m > 0.f || nan)) atomicMax(p.h1_amax + rb, nan ? 0x7fc00000u : __float_as_uint(m));
+        if (lane == 0 && nan) atomicOr(p.flag, 1);
     }
 }
 
