@@ -1662,6 +1662,79 @@ typedef struct tgp_pose_search_args {
 int64_t tgp_pose_search_workspace_bytes(int J, int R);
 int tgp_pose_search(const tgp_pose_search_args *args, tgp_stream_t stream);
 
+/* ---- Models from depth sequences: TSDF fusion and meshing (csrc/tsdf.hip; additive, ABI stays 8) ------------------------------------
+ * DESIGN.md section 3 "Models from depth sequences" is the contract; tests/tsdf_ref.py restates both kernels in NumPy, bit for bit.
+ * M cubes of G^3 voxels in model units: sum, weight (M, G, G, G) int32, voxel (ix, iy, iz) at (ix G + iy) G + iz, and meta (M, 4)
+ * float32 = the cube's centre ctr (3) and the voxel edge (tgp_field_build's layout).  A voxel's centre along axis a is
+ * c_a = ctr_a + (((float)i_a + 0.5f) - G/2) voxel: float32, the product and each sum rounded on their own.
+ *
+ * tgp_tsdf_integrate: job j = (frame job_img[j], volume job_model[j], pose job_pose[j] (3,4) float32 [s R | t], model to camera in
+ * metres); depth, camk, mask and job_mask_val as tgp_pose_verify takes them.  Every voxel of the job's volume, in float32:
+ *    p   = raster_vertex's pose of the centre: p_r = ((T_r0 x + T_r1 y) + T_r2 z) + T_r3;          skipped unless p_z > near
+ *    u   = K0 (p_x / p_z) + K2, v = K1 (p_y / p_z) + K3 (correctly rounded division, no contraction); the pixel is (rintf(u), rintf(v)),
+ *          ties to even;                                 skipped unless 0 <= rintf(u) <= W - 1 and 0 <= rintf(v) <= H - 1 (a NaN is not)
+ *    d   = depth[img, y, x];                             skipped if d == 0, or if a mask is given and mask[img, y, x] != job_mask_val[j]
+ *    sdf = (float)d - p_z 1000.f;                        skipped if sdf < -trunc
+ *    q   = (int)rintf(fminf(sdf, trunc) inv), inv = (float)(1024 / (double)trunc) made by the host;     sum += q, weight += 1
+ * The volumes are ADDED to: integer sums, so the result depends on neither the order of the jobs nor how they are spread over calls.
+ * A workgroup owns one 8 x 8 x 8 brick, walks all J jobs with the brick's sums in registers and adds them to memory once: no atomics.
+ * A job whose job_img is outside [0, S) or whose job_model is outside [0, M) adds nothing.  -> status (J) int32: 0, or 1 for such a
+ * job.  One kernel on the caller's stream, nothing read by the host; graph-capturable.
+ * TGP_EINVAL (before any launch): a NULL required pointer (with J > 0: the job arrays and status), mask without job_mask_val, S, H,
+ * W or M < 1, J < 0, trunc, inv or near <= 0 or not finite.  TGP_EUNSUPPORTED: G not a multiple of 8 in [TGP_TSDF_MIN_G,
+ * TGP_TSDF_MAX_G], J > TGP_TSDF_MAX_JOBS (|sum| <= 1025 J stays below 2^31), H or W > 16384, M (G/8)^3 >= 2^31.  J == 0 returns 0.
+ *
+ * tgp_tsdf_mesh_count / tgp_tsdf_mesh_emit: marching tetrahedra over volume ``model``.  The cube with its corner (0,0,0) at voxel
+ * (ix, iy, iz), ix, iy, iz < G - 1, takes part iff all eight corners have weight >= min_weight (>= 1); a corner is inside iff
+ * sum < 0.  The cube is split into the six Kuhn tetrahedra: tetrahedron k walks from corner (0,0,0) to (1,1,1) by the three axis
+ * steps in the order of the k-th permutation of (0, 1, 2) in lexicographic order; its corners in that walk are its path order.
+ * One or three corners inside: one triangle, its vertices on the three cut edges in the path order of the edges' other ends (the
+ * three outside corners, or the three inside ones).  Two inside (I0, I1) and two outside (O0, O1), each pair in path order: the quad
+ * I0O0, I0O1, I1O1, I1O0 as the triangles (0,1,2), (0,2,3).  A triangle whose bit in the tetrahedron's word of csrc/tsdf.hip's
+ * tsdf_flip (bit = the 4-bit case, bit c of which is path corner c inside) is set swaps its second and third vertex: every normal then points from
+ * the inside corners to the outside ones.  The vertex on an edge is computed from the end a earlier in the path (the one with the
+ * smaller flat index) to the other end b: f_a = (float)sum_a / (float)weight_a, t = f_a / (f_a - f_b), p = p_a + t (p_b - p_a) per
+ * axis on the voxel centres above, float32, each operation rounded on its own -- every tetrahedron that shares the edge gets the
+ * same bits.  Zero-area triangles are kept.
+ * count: counts (G^3) int32 = the triangles of each cube at its (0,0,0) corner's flat index (0 where there is no cube).  The host
+ * makes offsets (G^3) int64 = the inclusive prefix sum of counts.  emit: triangle n of the soup -- cube flat index, then
+ * tetrahedron, then triangle -- goes to verts[9 n .. 9 n + 8] if n < face_cap; info (2) int64 = {min(total, face_cap), total >
+ * face_cap}.  Rows of verts at and beyond 3 min(total, face_cap) are not written.  One kernel each; nothing read by the host.
+ * TGP_EINVAL: a NULL required pointer (emit: verts may be NULL when face_cap is 0), M < 1, model outside [0, M), min_weight < 1,
+ * face_cap < 0.  TGP_EUNSUPPORTED: G as above, face_cap > TGP_TSDF_MAX_FACES. */
+#define TGP_TSDF_MIN_G 16
+#define TGP_TSDF_MAX_G 256
+#define TGP_TSDF_MAX_JOBS 65535
+#define TGP_TSDF_MAX_FACES 100000000
+typedef struct tgp_tsdf_integrate_args {
+    const uint16_t *depth;
+    const float *camk;
+    int S, H, W;
+    int32_t *sum, *weight;
+    const float *meta;
+    int M, G;
+    const int32_t *job_img, *job_model;
+    const float *job_pose;
+    const uint8_t *mask;            /* may be NULL */
+    const uint8_t *job_mask_val;    /* required with mask, not read without */
+    int J;
+    float trunc, inv, near;
+    int32_t *status;
+} tgp_tsdf_integrate_args;
+int tgp_tsdf_integrate(const tgp_tsdf_integrate_args *args, tgp_stream_t stream);
+typedef struct tgp_tsdf_mesh_args {
+    const int32_t *sum, *weight;
+    const float *meta;
+    int M, G, model, min_weight;
+    int32_t *counts;
+    const int64_t *offsets;         /* emit only */
+    float *verts;                   /* emit only */
+    int64_t face_cap;               /* emit only */
+    int64_t *info;                  /* emit only */
+} tgp_tsdf_mesh_args;
+int tgp_tsdf_mesh_count(const tgp_tsdf_mesh_args *args, tgp_stream_t stream);
+int tgp_tsdf_mesh_emit(const tgp_tsdf_mesh_args *args, tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@ from .. import ops
 from ..evaluation import load_data_eval as lde
 from ..evaluation.metrics import compute_degree_cm_mAP
 from ..losses.utils_v2.model_utils import calc_cd, calc_emd
-from ..pose import IcpRefine, ModelSearch, Segmenter, SupportPlane, Verify, infer_device
+from ..pose import IcpRefine, ModelSearch, Segmenter, SupportPlane, Verify, infer_device, scan_models
 
 SYNSET_NAMES = ['BG', 'bottle', 'bowl', 'camera', 'can', 'laptop', 'mug']                                   # :115
 MEAN_SHAPE_MM = {1: (87, 220, 89), 2: (165, 80, 165), 3: (88, 128, 156), 4: (68, 146, 72), 5: (346, 200, 335), 6: (146, 83, 114)}
@@ -451,6 +451,57 @@ class myEvaluater:
         if pending is not None:
             fetch(pending)
         return results
+
+    def scan(self, sequence, tracked, camK=lde.REAL_INTRINSICS, volumes=None, G=64, trunc_mm=None, support=None, use_mask=True,
+             inst_ids=None, min_weight=1, near=0.01):
+        """Build a mesh model of every tracked object from the depth sequence it was tracked through (DESIGN.md section 3 "Models
+        from depth sequences"): TSDF fusion of all frames x objects in ONE ops.tsdf_integrate call, then marching tetrahedra.
+
+        sequence: the frames ``track`` took, {'depth' (H,W) uint16[, 'inst_mask' (H,W) uint8]}.  tracked: what ``track`` returned
+        for them (a list over frames of {'pred_RTs' (n,4,4)[, 'pred_scales' (n,3), 'tracked' (n,) bool]}; an object that is not
+        'tracked' in a frame is left out of that frame), or poses from anywhere else, ground truth included: a list over frames
+        of (n,4,4) arrays.  The poses are [s R | t], model units to camera metres, as pose.Verify and pose.IcpRefine read them; the
+        model comes out in those units.  volumes (an ops.TsdfVolumes with one cube per object; it is added to, so a scan can be
+        continued) or None: cubes of G^3 voxels about the model origin, sized by frame 0's 'pred_scales' (the object's extent in
+        model units).  trunc_mm: the truncation (default: two voxel edges of the coarsest volume at frame 0's scale: thin parts
+        need a truncation below their thickness).  support (a
+        pose.SupportPlane): each frame's supporting plane is cut out first, keyed by the frame's number as ``track`` does.
+        use_mask with inst_ids (n,) and an 'inst_mask' in every frame: object k only fuses the pixels whose byte is inst_ids[k].
+        The frames are uploaded once; nothing is read back before the meshing, which reads each volume's triangle count and soup.
+        -> (volumes, ops.MeshSet of the n scanned models); a volume without a face raises ValueError."""
+        if support is not None and not isinstance(support, SupportPlane):
+            raise TypeError("scan: support must be a pose.SupportPlane")
+        frames = list(sequence)
+        if not frames or len(tracked) != len(frames):
+            raise ValueError("scan: one entry of tracked per frame of a sequence that is not empty")
+        is_rec = isinstance(tracked[0], dict)
+        rts = np.stack([np.asarray(t["pred_RTs"] if is_rec else t, dtype=np.float32) for t in tracked])          # (T, n, 4, 4)
+        if rts.ndim != 4 or rts.shape[2:] != (4, 4) or rts.shape[1] < 1:
+            raise ValueError("scan: every frame needs (n,4,4) poses of the same n >= 1 objects")
+        T, n = rts.shape[:2]
+        live = np.stack([np.asarray(t["tracked"], dtype=bool) if is_rec and "tracked" in t else np.ones(n, dtype=bool) for t in tracked])
+        dev = self.device
+        if volumes is None:
+            if not (is_rec and "pred_scales" in tracked[0]):
+                raise ValueError("scan: without volumes, tracked[0]['pred_scales'] must give the objects' extents in model units")
+            volumes = ops.TsdfVolumes(np.zeros((n, 3), dtype=np.float32), np.asarray(tracked[0]["pred_scales"], dtype=np.float32).reshape(n, 3),
+                                      G, device=dev)
+        if not isinstance(volumes, ops.TsdfVolumes) or len(volumes) != n:
+            raise ValueError("scan: volumes must be an ops.TsdfVolumes with one cube for each of the %d objects" % n)
+        if trunc_mm is None:
+            s0 = np.cbrt(np.abs(np.linalg.det(rts[0, :, :3, :3].astype(np.float64))))
+            trunc_mm = 2000.0 * float((volumes.meta_host[:, 3].astype(np.float64) * s0).max())
+        masked = use_mask and inst_ids is not None and all("inst_mask" in fr for fr in frames)
+        job_model = np.where(live, np.arange(n, dtype=np.int32)[None, :], -1).astype(np.int32).reshape(-1)    # -1: the job is ignored
+        with torch.no_grad():
+            depth, inst, camk = lde._depth_frames(frames, camK, dev)
+            if support is not None:
+                depth = support(depth, camk, list(range(T)), self.seed)[0]
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            scan_models(volumes, depth, camk, up(rts.reshape(T * n, 4, 4)), job_img=up(np.repeat(np.arange(T, dtype=np.int32), n)),
+                        job_model=up(job_model), trunc_mm=trunc_mm, near=near, mask=inst.view(torch.uint8) if masked else None,
+                        job_mask_val=up(np.tile(np.asarray(inst_ids).astype(np.uint8), T)) if masked else None)
+            return volumes, ops.tsdf_meshset(volumes, min_weight)
 
 
 def calc_pose_metric(pred_results, output_path, per_obj=""):

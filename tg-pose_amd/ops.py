@@ -2581,6 +2581,193 @@ def pose_search(fields, job_model, clouds, counts, anchors, scales, rotations, K
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------ models from depth sequences
+TSDF_MIN_G, TSDF_MAX_G, TSDF_MAX_JOBS, TSDF_MAX_FACES = _lib.TSDF_MIN_G, _lib.TSDF_MAX_G, _lib.TSDF_MAX_JOBS, _lib.TSDF_MAX_FACES
+
+
+def tsdf_meta(center, extent, G):
+    """One volume's cube from its object's centre (3,) and extents (3,), in model units: (4,) float32 = the centre and the voxel
+    edge.  field_meta's rule: half edge = 0.575 x the largest extent, voxel = 2 half / G, float64 on the float32 inputs, each
+    rounded to float32 once -- a scanned model's distance field and its volume share a cube rule."""
+    import numpy as np
+    ctr = np.asarray(center, dtype=np.float32).reshape(3)
+    half = np.float32(0.575 * float(np.asarray(extent, dtype=np.float32).reshape(3).astype(np.float64).max()))
+    return np.concatenate([ctr, [np.float32(2.0 * float(half) / G)]]).astype(np.float32)
+
+
+class TsdfVolumes(object):
+    """M truncated-signed-distance volumes, one cube of G^3 voxels per object in the object's model units (csrc/tsdf.hip; DESIGN.md
+    section 3 "Models from depth sequences").  ``sum`` and ``weight`` (M,G,G,G) int32 on ``device``: the voxel's summed quantised
+    distances (1024 = the truncation) and how many frames it was seen in, voxel (ix, iy, iz) at (ix G + iy) G + iz; ``meta`` (M,4)
+    float32 = the cube's centre and the voxel edge, as DistanceFields.meta; ``meta_host`` the same on the host.  A voxel's centre
+    along an axis is c + (((float)i + 0.5f) - G/2) * voxel in float32.  centers, extents: (M,3) model units (tsdf_meta's rule)."""
+
+    def __init__(self, centers, extents, G=64, device="cuda"):
+        import numpy as np
+        if not (isinstance(G, int) and TSDF_MIN_G <= G <= TSDF_MAX_G and G % 8 == 0):
+            raise ValueError("TsdfVolumes: G must be a multiple of 8 in [%d, %d]" % (TSDF_MIN_G, TSDF_MAX_G))
+        centers, extents = np.asarray(centers, dtype=np.float32), np.asarray(extents, dtype=np.float32)
+        if centers.ndim != 2 or centers.shape[1] != 3 or centers.shape[0] < 1 or extents.shape != centers.shape:
+            raise ValueError("TsdfVolumes: centers and extents must be (M,3) with M >= 1")
+        if not (np.isfinite(centers).all() and np.isfinite(extents).all() and (extents.max(1) > 0).all()):
+            raise ValueError("TsdfVolumes: centers and extents must be finite and every object's largest extent positive")
+        self._alloc(np.stack([tsdf_meta(c, e, G) for c, e in zip(centers, extents)]), G, device)
+
+    def _alloc(self, meta, G, device):
+        import numpy as np
+        self.G = G
+        self.meta_host = np.ascontiguousarray(meta, dtype=np.float32)
+        self.meta = torch.from_numpy(self.meta_host).to(device)
+        M = len(self.meta_host)
+        self.sum = torch.zeros(M, G, G, G, device=device, dtype=torch.int32)
+        self.weight = torch.zeros(M, G, G, G, device=device, dtype=torch.int32)
+
+    @classmethod
+    def from_meta(cls, meta, G, device="cuda"):
+        """volumes on given cubes: meta (M,4) float32 = each cube's centre and its voxel edge (finite, the edge positive), for
+        instance an ops.DistanceFields' meta_host, so that a field and a volume cover the same cube"""
+        import numpy as np
+        meta = np.asarray(meta, dtype=np.float32)
+        if not (isinstance(G, int) and TSDF_MIN_G <= G <= TSDF_MAX_G and G % 8 == 0):
+            raise ValueError("TsdfVolumes: G must be a multiple of 8 in [%d, %d]" % (TSDF_MIN_G, TSDF_MAX_G))
+        if meta.ndim != 2 or meta.shape[1] != 4 or meta.shape[0] < 1 or not np.isfinite(meta).all() or not (meta[:, 3] > 0).all():
+            raise ValueError("TsdfVolumes.from_meta: meta must be (M,4) finite rows with a positive voxel edge")
+        self = cls.__new__(cls)
+        self._alloc(meta, G, device)
+        return self
+
+    @classmethod
+    def from_meshset(cls, meshset, G=64, pad=1.0):
+        """volumes around the meshes of an ops.MeshSet: each mesh's bounding box, its extents times ``pad``"""
+        import numpy as np
+        if not isinstance(meshset, MeshSet):
+            raise TypeError("TsdfVolumes.from_meshset: meshset must be an ops.MeshSet")
+        v, vptr = meshset.verts.cpu().numpy(), meshset.vptr.cpu().numpy()
+        lo = np.stack([v[vptr[m]:vptr[m + 1]].min(0) for m in range(len(meshset))]).astype(np.float64)
+        hi = np.stack([v[vptr[m]:vptr[m + 1]].max(0) for m in range(len(meshset))]).astype(np.float64)
+        return cls(((lo + hi) * 0.5).astype(np.float32), ((hi - lo) * float(pad)).astype(np.float32), G, meshset.device)
+
+    def __len__(self):
+        return self.sum.shape[0]
+
+    def zero_(self):
+        self.sum.zero_(), self.weight.zero_()
+        return self
+
+
+def tsdf_integrate(volumes, depth, camk, job_img, job_model, job_pose, trunc_mm, near=0.01, mask=None, job_mask_val=None):
+    """Fuse J posed depth frames into truncated-signed-distance volumes in one call (tgp_tsdf_integrate, csrc/tsdf.hip; DESIGN.md
+    section 3 "Models from depth sequences").  Job j projects every voxel centre of volume job_model[j] at job_pose[j] into frame
+    job_img[j]; a voxel in front of near whose pixel (rounded, ties to even) lies in the frame, holds a depth, carries the job's
+    mask byte when a mask is given, and is not more than trunc_mm behind the surface adds q = rint(1024 min(sdf, trunc) / trunc) to
+    its sum and 1 to its weight, sdf = depth - 1000 z in millimetres.  All tensors on the volumes' GPU, as pose_verify takes them:
+    depth (S,H,W) 16-bit millimetres, camk (S,4) float32, job_img and job_model (J) int32, job_pose (J,3,4) float32 [s R | t] (model
+    -> camera, metres), mask (S,H,W) uint8 with job_mask_val (J) uint8, or neither.  The volumes are added to in place; integer
+    sums, so neither the order of the jobs nor their split over calls matters.  -> status (J) int32: 1 for a job whose frame or
+    volume index is out of range (it adds nothing), else 0.  Nothing is read back."""
+    if not isinstance(volumes, TsdfVolumes):
+        raise TypeError("tsdf_integrate: volumes must be an ops.TsdfVolumes")
+    dev = volumes.sum.device
+    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in (torch.int16, torch.uint16) and depth.is_contiguous()):
+        raise TypeError("tsdf_integrate: depth must be a contiguous 16-bit GPU tensor")
+    given = [(depth, "depth", None), (camk, "camk", torch.float32), (job_img, "job_img", torch.int32), (job_model, "job_model", torch.int32),
+             (job_pose, "job_pose", torch.float32)]
+    if (mask is None) != (job_mask_val is None):
+        raise ValueError("tsdf_integrate: mask and job_mask_val come together")
+    if mask is not None:
+        given += [(mask, "mask", torch.uint8), (job_mask_val, "job_mask_val", torch.uint8)]
+    for t, name, dt in given:
+        if dt is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise TypeError("tsdf_integrate: %s must be a contiguous %s GPU tensor" % (name, str(dt).replace("torch.", "")))
+        if t.device != dev:
+            raise ValueError("tsdf_integrate: %s is not on the volumes' device" % name)
+    if depth.dim() != 3 or depth.numel() == 0:
+        raise ValueError("tsdf_integrate: depth must be (S,H,W)")
+    S, H, W = depth.shape
+    J = job_img.numel()
+    if camk.shape != (S, 4) or job_img.dim() != 1 or job_model.shape != (J,) or job_pose.shape != (J, 3, 4):
+        raise ValueError("tsdf_integrate: camk (S,4), job_img (J), job_model (J), job_pose (J,3,4) are expected")
+    if mask is not None and (mask.shape != (S, H, W) or job_mask_val.shape != (J,)):
+        raise ValueError("tsdf_integrate: mask (S,H,W) and job_mask_val (J) are expected")
+    import numpy as np
+    trunc = np.float32(trunc_mm)
+    if not (np.isfinite(trunc) and trunc > 0):
+        raise ValueError("tsdf_integrate: trunc_mm must be positive (millimetres)")
+    inv = np.float32(1024.0 / float(trunc))
+    if not (np.isfinite(inv) and inv > 0):
+        raise ValueError("tsdf_integrate: trunc_mm is out of range")
+    if not float(near) > 0.0:
+        raise ValueError("tsdf_integrate: near must be positive")
+    if J > TSDF_MAX_JOBS or H > 16384 or W > 16384:
+        raise ValueError("tsdf_integrate: at most %d jobs and frames of at most 16384 pixels a side" % TSDF_MAX_JOBS)
+    status = torch.empty(J, device=dev, dtype=torch.int32)
+    if J == 0:
+        return status
+    a = _lib.TsdfIntegrateArgs(depth=_p(depth), camk=_p(camk), S=S, H=H, W=W, sum=_p(volumes.sum), weight=_p(volumes.weight),
+                               meta=_p(volumes.meta), M=len(volumes), G=volumes.G, job_img=_p(job_img), job_model=_p(job_model),
+                               job_pose=_p(job_pose), mask=_p(mask), job_mask_val=_p(job_mask_val), J=J, trunc=float(trunc), inv=float(inv),
+                               near=float(near), status=_p(status))
+    check(_lib.lib().tgp_tsdf_integrate(ctypes.byref(a), _stream(job_pose)), "tgp_tsdf_integrate")
+    return status
+
+
+def _tsdf_mesh_args(volumes, model, min_weight, who):
+    if not isinstance(volumes, TsdfVolumes):
+        raise TypeError("%s: volumes must be an ops.TsdfVolumes" % who)
+    if not (isinstance(model, int) and 0 <= model < len(volumes)):
+        raise ValueError("%s: model must index the %d volumes" % (who, len(volumes)))
+    if not (isinstance(min_weight, int) and min_weight >= 1):
+        raise ValueError("%s: min_weight must be an int >= 1" % who)
+    G, dev = volumes.G, volumes.sum.device
+    counts = torch.empty(G * G * G, device=dev, dtype=torch.int32)
+    a = _lib.TsdfMeshArgs(sum=_p(volumes.sum), weight=_p(volumes.weight), meta=_p(volumes.meta), M=len(volumes), G=G, model=model,
+                          min_weight=min_weight, counts=_p(counts))
+    check(_lib.lib().tgp_tsdf_mesh_count(ctypes.byref(a), _stream(volumes.sum)), "tgp_tsdf_mesh_count")
+    return a, counts, torch.cumsum(counts, 0, dtype=torch.int64)
+
+
+def tsdf_mesh(volumes, model, min_weight=1, face_cap=None):
+    """The surface of one volume as a triangle soup by marching tetrahedra (tgp_tsdf_mesh_count / _emit, csrc/tsdf.hip; DESIGN.md
+    section 3 "Models from depth sequences").  A cube of eight voxel centres takes part iff all eight have weight >= min_weight; a
+    corner is inside iff its sum is negative; the cube is cut into the six Kuhn tetrahedra and every cut edge's vertex is
+    interpolated from the end with the smaller flat index, so shared edges share bits.  Triangles are ordered by cube flat index,
+    tetrahedron, triangle, and wind so that their normals point outward (from inside to outside corners).
+    face_cap None: the triangle count is read back once and ``verts`` is exactly (3 F,3).  face_cap an int: nothing is read back,
+    ``verts`` is (3 face_cap,3), its rows beyond 3 n_faces zero, and triangles beyond the cap are dropped in that order.
+    -> dict: verts float32 (model units), faces (rows/3, 3) int32 = arange, n_faces () int64 = min(total, face_cap), status () int64
+    = 1 iff triangles were dropped, counts (G^3) int32 = each cube's triangles; all on the volumes' device."""
+    a, counts, offsets = _tsdf_mesh_args(volumes, model, min_weight, "tsdf_mesh")
+    dev = counts.device
+    if face_cap is None:
+        cap = int(offsets[-1].item())                        # the read-back
+    elif isinstance(face_cap, int) and 0 <= face_cap <= TSDF_MAX_FACES:
+        cap = face_cap
+    else:
+        raise ValueError("tsdf_mesh: face_cap must be None or an int in [0, %d]" % TSDF_MAX_FACES)
+    if cap > TSDF_MAX_FACES:
+        raise ValueError("tsdf_mesh: the volume has %d triangles, above the cap of %d; pass a face_cap" % (cap, TSDF_MAX_FACES))
+    verts = torch.zeros(3 * cap, 3, device=dev, dtype=torch.float32)
+    info = torch.zeros(2, device=dev, dtype=torch.int64)
+    a.offsets, a.verts, a.face_cap, a.info = _p(offsets), _p(verts) if cap else None, cap, _p(info)
+    check(_lib.lib().tgp_tsdf_mesh_emit(ctypes.byref(a), _stream(volumes.sum)), "tgp_tsdf_mesh_emit")
+    return {"verts": verts, "faces": torch.arange(3 * cap, device=dev, dtype=torch.int32).reshape(cap, 3), "n_faces": info[0],
+            "status": info[1], "counts": counts}
+
+
+def tsdf_meshset(volumes, min_weight=1):
+    """Every volume's surface (tsdf_mesh) as one ops.MeshSet on the volumes' device: what IcpModels.from_meshset, pose.Verify,
+    DistanceFields (through IcpModels) and evaluation.bop take.  Each volume's triangle count is read back once, and its soup once
+    (MeshSet packs on the host).  A volume without a face is refused by name."""
+    meshes = []
+    for m in range(len(volumes)):
+        out = tsdf_mesh(volumes, m, min_weight)
+        if out["verts"].shape[0] == 0:
+            raise ValueError("tsdf_meshset: volume %d has no face (no cube with all eight corners seen %d times and a sign change)"
+                             % (m, min_weight))
+        meshes.append((out["verts"].cpu().numpy(), out["faces"].cpu().numpy()))
+    return MeshSet(meshes, device=volumes.sum.device)
+
+
 # ------------------------------------------------------------------------------------------------------------ the supporting plane
 PLANE_STATUS = {1: "no hypothesis reached min_inliers", 2: "a refit was not finite (the plane of before it is returned)"}
 

@@ -186,6 +186,24 @@ class Verify(object):
         return out
 
 
+def scan_models(volumes, depth, camk, RTs, scales=None, job_img=None, job_model=None, trunc_mm=None, near=0.01, mask=None,
+                job_mask_val=None):
+    """TSDF fusion (ops.tsdf_integrate) of depth frames (S,H,W) into ``volumes`` (ops.TsdfVolumes) at the project's 4x4 poses
+    [s R | t], as verify_poses is ops.pose_verify's 4x4 form: job j fuses frame job_img[j] (default: frame 0) into volume
+    job_model[j] (default: volume j) at RTs[j]; scales: see verify_job_pose (the volume is then in the normalised model's units).
+    trunc_mm: the truncation in millimetres (default: two voxel edges of the coarsest volume, at the first pose's scale -- one
+    read of RTs[0]; pass a number to read nothing back).  The job poses are built on the device.  -> status (J,) int32."""
+    J, dev = RTs.shape[0], RTs.device
+    if job_img is None:
+        job_img = torch.zeros(J, dtype=torch.int32, device=dev)
+    if job_model is None:
+        job_model = torch.arange(J, dtype=torch.int32, device=dev)
+    P = verify_job_pose(RTs, scales)
+    if trunc_mm is None:
+        trunc_mm = 2000.0 * float(volumes.meta_host[:, 3].max()) * float(P[0, :, :3].double().det().abs().pow(1.0 / 3.0))
+    return ops.tsdf_integrate(volumes, depth, camk, job_img, job_model, P, trunc_mm, near=near, mask=mask, job_mask_val=job_mask_val)
+
+
 def cloud_anchors(clouds, counts=None):
     """The mean of each cloud's finite rows (of the first counts[j] rows): float64 sums on the device, rounded once -> (J,3) float32;
     a cloud without a finite row gives 0."""
