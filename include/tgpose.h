@@ -1735,6 +1735,56 @@ typedef struct tgp_tsdf_mesh_args {
 int tgp_tsdf_mesh_count(const tgp_tsdf_mesh_args *args, tgp_stream_t stream);
 int tgp_tsdf_mesh_emit(const tgp_tsdf_mesh_args *args, tgp_stream_t stream);
 
+/* ---- Ray casting of TSDF volumes (csrc/raycast.hip; additive, ABI stays 8) ----------------------------------------------------------
+ * DESIGN.md section 3 "Ray casting and frame-to-model tracking" is the contract; tests/raycast_ref.py restates the kernel in NumPy, bit
+ * for bit.  The volumes are tgp_tsdf_integrate's (sum, weight, meta above).  Job j = (volume job_model[j], intrinsics camk[job_img[j]]
+ * = fx, fy, cx, cy, inverse pose job_inv[j] (3,4) float32 = camera (metres) -> model units, the inverse of the [s R | t] that
+ * tgp_tsdf_integrate takes, made in float64 and rounded once, window job_window[j] = (u0, v0, du, dv) float32); the call casts h x w
+ * rays per job, ray (r, c) through the pixel coordinates u = u0 + (float)c du, v = v0 + (float)r dv (the loaders' convention: pixel
+ * (x, y) is the ray ((x - cx) / fx, (y - cy) / fy, 1)).  float32, every operation rounded on its own, correctly rounded divisions and
+ * square roots; I = job_inv[j], (c_a, voxel) = meta, h = (float)(G/2) - 0.5f, L = (float)(G - 1):
+ *    d    = ((u - cx) / fx, (v - cy) / fy);    m_a = (I_a0 d_x + I_a1 d_y) + I_a2;    e_a = m_a / voxel;    o_a = (I_a3 - c_a) / voxel + h
+ *           -- the ray in the volume's voxel coordinates (voxel centre i at coordinate i) is g_a(z) = o_a + z e_a, z the camera depth
+ *    clip : z_in = near, z_out = +inf; per axis with e_a != 0: t0 = (0 - o_a) / e_a, t1 = (L - o_a) / e_a, z_in = fmaxf(z_in, fminf(t0,
+ *           t1)), z_out = fminf(z_out, fmaxf(t0, t1)); with e_a == 0 the ray misses unless 0 <= o_a <= L.  len = sqrtf((e_x e_x + e_y e_y)
+ *           + e_z e_z); dz = step / len.  The ray misses unless len > 0, dz > 0, z_in <= z_out and all of these are finite.
+ *    march: sample k = 0, 1, ..., max_samples - 1 at z_k = z_in + (float)k dz while z_k <= z_out.  Its point g = o + z_k e; it is
+ *           UNKNOWN unless -1 <= g_a <= G on every axis.  Its cell is i_a = clamp((int)floorf(g_a), 0, G - 2), t_a = g_a - (float)i_a;
+ *           the cell's eight voxels must all have weight >= min_weight, else the sample is unknown; f_v = (float)sum / (float)weight.
+ *           f = trilinear: along z first, c_xy = f_xy0 + t_z (f_xy1 - f_xy0); c_x = c_x0 + t_y (c_x1 - c_x0); f = c_0 + t_x (c_1 - c_0).
+ *           An unknown sample forgets the previous one.  A known f > 0 becomes the previous one.  A known f <= 0 ends the ray: a hit
+ *           iff the sample before it was known (and so positive), at z* = z_{k-1} + dz (f_{k-1} / (f_{k-1} - f_k)); else a miss.
+ *    hit  : g* = o + z* e, its cell and t as above (a miss if g* is out of the range above or one of the eight is unseen);
+ *           gradient n_x = c_1 - c_0;  n_y = d_0 + t_x (d_1 - d_0), d_x = c_x1 - c_x0;  n_z = q_0 + t_x (q_1 - q_0), q_x = r_x0 + t_y
+ *           (r_x1 - r_x0), r_xy = f_xy1 - f_xy0;  s = sqrtf((n_x n_x + n_y n_y) + n_z n_z), a miss unless 0 < s < inf; normal = n / s
+ *           (the TSDF is positive outside: outward);  vertex_a = c_a + ((g*_a + 0.5f) - (float)(G/2)) voxel (model units).
+ * -> z (J,h,w) float32 = z* (0 on a miss); depth (J,h,w) uint16 = rintf(z* 1000.f), 0 beyond 65535 or on a miss; vertex, normal
+ * (J,h,w,3) float32, zeros on a miss; count (J) int32 = the job's hits; status (J) int32 = 1 for a job whose job_model is outside
+ * [0, M) or whose job_img is outside [0, S): all its rays miss.  A NaN anywhere makes a comparison false and the ray a miss; cell
+ * indices are clamped as integers before every load.  One wave casts an 8 x 8 patch of rays; count is summed by wave ballots and one
+ * integer atomic per wave on a zeroed word: two calls give identical bytes.  One memset and one kernel on the caller's stream, nothing
+ * read by the host; graph-capturable.
+ * TGP_EINVAL (before any launch): a NULL required pointer, S or M < 1, J < 0, h or w < 1, min_weight < 1, step or near <= 0 or not
+ * finite.  TGP_EUNSUPPORTED: G not a multiple of 8 in [TGP_TSDF_MIN_G, TGP_TSDF_MAX_G], J > TGP_TSDF_MAX_JOBS, h or w >
+ * TGP_RAYCAST_MAX_SIDE, step < 1/16 (the march is at most 16 sqrt(3) G + 2 samples).  J == 0 returns 0. */
+#define TGP_RAYCAST_MAX_SIDE 16384
+typedef struct tgp_tsdf_raycast_args {
+    const int32_t *sum, *weight;
+    const float *meta;
+    int M, G;
+    const float *camk;
+    int S;
+    const int32_t *job_img, *job_model;
+    const float *job_inv, *job_window;
+    int J, h, w, min_weight;
+    float step, near;
+    float *z;
+    uint16_t *depth;
+    float *vertex, *normal;
+    int32_t *count, *status;
+} tgp_tsdf_raycast_args;
+int tgp_tsdf_raycast(const tgp_tsdf_raycast_args *args, tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -503,6 +503,108 @@ class myEvaluater:
                         job_mask_val=up(np.tile(np.asarray(inst_ids).astype(np.uint8), T)) if masked else None)
             return volumes, ops.tsdf_meshset(volumes, min_weight)
 
+    def scan_track(self, sequence, init, camK=lde.REAL_INTRINSICS, ratio=None, volumes=None, G=64, trunc_mm=None, refine_kw=None,
+                   n_pts=1024, sampler=None, use_mask=True, support=None, min_inlier_frac=0.5, max_rmse=None, near=0.01):
+        """Track objects that have no model while scanning them (DESIGN.md section 3 "Ray casting and frame-to-model tracking"): each
+        frame is registered to the TSDF volumes as they stand and is then fused into them.  One pose per object in frame 0 is all it
+        needs.
+
+        sequence, init, camK, ratio, n_pts, sampler, use_mask, support: as ``track`` takes them (init['RTs'] are [s R | t], model
+        units to camera metres, and init['scales'] the objects' extents in model units, as ``scan`` reads them; class_ids are not
+        used).  volumes: an ops.TsdfVolumes with one cube per object (it is added to), default ``scan``'s cubes of G^3 voxels from
+        init['scales']; trunc_mm: default ``scan``'s two voxel edges.  refine_kw: pose.RaycastRefine's keywords (default: max_dist
+        = three voxel edges of the coarsest volume at frame 0's scale, mode 'plane').
+        Frame 0 is fused at init's poses.  Frame k >= 1: the optional plane cut, the ball crop round the previous poses
+        (load_data_eval.clouds_from_poses, as ``track`` crops), pose.RaycastRefine from the previous poses, and ONE
+        ops.tsdf_integrate call.  An object is registered when its crop and its ICP succeeded, its inliers reach min_inlier_frac x
+        its cloud's finite rows and (with max_rmse, metres) its rmse stays within it; one that is not keeps its previous pose, and
+        its job's volume index becomes -1 on the device, so that the frame adds nothing to its volume.  Nothing is read back between
+        frames; the results are fetched on the fetch stream as ``track`` fetches them.
+        -> (results, volumes): per frame ``track``'s {'pred_RTs', 'pred_scales', 'status', 'tracked'} plus 'icp_status',
+        'icp_inliers' (int32), 'icp_rmse' (float32), 'ray_hits' (int32) and 'fused' (bool: registered, and so fused), (n,) each
+        (frame 0: status 0, no ICP, fused).  Mesh the volumes with ops.tsdf_meshset."""
+        from ..pose import RaycastRefine, verify_job_pose
+        if ratio is None:
+            raise ValueError("scan_track: ratio is required (the reference fixes none)")
+        if support is not None and not isinstance(support, SupportPlane):
+            raise TypeError("scan_track: support must be a pose.SupportPlane")
+        sampler = sampler or (self.sampler if self.sampler in ("device", "fps") else "device")
+        if sampler not in ("device", "fps"):
+            raise ValueError("scan_track: sampler must be 'device' or 'fps' (nothing is read back between frames)")
+        if not 0.0 <= float(min_inlier_frac) <= 1.0:
+            raise ValueError("scan_track: min_inlier_frac must be in [0, 1]")
+        dev = self.device
+        rts0 = np.asarray(init["RTs"], dtype=np.float32).reshape(-1, 4, 4)
+        n = len(rts0)
+        scales0 = np.asarray(init["scales"], dtype=np.float32).reshape(n, 3)
+        if volumes is None:
+            volumes = ops.TsdfVolumes(np.zeros((n, 3), dtype=np.float32), scales0, G, device=dev)
+        if not isinstance(volumes, ops.TsdfVolumes) or len(volumes) != n:
+            raise ValueError("scan_track: volumes must be an ops.TsdfVolumes with one cube for each of the %d objects" % n)
+        s0 = np.cbrt(np.abs(np.linalg.det(rts0[:, :3, :3].astype(np.float64))))
+        voxel_m = float((volumes.meta_host[:, 3].astype(np.float64) * s0).max())
+        if trunc_mm is None:
+            trunc_mm = 2000.0 * voxel_m
+        kw = dict(refine_kw or {})
+        kw.setdefault("max_dist", 3.0 * voxel_m)
+        kw.setdefault("near", near)
+        refine = RaycastRefine(volumes, kw.pop("max_dist"), **kw)
+        rts, scales = torch.from_numpy(rts0).to(dev), torch.from_numpy(scales0).to(dev)
+        inst_ids = init.get("inst_ids") if use_mask else None
+        mask_val = torch.as_tensor(np.asarray(inst_ids), dtype=torch.uint8).to(dev) if inst_ids is not None else None
+        job_img = torch.zeros(n, dtype=torch.int32, device=dev)
+        every = torch.arange(n, dtype=torch.int32, device=dev)
+        results, pending = [], None
+
+        def fetch(item):
+            done, tensors = item
+            with torch.cuda.stream(self._fetch):
+                self._fetch.wait_event(done)
+                for x in tensors:
+                    x.record_stream(self._fetch)
+                r, s, st, info, rmse, hits, fused = (x.cpu().numpy() for x in tensors)
+            results.append(dict(pred_RTs=r, pred_scales=s, status=st, tracked=st == 0, icp_status=info[:, 0].copy(),
+                                icp_inliers=info[:, 1].copy(), icp_rmse=rmse, ray_hits=hits, fused=fused))
+        for k, frame in enumerate(sequence):
+            masks = inst_ids if inst_ids is not None and "inst_mask" in frame else None
+            with torch.no_grad():
+                depth, inst, camk = lde._depth_frames([frame], camK, dev)
+                H, W = depth.shape[1:]
+                if support is not None:
+                    depth = support(depth, camk, [k], self.seed)[0]
+                if k == 0:
+                    status = torch.zeros(n, dtype=torch.int32, device=dev)
+                    info = torch.zeros(n, 4, dtype=torch.int32, device=dev)
+                    rmse = torch.zeros(n, dtype=torch.float32, device=dev)
+                    hits = torch.zeros(n, dtype=torch.int32, device=dev)
+                    ok = torch.ones(n, dtype=torch.bool, device=dev)
+                else:
+                    crop = dict(depth=depth) if inst is None else dict(depth=depth, inst_mask=inst)
+                    pts, ok, _, counts = lde.clouds_from_poses(crop, job_img, rts, scales, ratio, camK, n_pts=n_pts, sampler=sampler, masks=masks,
+                                                               seed=self.seed + k, fps_pool=self.fps_pool, device=dev, return_counts=True)
+                    new_rts, info, rmse, hits = refine(pts, rts, camk, job_img, H, W)   # a failed crop's NaN rows are never inliers
+                    rows = torch.isfinite(pts).all(-1).sum(1)
+                    ok = ok & (info[:, 0] == 0) & (info[:, 1].float() >= float(min_inlier_frac) * rows.float())
+                    if max_rmse is not None:
+                        ok = ok & (rmse <= float(max_rmse))
+                    rts = torch.where(ok[:, None, None], new_rts, rts)
+                    status = counts[:, 3].contiguous()
+                job_model = torch.where(ok, every, torch.full_like(every, -1))           # -1: the job adds nothing
+                ops.tsdf_integrate(volumes, depth, camk, job_img, job_model, verify_job_pose(rts), trunc_mm, near=near,
+                                   mask=inst.view(torch.uint8) if masks is not None else None, job_mask_val=mask_val if masks is not None else None)
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(dev))
+            item = (done, (rts, scales, status, info, rmse, hits, ok))
+            if pending is not None:
+                fetch(pending)
+            pending = item
+            if not self.overlap:
+                fetch(pending)
+                pending = None
+        if pending is not None:
+            fetch(pending)
+        return results, volumes
+
 
 def calc_pose_metric(pred_results, output_path, per_obj=""):
     """:111-175 -- the mAP tables and the lines the reference logs (degree 0..60, shift 0..10 cm by 0.5, IoU 0..1 by 0.01)."""

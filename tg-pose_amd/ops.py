@@ -2402,6 +2402,22 @@ class IcpModels(object):
         out = mesh_sample(meshset, meshes, n, keys=list(range(len(meshes))), seed=seed, normals=True, check_status=True)
         return cls(out["points"])
 
+    @classmethod
+    def from_raycast(cls, rc):
+        """one model per job of a tsdf_raycast result: the job's hits [vertex, normal] packed to the front in ray order (a stable sort
+        of the miss mask and a gather, on the device), counts = rc['count']; rows past the count are the misses' zeros.  Nothing is
+        read back.  h w must not exceed ICP_MAX_POINTS."""
+        z = rc["z"]
+        J, n = z.shape[0], z.shape[1] * z.shape[2]
+        if not 1 <= n <= ICP_MAX_POINTS:
+            raise ValueError("IcpModels.from_raycast: h w = %d rays a job, at most %d make a model" % (n, ICP_MAX_POINTS))
+        if J < 1:
+            raise ValueError("IcpModels.from_raycast: no job")
+        miss = (z.reshape(J, n) <= 0).to(torch.uint8)
+        order = torch.sort(miss, dim=1, stable=True).indices
+        rows = torch.cat([rc["vertex"].reshape(J, n, 3), rc["normal"].reshape(J, n, 3)], 2)
+        return cls(torch.gather(rows, 1, order[:, :, None].expand(J, n, 6)).contiguous(), rc["count"])
+
 
 def icp_check_status(info, what="icp_refine"):
     """one read of the (J,4) info words; raises TgpError naming the first failed job"""
@@ -2766,6 +2782,116 @@ def tsdf_meshset(volumes, min_weight=1):
                              % (m, min_weight))
         meshes.append((out["verts"].cpu().numpy(), out["faces"].cpu().numpy()))
     return MeshSet(meshes, device=volumes.sum.device)
+
+
+# ------------------------------------------------------------------------------------------------------------ ray casting of the volumes
+RAYCAST_MAX_SIDE = _lib.RAYCAST_MAX_SIDE
+
+
+def pose_inverse(job_pose):
+    """(J,3,4) float32 [s R | t] on the GPU -> (J,3,4) float32: the inverse map (camera -> model), by cofactors in float64 on the
+    device in a fixed order of single operations, rounded to float32 once (tests/raycast_ref.py inverse_pose does the same
+    operations in NumPy).  Nothing is read back; a NaN stays a NaN."""
+    T = job_pose.to(torch.float64)
+    a, b, c, d, e, f, g, h, i = (T[:, r, k] for r in range(3) for k in range(3))
+    c00, c01, c02 = e * i - f * h, c * h - b * i, b * f - c * e
+    c10, c11, c12 = f * g - d * i, a * i - c * g, c * d - a * f
+    c20, c21, c22 = d * h - e * g, b * g - a * h, a * e - b * d
+    det = (a * c00 + b * c10) + c * c20
+    A = torch.stack([torch.stack([c00, c01, c02], 1), torch.stack([c10, c11, c12], 1), torch.stack([c20, c21, c22], 1)], 1) / det[:, None, None]
+    t = T[:, :, 3]
+    back = -((A[:, :, 0] * t[:, None, 0] + A[:, :, 1] * t[:, None, 1]) + A[:, :, 2] * t[:, None, 2])
+    return torch.cat([A, back[:, :, None]], 2).to(torch.float32).contiguous()
+
+
+def _raycast_jobs(volumes, camk, job_img, job_model, job_pose, who):
+    if not isinstance(volumes, TsdfVolumes):
+        raise TypeError("%s: volumes must be an ops.TsdfVolumes" % who)
+    dev = volumes.sum.device
+    for t, name, dt in ((camk, "camk", torch.float32), (job_img, "job_img", torch.int32), (job_model, "job_model", torch.int32),
+                        (job_pose, "job_pose", torch.float32)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise TypeError("%s: %s must be a contiguous %s GPU tensor" % (who, name, str(dt).replace("torch.", "")))
+        if t.device != dev:
+            raise ValueError("%s: %s is not on the volumes' device" % (who, name))
+    J = job_img.numel()
+    if camk.dim() != 2 or camk.shape[1] != 4 or camk.shape[0] < 1 or job_img.dim() != 1 or job_model.shape != (J,) or job_pose.shape != (J, 3, 4):
+        raise ValueError("%s: camk (S,4), job_img (J), job_model (J), job_pose (J,3,4) are expected" % who)
+    if J > TSDF_MAX_JOBS:
+        raise ValueError("%s: at most %d jobs" % (who, TSDF_MAX_JOBS))
+    return dev, J
+
+
+def tsdf_raycast(volumes, camk, job_img, job_model, job_pose, window, h, w, *, min_weight=1, step=1.0, near=0.01, job_inv=None):
+    """The surface of TSDF volumes as cameras see it (tgp_tsdf_raycast, csrc/raycast.hip; DESIGN.md section 3 "Ray casting and
+    frame-to-model tracking").  Job j casts h x w rays into volume job_model[j] from the camera of job_pose[j] (3,4) [s R | t] (model
+    -> camera, metres) with the intrinsics camk[job_img[j]]; ray (r, c) goes through the pixel coordinates (u0 + c du, v0 + r dv) of
+    window[j] = (u0, v0, du, dv).  It is marched in steps of ``step`` voxels from where it enters the cube (not before ``near``
+    metres); a sample is the trilinear value of sum / weight over its cell, known when all eight voxels have weight >= min_weight;
+    the first known sample <= 0 ends the ray, as a hit where the sample before it was known and positive.  All tensors on the
+    volumes' GPU: camk (S,4) float32, job_img, job_model (J) int32, job_pose (J,3,4), window (J,4) float32; job_inv (J,3,4) float32:
+    the poses' inverses if the caller has them (default pose_inverse(job_pose)).
+    -> dict: z (J,h,w) float32 camera depth in metres (0: a miss), depth (J,h,w) int16-viewed uint16 millimetres, vertex, normal
+    (J,h,w,3) float32 in the MODEL frame (zeros on a miss), count (J) int32 hits, status (J) int32: 1 for a job whose volume or
+    camera index is out of range (all its rays miss).  Nothing is read back."""
+    dev, J = _raycast_jobs(volumes, camk, job_img, job_model, job_pose, "tsdf_raycast")
+    if not (torch.is_tensor(window) and window.is_cuda and window.dtype == torch.float32 and window.is_contiguous() and window.device == dev
+            and window.shape == (J, 4)):
+        raise ValueError("tsdf_raycast: window must be a contiguous (J,4) float32 tensor on the volumes' device")
+    if job_inv is None:
+        job_inv = pose_inverse(job_pose)
+    elif not (torch.is_tensor(job_inv) and job_inv.dtype == torch.float32 and job_inv.is_contiguous() and job_inv.device == dev
+              and job_inv.shape == (J, 3, 4)):
+        raise ValueError("tsdf_raycast: job_inv must be a contiguous (J,3,4) float32 tensor on the volumes' device")
+    if not (isinstance(h, int) and isinstance(w, int) and 1 <= h <= RAYCAST_MAX_SIDE and 1 <= w <= RAYCAST_MAX_SIDE):
+        raise ValueError("tsdf_raycast: h and w must be ints in [1, %d]" % RAYCAST_MAX_SIDE)
+    if not (isinstance(min_weight, int) and min_weight >= 1):
+        raise ValueError("tsdf_raycast: min_weight must be an int >= 1")
+    if not (0.0625 <= float(step) < math.inf):
+        raise ValueError("tsdf_raycast: step must be a finite number of voxels >= 1/16")
+    if not (0.0 < float(near) < math.inf):
+        raise ValueError("tsdf_raycast: near must be positive and finite")
+    out = {"z": torch.empty(J, h, w, device=dev, dtype=torch.float32), "depth": torch.empty(J, h, w, device=dev, dtype=torch.int16),
+           "vertex": torch.empty(J, h, w, 3, device=dev, dtype=torch.float32), "normal": torch.empty(J, h, w, 3, device=dev, dtype=torch.float32),
+           "count": torch.empty(J, device=dev, dtype=torch.int32), "status": torch.empty(J, device=dev, dtype=torch.int32)}
+    if J == 0:
+        return out
+    a = _lib.TsdfRaycastArgs(sum=_p(volumes.sum), weight=_p(volumes.weight), meta=_p(volumes.meta), M=len(volumes), G=volumes.G, camk=_p(camk),
+                             S=camk.shape[0], job_img=_p(job_img), job_model=_p(job_model), job_inv=_p(job_inv), job_window=_p(window), J=J,
+                             h=h, w=w, min_weight=min_weight, step=float(step), near=float(near), z=_p(out["z"]), depth=_p(out["depth"]),
+                             vertex=_p(out["vertex"]), normal=_p(out["normal"]), count=_p(out["count"]), status=_p(out["status"]))
+    check(_lib.lib().tgp_tsdf_raycast(ctypes.byref(a), _stream(job_pose)), "tgp_tsdf_raycast")
+    return out
+
+
+def tsdf_windows(volumes, camk, job_img, job_model, job_pose, h, w, H, W, pad=1.0):
+    """The ray-cast windows that frame each job's cube: (J,4) float32 (u0, v0, du, dv) on the device, an h x w grid that spans the box
+    of the cube's eight projected corners grown by ``pad`` pixels and clamped to the frame [0, W-1] x [0, H-1] (du = (u1 - u0) / (w
+    - 1); 1 for a single column).  A cube with a corner at or behind the camera (z <= 1e-6), or whose projection is not finite,
+    gets four NaN: every ray of it misses.  Indices out of range are clamped here (tsdf_raycast refuses the job).  Made of torch
+    operations, float32 one operation at a time (tests/raycast_ref.py windows); nothing is read back."""
+    dev, J = _raycast_jobs(volumes, camk, job_img, job_model, job_pose, "tsdf_windows")
+    if not all(isinstance(v, int) and v >= 1 for v in (h, w, H, W)):
+        raise ValueError("tsdf_windows: h, w, H, W must be ints >= 1")
+    meta = volumes.meta[job_model.long().clamp(0, len(volumes) - 1)]                  # (J,4)
+    K = camk[job_img.long().clamp(0, camk.shape[0] - 1)]
+    halfe = (meta[:, 3] * float(volumes.G)) * 0.5
+    k = torch.arange(8, device=dev)
+    signs = torch.stack([k // 4 % 2, k // 2 % 2, k % 2], 1).float() * 2.0 - 1.0              # (8,3) of +-1, made on the device
+    p = meta[:, None, :3] + signs[None] * halfe[:, None, None]                          # (J,8,3): +- halfe is exact
+    T = job_pose
+    c = [((T[:, None, r, 0] * p[:, :, 0] + T[:, None, r, 1] * p[:, :, 1]) + T[:, None, r, 2] * p[:, :, 2]) + T[:, None, r, 3] for r in range(3)]
+    us = K[:, None, 0] * (c[0] / c[2]) + K[:, None, 2]
+    vs = K[:, None, 1] * (c[1] / c[2]) + K[:, None, 3]
+    good = (c[2] > 1e-6).all(1) & torch.isfinite(us).all(1) & torch.isfinite(vs).all(1)
+    u0 = (us.min(1).values - float(pad)).clamp(0.0, float(W - 1))
+    u1 = (us.max(1).values + float(pad)).clamp(0.0, float(W - 1))
+    v0 = (vs.min(1).values - float(pad)).clamp(0.0, float(H - 1))
+    v1 = (vs.max(1).values + float(pad)).clamp(0.0, float(H - 1))
+    du = (u1 - u0) / float(w - 1) if w > 1 else torch.ones_like(u0)
+    dv = (v1 - v0) / float(h - 1) if h > 1 else torch.ones_like(v0)
+    win = torch.stack([u0, v0, du, dv], 1)
+    return torch.where(good[:, None], win, torch.full_like(win, float("nan"))).contiguous()
 
 
 # ------------------------------------------------------------------------------------------------------------ the supporting plane

@@ -204,6 +204,48 @@ def scan_models(volumes, depth, camk, RTs, scales=None, job_img=None, job_model=
     return ops.tsdf_integrate(volumes, depth, camk, job_img, job_model, P, trunc_mm, near=near, mask=mask, job_mask_val=job_mask_val)
 
 
+RAYCAST_FEW_HITS = 4           # RaycastRefine's status beside ops.ICP_STATUS' 1..3: fewer than min_hits rays met the surface
+
+
+class RaycastRefine(object):
+    """Frame-to-model registration against TSDF volumes as they stand (DESIGN.md section 3 "Ray casting and frame-to-model
+    tracking"): the surface each volume shows from its object's current pose is ray-cast (ops.tsdf_windows, ops.tsdf_raycast: h x w
+    rays over the cube's image, h w <= ops.ICP_MAX_POINTS) into an ops.IcpModels (from_raycast), and the pose is registered to the
+    frame's cloud by ONE ops.icp_refine call.  volumes: ops.TsdfVolumes; job_model: one volume index per object (default: object j
+    is volume j); max_dist: the gate in metres; min_weight, step, near: the ray cast's; icp_kw: ops.icp_refine's keywords.
+    __call__(clouds (J,n,3) camera metres, RTs (J,4,4) [s R | t], camk (S,4), job_img (J) int32, H, W: the frame's size)
+    -> (RTs (J,4,4), info (J,4) int32, rmse (J,), hits (J,) int32).  A job with fewer than ``min_hits`` hits keeps the pose it
+    came with and has status RAYCAST_FEW_HITS in info[:, 0].  Three launches and torch's glue; nothing is read back."""
+
+    def __init__(self, volumes, max_dist, h=40, w=48, min_weight=1, step=1.0, near=0.01, min_hits=64, job_model=None, **icp_kw):
+        if not isinstance(volumes, ops.TsdfVolumes):
+            raise TypeError("RaycastRefine: volumes must be an ops.TsdfVolumes")
+        if not (isinstance(h, int) and isinstance(w, int) and h >= 1 and w >= 1 and h * w <= ops.ICP_MAX_POINTS):
+            raise ValueError("RaycastRefine: h x w rays must be at least 1 and at most %d" % ops.ICP_MAX_POINTS)
+        if not (isinstance(min_hits, int) and min_hits >= 0):
+            raise ValueError("RaycastRefine: min_hits must be an int >= 0")
+        if icp_kw.get("return_corr"):
+            raise ValueError("RaycastRefine: return_corr is ops.icp_refine's")
+        dev = volumes.sum.device
+        self.volumes, self.h, self.w, self.min_weight, self.step, self.near, self.min_hits = volumes, h, w, min_weight, step, near, min_hits
+        self.job_model = None if job_model is None else torch.as_tensor(job_model, dtype=torch.int32).to(dev).contiguous()
+        self.max_dist = max_dist.to(dev).float().contiguous() if torch.is_tensor(max_dist) else float(max_dist)
+        self.kw = dict(icp_kw)
+
+    def __call__(self, clouds, RTs, camk, job_img, H, W):
+        J, dev = RTs.shape[0], RTs.device
+        job_model = self.job_model if self.job_model is not None else torch.arange(J, dtype=torch.int32, device=dev)
+        P = verify_job_pose(RTs)
+        win = ops.tsdf_windows(self.volumes, camk, job_img, job_model, P, self.h, self.w, H, W)
+        rc = ops.tsdf_raycast(self.volumes, camk, job_img, job_model, P, win, self.h, self.w, min_weight=self.min_weight, step=self.step,
+                              near=self.near)
+        models = ops.IcpModels.from_raycast(rc)
+        new, info, rmse = refine_poses(models, torch.arange(J, dtype=torch.int32, device=dev), clouds, RTs, self.max_dist, **self.kw)
+        few = rc["count"] < self.min_hits
+        info = torch.cat([torch.where(few, torch.full_like(info[:, 0], RAYCAST_FEW_HITS), info[:, 0])[:, None], info[:, 1:]], 1)
+        return torch.where(few[:, None, None], RTs, new), info, rmse, rc["count"]
+
+
 def cloud_anchors(clouds, counts=None):
     """The mean of each cloud's finite rows (of the first counts[j] rows): float64 sums on the device, rounded once -> (J,3) float32;
     a cloud without a finite row gives 0."""
