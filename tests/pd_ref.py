@@ -8,7 +8,9 @@ section 3, "Ground-truth persistence images"); parity with gudhi and persim them
 - the alpha filtration on scipy's Delaunay triangulation: a simplex is Gabriel when no vertex of a Delaunay coface lies strictly
   inside its smallest circumsphere; a Gabriel simplex takes its squared smallest-circumsphere radius, any other simplex the minimum
   value over its cofaces, a vertex 0.  Every value is then also capped by its cofaces' values (a no-op in exact arithmetic; it keeps
-  faces before cofaces when two rounded radii of the same sphere differ in the last bit);
+  faces before cofaces when two rounded radii of the same sphere differ in the last bit).  Spheres are evaluated from the
+  simplex's shortest edge (``_near_order``), so a value does not depend on the row order of the cloud; the arithmetic stays plain
+  float64 (tests/pd_exact.py is the exact referee);
 - persistence over Z/2 by a plain boundary-matrix reduction in (value, dimension, index) order, pairs with death > birth, no
   infinite deaths;
 - the image as persim's legacy PersImage(spread=1e-2, pixels=[50, 50]) with one object for both dimensions.
@@ -19,6 +21,8 @@ from scipy.stats import norm
 
 PIXELS = 50
 SPREAD = 1e-2
+# the tests' tolerances on the kernel against this restatement: a pair's birth and death (relative), an image pixel (absolute)
+PAIR_RTOL, IMG_ATOL = 1e-9, 1e-6
 
 
 def unique_points(pcl):
@@ -38,9 +42,23 @@ def delaunay_tets(P):
     return T[vol != 0]
 
 
+def _near_order(A):
+    """rows of A reordered: an endpoint of the shortest edge first (the base of the differences), the edge's other endpoint,
+    then the rest by distance from the base.  Based at a far vertex the cross products of two nearly equal long differences
+    cancel, and the centre of a simplex with two close vertices and a distant one loses the digits the Gabriel tests need."""
+    n = len(A)
+    d = ((A[:, None, :] - A[None, :, :]) ** 2).sum(-1)
+    i, j = min(((i, j) for i in range(n) for j in range(i + 1, n)), key=lambda ij: d[ij])
+    rest = sorted((k for k in range(n) if k not in (i, j)), key=lambda k: d[i, k])
+    return A[[i, j] + rest]
+
+
 def _sphere(P, s):
-    """smallest circumsphere (centre, squared radius) of the simplex s (2, 3 or 4 vertex indices)"""
+    """smallest circumsphere (centre, squared radius) of the simplex s (2, 3 or 4 vertex indices); the value does not depend on
+    the order of s beyond rounding"""
     A = P[list(s)]
+    if len(s) > 2:
+        A = _near_order(A)
     if len(s) == 2:
         c = (A[0] + A[1]) * 0.5
         d = A[0] - A[1]

@@ -8,11 +8,11 @@ import torch
 from scipy.spatial import ConvexHull
 
 from tests import pd_ref
+from tests.pd_ref import IMG_ATOL, PAIR_RTOL          # 1e-9 relative on a pair, 1e-6 absolute on an image
 from tests.util import golden
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-PAIR_RTOL, IMG_ATOL = 1e-9, 1e-6
 # pairs whose persistence is at the rounding level of the squared radii (~1e-3) are not compared: two float64 evaluations of the
 # same sphere may differ in the last bit and so create or remove a zero-length pair
 PERS_MIN = 1e-12

@@ -7,7 +7,18 @@
 //   pd_image_kernel    one workgroup per (cloud, dimension): the 50 x 50 image from the pairs, normalised to max 1
 //
 // The per-cloud algorithm (pd_run) is written for `nt` cooperating lanes: strided loops, lane-0 sections, PD_SYNC() between
-// them.  Run with nt = 1 on the host it is the same computation serially (PD_SYNC() is then nothing).
+// them.  With nt = 1 on the host it is the same computation serially (PD_SYNC() is then nothing): tests/host/pd_host.cpp
+// builds exactly that as a stand-alone program.  tests/test_pd_exact_cpu.py runs it, also under the address and undefined-
+// behaviour sanitizers, and checks its triangulations and diagrams with exact integer and rational arithmetic;
+// tests/test_pd_exact_gpu.py finds the kernel's status, tetrahedra and pair bits equal to that program's on every test cloud.
+//
+// Values.  A simplex's filtration value is the squared radius of its smallest circumsphere, evaluated in double-double
+// arithmetic (~2^-100) from the simplex's shortest edge and rounded once to float64, and the Gabriel tests compare
+// double-doubles.  The evaluation is accurate to ~2^-100, not exact: a value depends on the order of the simplex's vertices
+// far below float64's rounding, and two simplices with the same sphere get the same float64 unless the true value lies that
+// close to a rounding boundary.  So a pair of zero length in exact arithmetic is almost never reported (none is on the test
+// clouds), but that is not guaranteed; nor is the direction in which a true length below half an ulp rounds.  Against the exact rational diagram the pairs agree within 1e-9 of the diagram's
+// largest death, also for clusters 2^-32 wide beside coordinates of 0.5.
 //
 // Exactness.  Coordinates are float32; promoted to float64 they are integers on the grid 2^G, G = (top exponent of the cloud) - 60,
 // unless a coordinate is below ~1e-11 of the cloud's extent (then the status is TGP_PD_ERANGE).  orient3d / insphere first run
@@ -529,49 +540,161 @@ PD_HD inline int insert(Cloud &c, const Pts &s, int p, int start, int stamp, int
     return first_fin;
 }
 
-// circumcentre offsets (float64); the squared radius is |offset|^2
-PD_HD inline double tet_r2(const double *A, const double *B, const double *C, const double *D, double *ctr)
+// The order in which tet_r2 / tri_r2 take a simplex's n = 3 or 4 vertices: an endpoint of the shortest edge is the base of the
+// differences, the edge's other endpoint comes next, the rest follow by distance from the base.  With a far vertex as the base
+// the products u x v of two nearly equal long differences cancel, and the circumcentre of a simplex with two close vertices
+// and a distant one loses the digits that the Gabriel tests need; based at the short edge the short difference enters exactly.
+PD_HD inline void near_order(const double *const *V, int n, int *o)
 {
-    const double u[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
-    const double v[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]};
-    const double w[3] = {D[0] - A[0], D[1] - A[1], D[2] - A[2]};
-    const double vw[3] = {v[1] * w[2] - v[2] * w[1], v[2] * w[0] - v[0] * w[2], v[0] * w[1] - v[1] * w[0]};
-    const double wu[3] = {w[1] * u[2] - w[2] * u[1], w[2] * u[0] - w[0] * u[2], w[0] * u[1] - w[1] * u[0]};
-    const double uv[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-    const double uu = u[0] * u[0] + u[1] * u[1] + u[2] * u[2], vv = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-    const double ww = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    const double den = 2.0 * (u[0] * vw[0] + u[1] * vw[1] + u[2] * vw[2]);
-    double r2 = 0.0;
+    double best = INFINITY;
+    o[0] = 0;
+    o[1] = 1;
+    for (int i = 0; i < n; ++i)
+        for (int j = i + 1; j < n; ++j) {
+            const double x = V[i][0] - V[j][0], y = V[i][1] - V[j][1], z = V[i][2] - V[j][2];
+            const double d = x * x + y * y + z * z;
+            if (d < best) {
+                best = d;
+                o[0] = i;
+                o[1] = j;
+            }
+        }
+    int m = 2;
+    for (int k = 0; k < n; ++k)
+        if (k != o[0] && k != o[1]) o[m++] = k;
+    if (n == 4) {
+        const double *A = V[o[0]], *P = V[o[2]], *Q = V[o[3]];
+        const double px = P[0] - A[0], py = P[1] - A[1], pz = P[2] - A[2], qx = Q[0] - A[0], qy = Q[1] - A[1], qz = Q[2] - A[2];
+        if (qx * qx + qy * qy + qz * qz < px * px + py * py + pz * pz) {
+            const int t = o[2];
+            o[2] = o[3];
+            o[3] = t;
+        }
+    }
+}
+
+// Double-double arithmetic (an unevaluated sum h + l of two float64, ~106 bits) for the filtration values.  Many simplices
+// share one sphere (a right triangle and its hypotenuse, the tetrahedra of a cospherical group), and a plain float64 evaluation
+// from different vertices gives values an ulp or two apart: a pair of that length where there is none.  Evaluated to ~2^-100 and
+// rounded once, two expressions of one number give the same float64 unless it lies that close to a rounding boundary.
+// fma() is written out; the library is compiled with -ffp-contract=off, which the error-free sums need.
+struct DD {
+    double h, l;
+};
+PD_HD inline DD dd_fast(double a, double b)          // |a| >= |b| or a == 0
+{
+    const double s = a + b;
+    return {s, b - (s - a)};
+}
+PD_HD inline DD dd_sum(double a, double b)           // exact a + b
+{
+    const double s = a + b, bb = s - a;
+    return {s, (a - (s - bb)) + (b - bb)};
+}
+PD_HD inline DD dd_prod(double a, double b)          // exact a * b
+{
+    const double p = a * b;
+    return {p, fma(a, b, -p)};
+}
+PD_HD inline DD dd_add(DD a, DD b)
+{
+    DD s = dd_sum(a.h, b.h);
+    const DD t = dd_sum(a.l, b.l);
+    s = dd_sum(s.h, s.l + t.h);              // after a cancellation the low parts may outweigh s.h
+    return dd_fast(s.h, s.l + t.l);
+}
+PD_HD inline DD dd_sub(DD a, DD b) { return dd_add(a, DD{-b.h, -b.l}); }
+PD_HD inline DD dd_mul(DD a, DD b)
+{
+    const DD p = dd_prod(a.h, b.h);
+    return dd_fast(p.h, p.l + (a.h * b.l + a.l * b.h));
+}
+PD_HD inline DD dd_scale(DD a, double p2) { return {a.h * p2, a.l * p2}; }       // p2 a power of two
+PD_HD inline DD dd_div(DD a, DD b)
+{
+    const double q1 = a.h / b.h;
+    DD r = dd_sub(a, dd_mul(b, DD{q1, 0.0}));
+    const double q2 = r.h / b.h;
+    r = dd_sub(r, dd_mul(b, DD{q2, 0.0}));
+    const double q3 = r.h / b.h;
+    return dd_add(dd_fast(q1, q2), DD{q3, 0.0});
+}
+PD_HD inline bool dd_less(DD a, DD b) { return a.h < b.h || (a.h == b.h && a.l < b.l); }
+PD_HD inline void dd_diff3(const double *B, const double *A, DD *u)
+{
+    for (int k = 0; k < 3; ++k) u[k] = dd_sum(B[k], -A[k]);
+}
+PD_HD inline void dd_cross(const DD *a, const DD *b, DD *c)
+{
+    c[0] = dd_sub(dd_mul(a[1], b[2]), dd_mul(a[2], b[1]));
+    c[1] = dd_sub(dd_mul(a[2], b[0]), dd_mul(a[0], b[2]));
+    c[2] = dd_sub(dd_mul(a[0], b[1]), dd_mul(a[1], b[0]));
+}
+PD_HD inline DD dd_dot(const DD *a, const DD *b)
+{
+    return dd_add(dd_add(dd_mul(a[0], b[0]), dd_mul(a[1], b[1])), dd_mul(a[2], b[2]));
+}
+
+// the squared circumradius and (ctr != NULL) the circumcentre from the offsets o = N / den of the base vertex A
+PD_HD inline DD dd_centre(const double *A, const DD *N, DD den, DD *ctr)
+{
+    DD r2 = {0.0, 0.0};
     for (int k = 0; k < 3; ++k) {
-        const double o = (uu * vw[k] + vv * wu[k] + ww * uv[k]) / den;
-        if (ctr) ctr[k] = A[k] + o;
-        r2 += o * o;
+        const DD o = dd_div(N[k], den);
+        if (ctr) ctr[k] = dd_add(DD{A[k], 0.0}, o);
+        r2 = dd_add(r2, dd_mul(o, o));
     }
     return r2;
 }
 
-PD_HD inline double tri_r2(const double *A, const double *B, const double *C, double *ctr)
+// Smallest circumspheres.  The vertices are taken in near_order; the squared radius comes back as a double-double (its .h is
+// the value, rounded once) and the centre as three, for the Gabriel tests.
+PD_HD inline DD tet_r2(const double *A, const double *B, const double *C, const double *D, DD *ctr)
 {
-    const double u[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
-    const double v[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]};
-    const double w[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-    const double vw[3] = {v[1] * w[2] - v[2] * w[1], v[2] * w[0] - v[0] * w[2], v[0] * w[1] - v[1] * w[0]};
-    const double wu[3] = {w[1] * u[2] - w[2] * u[1], w[2] * u[0] - w[0] * u[2], w[0] * u[1] - w[1] * u[0]};
-    const double uu = u[0] * u[0] + u[1] * u[1] + u[2] * u[2], vv = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-    const double den = 2.0 * (w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-    double r2 = 0.0;
-    for (int k = 0; k < 3; ++k) {
-        const double o = (uu * vw[k] + vv * wu[k]) / den;
-        ctr[k] = A[k] + o;
-        r2 += o * o;
-    }
-    return r2;
+    const double *const V[4] = {A, B, C, D};
+    int o[4];
+    near_order(V, 4, o);
+    DD u[3], v[3], w[3], vw[3], wu[3], uv[3], N[3];
+    dd_diff3(V[o[1]], V[o[0]], u);
+    dd_diff3(V[o[2]], V[o[0]], v);
+    dd_diff3(V[o[3]], V[o[0]], w);
+    dd_cross(v, w, vw);
+    dd_cross(w, u, wu);
+    dd_cross(u, v, uv);
+    const DD uu = dd_dot(u, u), vv = dd_dot(v, v), ww = dd_dot(w, w);
+    for (int k = 0; k < 3; ++k) N[k] = dd_add(dd_add(dd_mul(uu, vw[k]), dd_mul(vv, wu[k])), dd_mul(ww, uv[k]));
+    return dd_centre(V[o[0]], N, dd_scale(dd_dot(u, vw), 2.0), ctr);
 }
 
-PD_HD inline double dist2(const double *A, const double *B)
+PD_HD inline DD tri_r2(const double *A, const double *B, const double *C, DD *ctr)
 {
-    const double x = A[0] - B[0], y = A[1] - B[1], z = A[2] - B[2];
-    return x * x + y * y + z * z;
+    const double *const V[3] = {A, B, C};
+    int o[4];
+    near_order(V, 3, o);
+    DD u[3], v[3], w[3], vw[3], wu[3], N[3];
+    dd_diff3(V[o[1]], V[o[0]], u);
+    dd_diff3(V[o[2]], V[o[0]], v);
+    dd_cross(u, v, w);
+    dd_cross(v, w, vw);
+    dd_cross(w, u, wu);
+    const DD uu = dd_dot(u, u), vv = dd_dot(v, v);
+    for (int k = 0; k < 3; ++k) N[k] = dd_add(dd_mul(uu, vw[k]), dd_mul(vv, wu[k]));
+    return dd_centre(V[o[0]], N, dd_scale(dd_dot(w, w), 2.0), ctr);
+}
+
+PD_HD inline DD edge_r2(const double *A, const double *B, DD *ctr)
+{
+    DD d[3];
+    dd_diff3(A, B, d);
+    for (int k = 0; k < 3; ++k) ctr[k] = dd_scale(dd_sum(A[k], B[k]), 0.5);
+    return dd_scale(dd_dot(d, d), 0.25);
+}
+
+PD_HD inline DD dist2(const double *A, const DD *ctr)
+{
+    DD d[3];
+    for (int k = 0; k < 3; ++k) d[k] = dd_sub(DD{A[k], 0.0}, ctr[k]);
+    return dd_dot(d, d);
 }
 
 PD_HD inline uint64_t dkey(double v)
@@ -702,11 +825,16 @@ PD_HD inline void pd_run(Cloud &c, int tid, int nt)
         c.cnt[0] = c.cnt[1] = 0;
         if (c.ntet_out) *c.ntet_out = 0;
         float m = 0.f;
-        for (int i = 0; i < 3 * n; ++i) m = fmaxf(m, fabsf(c.pc[i]));
+        bool finite = true;                            // fmaxf drops a NaN, so each coordinate is looked at on its own: a cloud
+        for (int i = 0; i < 3 * n; ++i) {              // with one stops here, before any float -> int conversion sees it
+            const float a = fabsf(c.pc[i]);
+            finite = finite && a < INFINITY;
+            m = fmaxf(m, a);
+        }
         int e = 0;
         frexp((double)m, &e);
         c.sc[5] = e - 60;
-        if (!(m < INFINITY)) fail(c, TGP_PD_ERANGE);
+        if (!finite) fail(c, TGP_PD_ERANGE);
     }
     PD_SYNC();
     if (*c.status) return;
@@ -721,8 +849,8 @@ PD_HD inline void pd_run(Cloud &c, int tid, int nt)
         uint64_t code = 0;
         for (int k = 0; k < 3; ++k) {
             const float ext = hi[k] - lo[k];
-            int q = ext > 0.f ? (int)((c.pc[3 * i + k] - lo[k]) / ext * 1023.f) : 0;
-            q = q < 0 ? 0 : (q > 1023 ? 1023 : q);
+            const float f = ext > 0.f ? (c.pc[3 * i + k] - lo[k]) / ext * 1023.f : 0.f;
+            const int q = f >= 0.f ? (f < 1023.f ? (int)f : 1023) : 0;      // an extent beyond float32 gives inf / inf: cell 0
             code |= spread3((uint32_t)q) << k;
         }
         c.key[i] = (code << 32) | (uint64_t)i;
@@ -842,13 +970,13 @@ PD_HD inline void pd_run(Cloud &c, int tid, int nt)
     for (int t = tid; t < nslots; t += nt)
         if (c.fin[t] >= 0) {
             const int *v = c.tv + 4 * t;
-            c.tval[t] = tet_r2(c.P + 3 * v[0], c.P + 3 * v[1], c.P + 3 * v[2], c.P + 3 * v[3], nullptr);
+            c.tval[t] = tet_r2(c.P + 3 * v[0], c.P + 3 * v[1], c.P + 3 * v[2], c.P + 3 * v[3], nullptr).h;
         }
     PD_SYNC();
     for (int f = tid; f < F; f += nt) {
         const int *v = c.tri + 3 * f;
-        double ctr[3];
-        const double r2 = tri_r2(c.P + 3 * v[0], c.P + 3 * v[1], c.P + 3 * v[2], ctr);
+        DD ctr[3];
+        const DD r2 = tri_r2(c.P + 3 * v[0], c.P + 3 * v[1], c.P + 3 * v[2], ctr);
         double val = INFINITY;
         bool gab = true;
         for (int side = 0; side < 2; ++side) {
@@ -856,10 +984,10 @@ PD_HD inline void pd_run(Cloud &c, int tid, int nt)
             if (t < 0) continue;
             const int *u = c.tv + 4 * t;
             for (int m = 0; m < 4; ++m)
-                if (u[m] != v[0] && u[m] != v[1] && u[m] != v[2] && dist2(c.P + 3 * u[m], ctr) < r2) gab = false;
+                if (u[m] != v[0] && u[m] != v[1] && u[m] != v[2] && dd_less(dist2(c.P + 3 * u[m], ctr), r2)) gab = false;
             val = fmin(val, c.tval[t]);
         }
-        c.fval[f] = gab ? fmin(r2, val) : val;
+        c.fval[f] = gab ? fmin(r2.h, val) : val;
     }
     PD_SYNC();
     // ---- 4: edges, each numbered by the lowest finite tetrahedron around it (lane 0) ----------------------------------------
@@ -896,18 +1024,16 @@ PD_HD inline void pd_run(Cloud &c, int tid, int nt)
     const int E = c.sc[4];
     for (int e = tid; e < E; e += nt) {
         const int a = c.edge[2 * e], b = c.edge[2 * e + 1];
-        const double *A = c.P + 3 * a, *B = c.P + 3 * b;
-        const double ctr[3] = {(A[0] + B[0]) * 0.5, (A[1] + B[1]) * 0.5, (A[2] + B[2]) * 0.5};
-        const double d0 = A[0] - B[0], d1 = A[1] - B[1], d2 = A[2] - B[2];
-        const double r2 = (d0 * d0 + d1 * d1 + d2 * d2) * 0.25;
+        DD ctr[3];
+        const DD r2 = edge_r2(c.P + 3 * a, c.P + 3 * b, ctr);
         double val = INFINITY;
         bool gab = true;
         ring(c, c.epos[e], a, b, [&](int cur, int px, int y) {
             if (y == INF_V) return;
-            if (dist2(c.P + 3 * y, ctr) < r2) gab = false;
+            if (dd_less(dist2(c.P + 3 * y, ctr), r2)) gab = false;
             val = fmin(val, c.fval[face_tri(c, cur, px)]);
         });
-        c.eval[e] = gab ? fmin(r2, val) : val;
+        c.eval[e] = gab ? fmin(r2.h, val) : val;
     }
     PD_SYNC();
     // ---- 5: H0 (Kruskal over the edges in order; negative edges leave the H1 rows) ------------------------------------------
