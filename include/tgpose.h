@@ -1785,6 +1785,96 @@ typedef struct tgp_tsdf_raycast_args {
 } tgp_tsdf_raycast_args;
 int tgp_tsdf_raycast(const tgp_tsdf_raycast_args *args, tgp_stream_t stream);
 
+/* ---- Indexed meshes from volumes: welding and vertex normals (csrc/weld.hip; additive, ABI stays 8) ---------------------------------
+ * DESIGN.md section 3 "Indexed meshes from volumes" is the contract; tests/weld_ref.py restates every kernel in NumPy, bit for bit.
+ * The volumes, the cubes that mesh, the tetrahedra and the triangles' order are tgp_tsdf_mesh_count / _emit's above.
+ *
+ * A vertex is named by the voxel edge it cuts: key = flat(A) 8 + d, A the edge's componentwise smaller end (the end earlier in the
+ * Kuhn path), flat(A) = (ix G + iy) G + iz, d = dx << 2 | dy << 1 | dz in 1..7 the step to the other end B = A + d (the 19 edges of
+ * a cube are its axis edges, face diagonals and body diagonal).  The vertex (A, d) EXISTS iff (sum[A] < 0) != (sum[B] < 0) and at
+ * least one cube that holds both ends meshes (all eight corners with weight >= min_weight, origin < G - 1 on every axis): the cubes
+ * whose origin equals A on the axes where d steps and is A or A - 1 on the others.  Its position is tgp_tsdf_mesh_emit's, from A to
+ * B: f_a = (float)sum_A / (float)weight_A, t = f_a / (f_a - f_b), p = p_A + t (p_B - p_A) per axis.  Vertices are numbered in
+ * ascending key.  A corner whose sum is 0 is outside and gives t = 0 on each of its cut edges: those vertices have equal positions
+ * and different names, and stay distinct vertices.
+ *   mark : mask (G^3) uint8, bit d of mask[A] set iff (A, d) exists; vcounts (G^3) int32 = popcount(mask).  The host makes voffsets
+ *          (G^3) int64 = the inclusive prefix sum of vcounts; index(A, d) = voffsets[A] - popcount(mask[A]) + popcount(mask[A] &
+ *          ((1 << d) - 1)).
+ *   count: fcounts (G^3) int32 = the cube's triangles whose three indices are all < vert_cap (0 where there is no cube).  The host
+ *          makes foffsets (G^3) int64 = the inclusive prefix sum of fcounts.
+ *   verts: vertex n goes to verts[3 n .. 3 n + 2] if n < vert_cap.
+ *   faces: the counted triangles in tgp_tsdf_mesh_emit's order -- cube flat index, tetrahedron, triangle, the same winding --
+ *          triangle n to faces[3 n .. 3 n + 2] (int32 indices, local to the mesh) if n < face_cap.  info (3) int64 = {min(vertices,
+ *          vert_cap), min(counted triangles, face_cap), status}; status bit 1: counted triangles were dropped by face_cap, bit 2:
+ *          vertices lie beyond vert_cap (a triangle that names one of them is not counted).
+ * With vert_cap >= the vertices and face_cap >= the triangles, verts[faces] is tgp_tsdf_mesh_emit's soup byte for byte.  Rows at
+ * and beyond the counts are not written.  One kernel each on the caller's stream; nothing read by the host.
+ * TGP_EINVAL: a NULL pointer that the stage reads or writes (verts / faces may be NULL when their cap is 0), M < 1, model outside
+ * [0, M), min_weight < 1, a cap < 0.  TGP_EUNSUPPORTED: G as above, vert_cap > TGP_WELD_MAX_VERTS, face_cap > TGP_TSDF_MAX_FACES.
+ *
+ * tgp_weld_cluster: decimation by voxel clusters, the device's share.  A vertex (A, d) belongs to the cell A / c per axis (integer
+ * division) of a grid of side ceil(G / c), cell (cx, cy, cz) at (cx side + cy) side + cz; c = cluster in {2, 4, 8}.  Per vertex n <
+ * vert_cap of tgp_tsdf_weld_verts' rows: vcell[n] = its cell, and per axis o = llrint(((double)p - (double)c0) (65536.0 /
+ * (double)voxel)), c0 the float32 centre of voxel 0 on that axis, is added to cell_sums (side^3, 3) int64 and 1 to cell_counts (side^3)
+ * int32, by integer atomics on words the call zeroes first.  The host numbers the occupied cells in ascending flat index and makes the
+ * representative of a cell, float64 rounded to float32 once:  (float)((double)c0 + (((double)sum / (double)count) (double)voxel) /
+ * 65536.0).  Two memsets and one kernel on the caller's stream; nothing read by the host.
+ * TGP_EINVAL: a NULL pointer, M < 1, model outside [0, M), vert_cap < 0.  TGP_EUNSUPPORTED: G as above, cluster not 2, 4 or 8,
+ * vert_cap > TGP_WELD_MAX_VERTS.
+ *
+ * tgp_mesh_vertex_normals: area-weighted vertex normals of a packed mesh set (tgp_render_depth's: verts (V,3) float32, faces (F,3)
+ * int32 local to their mesh, vptr / fptr (M+1) int32).  Per face of mesh m, float32, each operation rounded on its own:
+ *    u = p1 - p0, w = p2 - p0;  c = (u_y w_z - u_z w_y,  u_z w_x - u_x w_z,  u_x w_y - u_y w_x)
+ *    q_k = llrint((double)c_k scale[m]) (ties to even; 0 unless |(double)c_k scale[m]| < 4e15)
+ * and q is added to the three int64 sums of each of the face's three vertices by integer atomics (the sums are the same in any
+ * order).  A face with an index outside its mesh adds nothing.  Then per vertex, float64: (0, 0, 0) if its three sums are zero, else
+ * n = s / sqrt((s_x s_x + s_y s_y) + s_z s_z), correctly rounded square root and divisions, each component rounded to float32 once.
+ * sums (V,3) int64 is workspace, zeroed by the call.  One memset and two kernels on the caller's stream; nothing read by the host.
+ * TGP_EINVAL: a NULL required pointer, M < 1, V or F < 0.  TGP_EUNSUPPORTED: V > TGP_WELD_MAX_VERTS, F > TGP_TSDF_MAX_FACES. */
+#define TGP_WELD_MAX_VERTS 300000000
+typedef struct tgp_tsdf_weld_args {
+    const int32_t *sum, *weight;
+    const float *meta;
+    int M, G, model, min_weight;
+    uint8_t *mask;                  /* mark writes; count, verts and faces read */
+    int32_t *vcounts;               /* mark only */
+    const int64_t *voffsets;        /* count, verts, faces */
+    int32_t *fcounts;               /* count writes; faces reads */
+    const int64_t *foffsets;        /* faces only */
+    int64_t vert_cap;               /* count, verts, faces */
+    int64_t face_cap;               /* faces only */
+    float *verts;                   /* verts only */
+    int32_t *faces;                 /* faces only */
+    int64_t *info;                  /* faces only */
+} tgp_tsdf_weld_args;
+int tgp_tsdf_weld_mark(const tgp_tsdf_weld_args *args, tgp_stream_t stream);
+int tgp_tsdf_weld_count(const tgp_tsdf_weld_args *args, tgp_stream_t stream);
+int tgp_tsdf_weld_verts(const tgp_tsdf_weld_args *args, tgp_stream_t stream);
+int tgp_tsdf_weld_faces(const tgp_tsdf_weld_args *args, tgp_stream_t stream);
+typedef struct tgp_weld_cluster_args {
+    const uint8_t *mask;
+    const int64_t *voffsets;
+    const float *verts;
+    const float *meta;
+    int M, G, model, cluster;
+    int64_t vert_cap;
+    int32_t *vcell;                 /* (vert_cap) */
+    int64_t *cell_sums;             /* (side^3, 3) */
+    int32_t *cell_counts;           /* (side^3) */
+} tgp_weld_cluster_args;
+int tgp_weld_cluster(const tgp_weld_cluster_args *args, tgp_stream_t stream);
+typedef struct tgp_mesh_normals_args {
+    const float *verts;
+    const int32_t *faces;
+    const int32_t *vptr, *fptr;
+    int M;
+    int64_t V, F;
+    const double *scale;            /* (M) */
+    int64_t *sums;                  /* (V,3) workspace */
+    float *normals;                 /* (V,3) */
+} tgp_mesh_normals_args;
+int tgp_mesh_vertex_normals(const tgp_mesh_normals_args *args, tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,12 +13,14 @@
 // Integer sums and fixed places: two calls give identical bytes.
 #include "tgp_common.h"
 
-#define TSDF_THREADS 256
+// the cube corner (dx << 2 | dy << 1 | dz) of path corner c of tetrahedron k: the axis steps of the k-th permutation of (0, 1, 2)
+__device__ static const uint8_t tsdf_path[6][4] = {{0, 4, 6, 7}, {0, 4, 5, 7}, {0, 2, 6, 7}, {0, 2, 3, 7}, {0, 1, 5, 7}, {0, 1, 3, 7}};
+// bit `case` of word k: the triangles swap their second and third vertex (derived by tests/tsdf_ref.py derive_flip; the word of an
+// odd permutation is the complement of an even one's over the cases 1..14)
+__device__ static const uint16_t tsdf_flip[6] = {0x4d24, 0x32da, 0x32da, 0x4d24, 0x4d24, 0x32da};
+#include "tsdf_cells.h"
 
-__device__ __forceinline__ float tsdf_centre(float c, int i, int G, float voxel)
-{
-    return c + (((float)i + 0.5f) - (float)(G / 2)) * voxel;
-}
+#define TSDF_THREADS 256
 
 __global__ __launch_bounds__(TSDF_THREADS) void tsdf_integrate_kernel(const tgp_tsdf_integrate_args a, int bricks)
 {
@@ -108,47 +110,7 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_integrate_kernel(const tgp_
 }
 
 // ---- marching tetrahedra ---------------------------------------------------------------------------------------------------------
-// the cube corner (dx << 2 | dy << 1 | dz) of path corner c of tetrahedron k: the axis steps of the k-th permutation of (0, 1, 2)
-__device__ static const uint8_t tsdf_path[6][4] = {{0, 4, 6, 7}, {0, 4, 5, 7}, {0, 2, 6, 7}, {0, 2, 3, 7}, {0, 1, 5, 7}, {0, 1, 3, 7}};
-// bit `case` of word k: the triangles swap their second and third vertex (derived by tests/tsdf_ref.py derive_flip; the word of an
-// odd permutation is the complement of an even one's over the cases 1..14)
-__device__ static const uint16_t tsdf_flip[6] = {0x4d24, 0x32da, 0x32da, 0x4d24, 0x4d24, 0x32da};
-
-struct TsdfCube {
-    int s[8], w[8];
-};
-
-// the cube at voxel v of the volume: false where there is none (a last row, or a corner below min_weight)
-__device__ __forceinline__ bool tsdf_cube(const tgp_tsdf_mesh_args &a, int ix, int iy, int iz, TsdfCube &c)
-{
-    const int G = a.G;
-    if (ix >= G - 1 || iy >= G - 1 || iz >= G - 1) return false;
-    const size_t base = (size_t)a.model * G * G * G;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const size_t o = base + ((size_t)(ix + (k >> 2)) * G + (iy + ((k >> 1) & 1))) * G + (iz + (k & 1));
-        c.w[k] = a.weight[o];
-        c.s[k] = a.sum[o];
-        ok = ok && c.w[k] >= a.min_weight;
-    }
-    return ok;
-}
-
-__device__ __forceinline__ int tsdf_case(const TsdfCube &c, int k)
-{
-    int cs = 0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) cs |= (c.s[tsdf_path[k][p]] < 0 ? 1 : 0) << p;
-    return cs;
-}
-
-__device__ __forceinline__ int tsdf_case_faces(int cs)
-{
-    const int n = __popc(cs);
-    return n == 2 ? 2 : (n == 1 || n == 3) ? 1 : 0;
-}
-
+// the cubes, the cases and the vertex arithmetic are tsdf_cells.h's, shared with weld.hip
 __global__ __launch_bounds__(TSDF_THREADS) void tsdf_count_kernel(const tgp_tsdf_mesh_args a)
 {
     const int G = a.G;
@@ -183,53 +145,22 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_emit_kernel(const tgp_tsdf_
     TsdfCube c;
     if (!tsdf_cube(a, ix, iy, iz, c)) return; // not with counts[v] > 0
     const float *meta = a.meta + (size_t)a.model * 4;
-    const float voxel = meta[3];
     for (int k = 0; k < 6; ++k) {
         const int cs = tsdf_case(c, k);
         const int faces = tsdf_case_faces(cs);
         if (faces == 0) continue;
-        // the path corners, inside ones first, each kind in path order
-        int in[4], out[4], ni = 0, no = 0;
-        for (int p = 0; p < 4; ++p) {
-            if (cs >> p & 1)
-                in[ni++] = p;
-            else
-                out[no++] = p;
-        }
         int ea[4], eb[4]; // the cut edges (path corners) in the order the contract lists them
-        if (ni == 1) {
-            for (int e = 0; e < 3; ++e) ea[e] = in[0], eb[e] = out[e];
-        } else if (ni == 3) {
-            for (int e = 0; e < 3; ++e) ea[e] = in[e], eb[e] = out[0];
-        } else {
-            ea[0] = in[0], eb[0] = out[0];
-            ea[1] = in[0], eb[1] = out[1];
-            ea[2] = in[1], eb[2] = out[1];
-            ea[3] = in[1], eb[3] = out[0];
-        }
+        tsdf_case_edges(cs, ea, eb);
         const bool flip = tsdf_flip[k] >> cs & 1;
         for (int t = 0; t < faces; ++t, ++n) {
             if (n >= a.face_cap) return;
-            int e3[3] = {0, t + 1, t + 2}; // (0,1,2), then (0,2,3)
-            if (flip) {
-                const int tmp = e3[1];
-                e3[1] = e3[2], e3[2] = tmp;
-            }
             float *dst = a.verts + (size_t)n * 9;
             for (int q = 0; q < 3; ++q) {
-                const int p0 = ea[e3[q]], p1 = eb[e3[q]];
+                const int e = tsdf_face_edge(t, q, flip);
+                const int p0 = ea[e], p1 = eb[e];
                 const int ka = tsdf_path[k][p0 < p1 ? p0 : p1], kb = tsdf_path[k][p0 < p1 ? p1 : p0]; // from the end earlier in the path
-                const float fa = (float)c.s[ka] / (float)c.w[ka], fb = (float)c.s[kb] / (float)c.w[kb];
-                const float tt = fa / (fa - fb);
-                const int ax = ix + (ka >> 2), ay = iy + ((ka >> 1) & 1), az = iz + (ka & 1);
-                const int bx = ix + (kb >> 2), by = iy + ((kb >> 1) & 1), bz = iz + (kb & 1);
-                const float pax = tsdf_centre(meta[0], ax, G, voxel), pay = tsdf_centre(meta[1], ay, G, voxel),
-                            paz = tsdf_centre(meta[2], az, G, voxel);
-                const float pbx = tsdf_centre(meta[0], bx, G, voxel), pby = tsdf_centre(meta[1], by, G, voxel),
-                            pbz = tsdf_centre(meta[2], bz, G, voxel);
-                dst[q * 3 + 0] = pax + tt * (pbx - pax);
-                dst[q * 3 + 1] = pay + tt * (pby - pay);
-                dst[q * 3 + 2] = paz + tt * (pbz - paz);
+                tsdf_edge_vertex(meta, G, c.s[ka], c.w[ka], c.s[kb], c.w[kb], ix + (ka >> 2), iy + ((ka >> 1) & 1), iz + (ka & 1),
+                                 ix + (kb >> 2), iy + ((kb >> 1) & 1), iz + (kb & 1), dst + q * 3);
             }
         }
     }

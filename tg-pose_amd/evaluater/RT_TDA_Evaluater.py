@@ -453,7 +453,7 @@ class myEvaluater:
         return results
 
     def scan(self, sequence, tracked, camK=lde.REAL_INTRINSICS, volumes=None, G=64, trunc_mm=None, support=None, use_mask=True,
-             inst_ids=None, min_weight=1, near=0.01):
+             inst_ids=None, min_weight=1, near=0.01, indexed=False, cluster=1):
         """Build a mesh model of every tracked object from the depth sequence it was tracked through (DESIGN.md section 3 "Models
         from depth sequences"): TSDF fusion of all frames x objects in ONE ops.tsdf_integrate call, then marching tetrahedra.
 
@@ -468,9 +468,14 @@ class myEvaluater:
         pose.SupportPlane): each frame's supporting plane is cut out first, keyed by the frame's number as ``track`` does.
         use_mask with inst_ids (n,) and an 'inst_mask' in every frame: object k only fuses the pixels whose byte is inst_ids[k].
         The frames are uploaded once; nothing is read back before the meshing, which reads each volume's triangle count and soup.
+        indexed, cluster: ops.tsdf_meshset's -- indexed=True welds each model into an indexed mesh on the device (the same triangles
+        over shared vertices; only counts are read back), cluster in (2, 4, 8) then decimates it by voxel clusters (DESIGN.md section
+        3 "Indexed meshes from volumes").
         -> (volumes, ops.MeshSet of the n scanned models); a volume without a face raises ValueError."""
         if support is not None and not isinstance(support, SupportPlane):
             raise TypeError("scan: support must be a pose.SupportPlane")
+        if cluster not in ops.WELD_CLUSTERS or (cluster != 1 and not indexed):
+            raise ValueError("scan: cluster must be 1, 2, 4 or 8, and needs indexed=True")
         frames = list(sequence)
         if not frames or len(tracked) != len(frames):
             raise ValueError("scan: one entry of tracked per frame of a sequence that is not empty")
@@ -501,7 +506,7 @@ class myEvaluater:
             scan_models(volumes, depth, camk, up(rts.reshape(T * n, 4, 4)), job_img=up(np.repeat(np.arange(T, dtype=np.int32), n)),
                         job_model=up(job_model), trunc_mm=trunc_mm, near=near, mask=inst.view(torch.uint8) if masked else None,
                         job_mask_val=up(np.tile(np.asarray(inst_ids).astype(np.uint8), T)) if masked else None)
-            return volumes, ops.tsdf_meshset(volumes, min_weight)
+            return volumes, ops.tsdf_meshset(volumes, min_weight, indexed=indexed, cluster=cluster)
 
     def scan_track(self, sequence, init, camK=lde.REAL_INTRINSICS, ratio=None, volumes=None, G=64, trunc_mm=None, refine_kw=None,
                    n_pts=1024, sampler=None, use_mask=True, support=None, min_inlier_frac=0.5, max_rmse=None, near=0.01):
@@ -522,7 +527,8 @@ class myEvaluater:
         frames; the results are fetched on the fetch stream as ``track`` fetches them.
         -> (results, volumes): per frame ``track``'s {'pred_RTs', 'pred_scales', 'status', 'tracked'} plus 'icp_status',
         'icp_inliers' (int32), 'icp_rmse' (float32), 'ray_hits' (int32) and 'fused' (bool: registered, and so fused), (n,) each
-        (frame 0: status 0, no ICP, fused).  Mesh the volumes with ops.tsdf_meshset."""
+        (frame 0: status 0, no ICP, fused).  Mesh the volumes with ops.tsdf_meshset (indexed=True, cluster=c for a welded or a
+        decimated model, as ``scan`` takes them)."""
         from ..pose import RaycastRefine, verify_job_pose
         if ratio is None:
             raise ValueError("scan_track: ratio is required (the reference fixes none)")

@@ -1116,7 +1116,8 @@ class MeshSet(object):
     """Triangle meshes packed once for ops.render_depth (tgp_render_depth's mesh set): ``meshes`` is a list of (verts (V,3) float,
     faces (F,3) int, local to their mesh).  Holds verts (sum V,3) float32, faces (sum F,3) int32 and the prefix sums vptr / fptr
     (M+1) int32 on ``device``, and on the host the counts, the largest mesh and each mesh's axis-aligned extent.  ops.mesh_sample
-    reads the same set; its cumulative-area table is built on first use (area_cdf)."""
+    reads the same set; its cumulative-area table is built on first use (area_cdf).  from_device takes meshes that are packed on
+    the GPU already (ops.tsdf_meshset(indexed=True) makes its set that way)."""
 
     def __init__(self, meshes, device="cuda"):
         import numpy as np
@@ -1142,6 +1143,53 @@ class MeshSet(object):
         self.fptr = up(np.concatenate([[0], np.cumsum(self.n_faces)]).astype(np.int32))
         self._area_cdf = None
         self._diameter = None            # (M) float64, each mesh's largest vertex-to-vertex distance: evaluation.bop.diameter fills it
+        self.vert_normals = None         # (sum V,3) float32 unit vertex normals: mesh_vertex_normals makes them, tsdf_meshset(normals=True) keeps them
+        self.normal_scale = None         # (M) float64 quantisation of mesh_vertex_normals; None: 2^40 / (largest extent)^2
+
+    @classmethod
+    def from_device(cls, verts, faces, n_verts, n_faces):
+        """The set of meshes that are already packed on a GPU: verts (sum V,3) float32 and faces (sum F,3) int32, local to their
+        mesh, contiguous, with the host lists n_verts and n_faces (M ints each).  The meshes are not read back: each mesh's extent
+        and its smallest and largest face index are made on the device and M x 5 numbers are read once.  An empty mesh, a mesh at
+        the renderer's face cap and a face index outside its mesh are refused by name, as __init__ refuses them."""
+        import numpy as np
+        if not (torch.is_tensor(verts) and verts.is_cuda and verts.dtype == torch.float32 and verts.is_contiguous() and verts.dim() == 2
+                and verts.shape[1] == 3):
+            raise TypeError("MeshSet.from_device: verts must be a contiguous (sum V,3) float32 GPU tensor")
+        if not (torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int32 and faces.is_contiguous() and faces.dim() == 2
+                and faces.shape[1] == 3 and faces.device == verts.device):
+            raise TypeError("MeshSet.from_device: faces must be a contiguous (sum F,3) int32 tensor on verts' device")
+        n_verts, n_faces = [int(n) for n in n_verts], [int(n) for n in n_faces]
+        if not n_verts or len(n_verts) != len(n_faces):
+            raise ValueError("MeshSet.from_device: n_verts and n_faces must list the same M >= 1 meshes")
+        for i, (nv, nf) in enumerate(zip(n_verts, n_faces)):
+            if nv < 1 or nf < 1:
+                raise ValueError("MeshSet.from_device: mesh %d is empty (%d vertices, %d faces)" % (i, nv, nf))
+            if nf >= render_max_faces():
+                raise ValueError("MeshSet.from_device: mesh %d has %d faces; the cap is %d" % (i, nf, render_max_faces() - 1))
+        if sum(n_verts) != verts.shape[0] or sum(n_faces) != faces.shape[0]:
+            raise ValueError("MeshSet.from_device: the counts must add up to the rows of verts and faces")
+        vp, fp = np.concatenate([[0], np.cumsum(n_verts)]), np.concatenate([[0], np.cumsum(n_faces)])
+        rows = []
+        for m in range(len(n_verts)):
+            v, f = verts[vp[m]:vp[m + 1]], faces[fp[m]:fp[m + 1]]
+            rows.append(torch.cat([(v.amax(0) - v.amin(0)).double(), torch.stack([f.min(), f.max()]).double()]))
+        host = torch.stack(rows).cpu().numpy()                # the read-back: M x 5 numbers
+        for i in range(len(n_verts)):
+            if host[i, 3] < 0 or host[i, 4] >= n_verts[i]:
+                raise ValueError("MeshSet.from_device: mesh %d has a face index outside its %d vertices" % (i, n_verts[i]))
+        self = cls.__new__(cls)
+        self.n_verts, self.n_faces = n_verts, n_faces
+        self.extent = host[:, :3].astype(np.float32)
+        self.device = verts.device
+        self.verts, self.faces = verts, faces
+        self.vptr = torch.from_numpy(vp.astype(np.int32)).to(self.device)
+        self.fptr = torch.from_numpy(fp.astype(np.int32)).to(self.device)
+        self._area_cdf = None
+        self._diameter = None
+        self.vert_normals = None
+        self.normal_scale = None
+        return self
 
     def __len__(self):
         return len(self.n_verts)
@@ -2403,6 +2451,35 @@ class IcpModels(object):
         return cls(out["points"])
 
     @classmethod
+    def from_vertices(cls, meshset, meshes, n):
+        """each of ``meshes`` (mesh indices of the set) thinned to n of its own vertices by ops.farthest_points, with their vertex
+        normals (``meshset.vert_normals``: ops.tsdf_meshset(..., indexed=True, normals=True), or ops.mesh_vertex_normals): the model
+        points of a welded or decimated scan.  A mesh of more vertices than farthest_points takes is first thinned to that many at
+        an even stride.  Nothing is read back.  Raises if the set has no vert_normals or a mesh has fewer than n vertices."""
+        if not isinstance(meshset, MeshSet):
+            raise TypeError("IcpModels.from_vertices: meshset must be an ops.MeshSet")
+        if getattr(meshset, "vert_normals", None) is None:
+            raise ValueError("IcpModels.from_vertices: the mesh set has no vert_normals (ops.mesh_vertex_normals makes them)")
+        meshes, n = [int(m) for m in meshes], int(n)
+        if not meshes or not 1 <= n <= ICP_MAX_POINTS:
+            raise ValueError("IcpModels.from_vertices: at least one mesh and n in [1, %d]" % ICP_MAX_POINTS)
+        rows, first, cap = [], [0], fps_max_points()
+        for nv in meshset.n_verts:
+            first.append(first[-1] + nv)
+        for m in meshes:
+            if not 0 <= m < len(meshset):
+                raise ValueError("IcpModels.from_vertices: mesh %d is outside the set of %d meshes" % (m, len(meshset)))
+            nv = meshset.n_verts[m]
+            if nv < n:
+                raise ValueError("IcpModels.from_vertices: mesh %d has %d vertices, fewer than n = %d" % (m, nv, n))
+            pn = torch.cat([meshset.verts[first[m]:first[m + 1]], meshset.vert_normals[first[m]:first[m + 1]]], 1)
+            if nv > cap:
+                pn = pn[(torch.arange(cap, device=pn.device, dtype=torch.int64) * nv) // cap]
+            idx = farthest_points(pn[None, :, :3].contiguous(), n)
+            rows.append(pn[idx[0].long()])
+        return cls(torch.stack(rows).contiguous())
+
+    @classmethod
     def from_raycast(cls, rc):
         """one model per job of a tsdf_raycast result: the job's hits [vertex, normal] packed to the front in ray order (a stable sort
         of the miss mask and a gather, on the device), counts = rc['count']; rows past the count are the misses' zeros.  Nothing is
@@ -2770,18 +2847,177 @@ def tsdf_mesh(volumes, model, min_weight=1, face_cap=None):
             "status": info[1], "counts": counts}
 
 
-def tsdf_meshset(volumes, min_weight=1):
-    """Every volume's surface (tsdf_mesh) as one ops.MeshSet on the volumes' device: what IcpModels.from_meshset, pose.Verify,
-    DistanceFields (through IcpModels) and evaluation.bop take.  Each volume's triangle count is read back once, and its soup once
-    (MeshSet packs on the host).  A volume without a face is refused by name."""
-    meshes = []
-    for m in range(len(volumes)):
-        out = tsdf_mesh(volumes, m, min_weight)
-        if out["verts"].shape[0] == 0:
-            raise ValueError("tsdf_meshset: volume %d has no face (no cube with all eight corners seen %d times and a sign change)"
-                             % (m, min_weight))
-        meshes.append((out["verts"].cpu().numpy(), out["faces"].cpu().numpy()))
-    return MeshSet(meshes, device=volumes.sum.device)
+# ------------------------------------------------------------------------------------------------------------ indexed meshes from volumes
+WELD_MAX_VERTS = _lib.WELD_MAX_VERTS
+WELD_CLUSTERS = (1, 2, 4, 8)
+
+
+def volume_normal_scale(voxel):
+    """mesh_vertex_normals' quantisation for a volume's mesh: 2^30 / voxel^2 in float64 on the float32 voxel edge (a face's cross
+    product is at most a few voxel^2)"""
+    v = float(voxel)
+    return 2.0 ** 30 / (v * v)
+
+
+def tsdf_mesh_indexed(volumes, model, min_weight=1, face_cap=None, vert_cap=None, cluster=1):
+    """The surface of one volume as an INDEXED mesh (tgp_tsdf_weld_*, csrc/weld.hip; DESIGN.md section 3 "Indexed meshes from
+    volumes"): tsdf_mesh's triangles in tsdf_mesh's order, with every vertex once.  A vertex is named by the voxel edge it cuts --
+    key = flat(A) 8 + d, A the edge's smaller end, d = dx << 2 | dy << 1 | dz the step to the other -- and vertices are numbered in
+    ascending key: a bit mask per voxel, a prefix sum and a rank, no float is compared.  verts[faces].reshape(-1, 3) is tsdf_mesh's
+    soup byte for byte.  Vertices at a corner whose sum is 0 have equal positions and different names; they stay distinct.
+    Both caps None: the two counts are read back once and verts, faces are exactly (V,3), (F,3).  Both caps ints: nothing is read
+    back, verts is (vert_cap,3) and faces (face_cap,3), rows beyond the counts zero; a face that names a vertex at or beyond
+    vert_cap is dropped (status bit 2), then faces beyond face_cap are dropped in order (status bit 1).
+    cluster c in (2, 4, 8) decimates: the vertices whose A lies in one cell of c^3 voxels become their mean (in 2^-16 voxel
+    fixed point, integer sums), occupied cells are numbered in ascending flat cell index, faces are renamed, those with two equal
+    names dropped, the rest rotated to start at their smallest name (winding kept), exact duplicates removed and the survivors
+    sorted by that triple; this path reads the cell count back and torch.unique sizes its result on the host.
+    -> dict: verts float32 (model units), faces int32, n_verts, n_faces, status () int64, mask (G^3) uint8 (bit d of mask[A]: vertex
+    (A, d) exists), normal_scale (mesh_vertex_normals' quantisation for this mesh); all tensors on the volumes' device."""
+    who = "tsdf_mesh_indexed"
+    if not isinstance(volumes, TsdfVolumes):
+        raise TypeError("%s: volumes must be an ops.TsdfVolumes" % who)
+    if not (isinstance(model, int) and 0 <= model < len(volumes)):
+        raise ValueError("%s: model must index the %d volumes" % (who, len(volumes)))
+    if not (isinstance(min_weight, int) and min_weight >= 1):
+        raise ValueError("%s: min_weight must be an int >= 1" % who)
+    if cluster not in WELD_CLUSTERS:
+        raise ValueError("%s: cluster must be 1, 2, 4 or 8" % who)
+    if (face_cap is None) != (vert_cap is None):
+        raise ValueError("%s: face_cap and vert_cap come together" % who)
+    if face_cap is not None and not (isinstance(face_cap, int) and 0 <= face_cap <= TSDF_MAX_FACES):
+        raise ValueError("%s: face_cap must be None or an int in [0, %d]" % (who, TSDF_MAX_FACES))
+    if vert_cap is not None and not (isinstance(vert_cap, int) and 0 <= vert_cap <= WELD_MAX_VERTS):
+        raise ValueError("%s: vert_cap must be None or an int in [0, %d]" % (who, WELD_MAX_VERTS))
+    G, dev, lib, st = volumes.G, volumes.sum.device, _lib.lib(), _stream(volumes.sum)
+    cells = G * G * G
+    mask = torch.empty(cells, device=dev, dtype=torch.uint8)
+    vcounts = torch.empty(cells, device=dev, dtype=torch.int32)
+    fcounts = torch.empty(cells, device=dev, dtype=torch.int32)
+    a = _lib.TsdfWeldArgs(sum=_p(volumes.sum), weight=_p(volumes.weight), meta=_p(volumes.meta), M=len(volumes), G=G, model=model,
+                          min_weight=min_weight, mask=_p(mask), vcounts=_p(vcounts), fcounts=_p(fcounts),
+                          vert_cap=WELD_MAX_VERTS if vert_cap is None else vert_cap)
+    check(lib.tgp_tsdf_weld_mark(ctypes.byref(a), st), "tgp_tsdf_weld_mark")
+    voffsets = torch.cumsum(vcounts, 0, dtype=torch.int64)
+    a.voffsets = _p(voffsets)
+    check(lib.tgp_tsdf_weld_count(ctypes.byref(a), st), "tgp_tsdf_weld_count")
+    foffsets = torch.cumsum(fcounts, 0, dtype=torch.int64)
+    if vert_cap is None:
+        vcap, fcap = torch.stack([voffsets[-1], foffsets[-1]]).cpu().tolist()       # the read-back
+        if fcap > TSDF_MAX_FACES:
+            raise ValueError("%s: the volume has %d triangles, above the cap of %d; pass caps" % (who, fcap, TSDF_MAX_FACES))
+    else:
+        vcap, fcap = vert_cap, face_cap
+    verts = torch.zeros(vcap, 3, device=dev, dtype=torch.float32)
+    faces = torch.zeros(fcap, 3, device=dev, dtype=torch.int32)
+    info = torch.zeros(3, device=dev, dtype=torch.int64)
+    a.foffsets, a.vert_cap, a.face_cap, a.info = _p(foffsets), vcap, fcap, _p(info)
+    a.verts, a.faces = _p(verts) if vcap else None, _p(faces) if fcap else None
+    check(lib.tgp_tsdf_weld_verts(ctypes.byref(a), st), "tgp_tsdf_weld_verts")
+    check(lib.tgp_tsdf_weld_faces(ctypes.byref(a), st), "tgp_tsdf_weld_faces")
+    out = {"verts": verts, "faces": faces, "n_verts": info[0], "n_faces": info[1], "status": info[2], "mask": mask,
+           "normal_scale": volume_normal_scale(volumes.meta_host[model, 3])}
+    if cluster == 1:
+        return out
+    side = -(-G // cluster)
+    vcell = torch.zeros(vcap, device=dev, dtype=torch.int32)
+    sums = torch.empty(side ** 3, 3, device=dev, dtype=torch.int64)
+    counts = torch.empty(side ** 3, device=dev, dtype=torch.int32)
+    c = _lib.WeldClusterArgs(mask=_p(mask), voffsets=_p(voffsets), verts=_p(verts) if vcap else None, meta=_p(volumes.meta), M=len(volumes),
+                             G=G, model=model, cluster=cluster, vert_cap=vcap, vcell=_p(vcell) if vcap else None, cell_sums=_p(sums),
+                             cell_counts=_p(counts))
+    check(lib.tgp_weld_cluster(ctypes.byref(c), st), "tgp_weld_cluster")
+    occupied = counts > 0
+    number = torch.cumsum(occupied, 0, dtype=torch.int64) - 1                       # a cell's name: its rank among the occupied ones
+    n_cells = int(number[-1].item()) + 1                                            # the read-back
+    order = torch.sort((~occupied).to(torch.uint8), stable=True).indices[:n_cells]  # the occupied cells, ascending
+    meta = volumes.meta[model]
+    first = meta[:3] + torch.tensor(0.5 - (G // 2), device=dev, dtype=torch.float32) * meta[3]      # voxel 0's centre, float32
+    mean = sums[order].double() / counts[order].double()[:, None]
+    rep = (first.double() + (mean * meta[3].double()) / 65536.0).float()
+    names = number[vcell.long()[faces.long()]]                                     # (fcap,3); rows beyond n_faces name one cell thrice
+    keep = (names[:, 0] != names[:, 1]) & (names[:, 1] != names[:, 2]) & (names[:, 2] != names[:, 0])
+    turn = (names.argmin(1)[:, None] + torch.arange(3, device=dev)[None]) % 3
+    r = torch.gather(names, 1, turn)
+    packed = torch.unique(((r[:, 0] << 42) | (r[:, 1] << 21) | r[:, 2])[keep])      # names are below 2^21; sorted = lexicographic
+    low = (1 << 21) - 1
+    cfaces = torch.stack([packed >> 42, (packed >> 21) & low, packed & low], 1).to(torch.int32)
+    out.update(verts=rep, faces=cfaces, n_verts=torch.tensor(n_cells, device=dev), n_faces=torch.tensor(cfaces.shape[0], device=dev))
+    return out
+
+
+def mesh_vertex_normals(mesh, scale=None):
+    """Area-weighted unit vertex normals (tgp_mesh_vertex_normals, csrc/weld.hip; DESIGN.md section 3 "Indexed meshes from
+    volumes") of an ops.MeshSet -- CAD meshes too -- or of a tsdf_mesh_indexed result.  Per face the float32 cross product (p1 -
+    p0) x (p2 - p0), times the mesh's ``scale`` in float64, rounded to an integer and added to its three vertices' int64 sums by
+    integer atomics; each sum is normalised in float64 and rounded to float32 once.  Integer sums: two calls give identical bytes.
+    A vertex that no face with area uses gets (0, 0, 0).  scale: (M) floats; None: the set's ``normal_scale`` (2^30 / voxel^2 for a
+    volume's mesh), else 2^40 / (the mesh's largest extent)^2.  -> (sum V,3) float32 on the mesh's device; nothing is read back."""
+    if isinstance(mesh, MeshSet):
+        verts, faces, vptr, fptr, M = mesh.verts, mesh.faces, mesh.vptr, mesh.fptr, len(mesh)
+        if scale is None:
+            scale = mesh.normal_scale
+        if scale is None:
+            ext = [float(e.max()) for e in mesh.extent]
+            scale = [2.0 ** 40 / (e * e) if e > 0 else 1.0 for e in ext]
+    elif isinstance(mesh, dict) and all(k in mesh for k in ("verts", "faces", "n_verts", "n_faces")):
+        verts, faces, M = mesh["verts"], mesh["faces"], 1
+        zero = torch.zeros((), device=verts.device, dtype=torch.int64)
+        vptr, fptr = torch.stack([zero, mesh["n_verts"]]).to(torch.int32), torch.stack([zero, mesh["n_faces"]]).to(torch.int32)
+        if scale is None:
+            scale = [mesh["normal_scale"]]
+    else:
+        raise TypeError("mesh_vertex_normals: an ops.MeshSet or a tsdf_mesh_indexed result is expected")
+    if not verts.is_cuda:
+        raise TypeError("mesh_vertex_normals: the mesh must be on a GPU")
+    scale = [float(x) for x in scale]
+    if len(scale) != M or not all(math.isfinite(x) and x > 0 for x in scale):
+        raise ValueError("mesh_vertex_normals: scale must be %d positive finite numbers" % M)
+    dev, V, F = verts.device, verts.shape[0], faces.shape[0]
+    scale_t = torch.tensor(scale, device=dev, dtype=torch.float64)
+    sums = torch.empty(V, 3, device=dev, dtype=torch.int64)
+    normals = torch.zeros(V, 3, device=dev, dtype=torch.float32)
+    a = _lib.MeshNormalsArgs(verts=_p(verts) if V else None, faces=_p(faces) if F else None, vptr=_p(vptr), fptr=_p(fptr), M=M, V=V, F=F,
+                             scale=_p(scale_t), sums=_p(sums) if V else None, normals=_p(normals) if V else None)
+    check(_lib.lib().tgp_mesh_vertex_normals(ctypes.byref(a), _stream(verts)), "tgp_mesh_vertex_normals")
+    return normals
+
+
+def tsdf_meshset(volumes, min_weight=1, indexed=False, cluster=1, normals=False):
+    """Every volume's surface as one ops.MeshSet on the volumes' device: what IcpModels.from_meshset, pose.Verify, DistanceFields
+    (through IcpModels) and evaluation.bop take.  A volume without a face is refused by name.
+    indexed False (the default): tsdf_mesh's soups; each volume's triangle count is read back once, and its soup once (MeshSet
+    packs on the host).  indexed True: tsdf_mesh_indexed's welded meshes -- the same triangles in the same order over shared
+    vertices -- packed on the device (MeshSet.from_device): per volume only the two counts are read back, and M x 5 numbers for the
+    set.  cluster (2, 4 or 8, with indexed) decimates by voxel clusters.  normals: the set carries ``vert_normals`` (sum V,3)
+    float32 (mesh_vertex_normals), which IcpModels.from_vertices needs."""
+    if not isinstance(volumes, TsdfVolumes):
+        raise TypeError("tsdf_meshset: volumes must be an ops.TsdfVolumes")
+    if cluster not in WELD_CLUSTERS:
+        raise ValueError("tsdf_meshset: cluster must be 1, 2, 4 or 8")
+    if cluster != 1 and not indexed:
+        raise ValueError("tsdf_meshset: cluster needs indexed=True")
+    empty = "tsdf_meshset: volume %d has no face (no cube with all eight corners seen %d times and a sign change)"
+    if indexed:
+        vs, fs = [], []
+        for m in range(len(volumes)):
+            out = tsdf_mesh_indexed(volumes, m, min_weight, cluster=cluster)
+            if out["faces"].shape[0] == 0:
+                raise ValueError(empty % (m, min_weight))
+            vs.append(out["verts"]), fs.append(out["faces"])
+        ms = MeshSet.from_device(torch.cat(vs), torch.cat(fs), [v.shape[0] for v in vs], [f.shape[0] for f in fs])
+        ms.normal_scale = [volume_normal_scale(v) for v in volumes.meta_host[:, 3]]
+    else:
+        meshes = []
+        for m in range(len(volumes)):
+            out = tsdf_mesh(volumes, m, min_weight)
+            if out["verts"].shape[0] == 0:
+                raise ValueError(empty % (m, min_weight))
+            meshes.append((out["verts"].cpu().numpy(), out["faces"].cpu().numpy()))
+        ms = MeshSet(meshes, device=volumes.sum.device)
+    if normals:
+        ms.vert_normals = mesh_vertex_normals(ms)
+    return ms
 
 
 # ------------------------------------------------------------------------------------------------------------ ray casting of the volumes
