@@ -128,6 +128,56 @@ def three_scenes():
     return case(meshes, [[], [(1, 9, rot("y", 30), (0.05, 0.0, 0.7), 0.3)], seven], camk=camk)
 
 
+RASTER_THREADS, RASTER_CAP = 256, 512                     # csrc/raster.h: the boxes a tile walks per chunk, the records its list holds
+CARRY_IDS = (11, 22)
+
+
+def tile_walk(c, scene=0, tile=(0, 0)):
+    """The record list of one 16 x 16 tile over its scene's instance slots, as csrc/raster.h walks it: per slot, the number of records
+    held after the slot's last chunk, and the sizes of the lists swept inside the slot's walk -- a list is swept, and emptied, when
+    it holds more than RASTER_CAP - RASTER_THREADS records after a chunk of RASTER_THREADS boxes.  The boxes are render_ref's."""
+    tx0, ty0 = tile[0] * 16, tile[1] * 16
+    held, n = [], 0
+    for i in range(int(c["scene_ptr"][scene]), int(c["scene_ptr"][scene + 1])):
+        verts, faces = c["meshes"][int(c["inst_mesh"][i])]
+        X, Y, _, flag = render_ref.project(verts, c["inst_pose"][i], c["camk"][scene], c["near"])
+        faces = np.asarray(faces, dtype=np.int64)
+        x, y = X[faces], Y[faces]
+        x0, x1 = np.maximum(-((-x.min(1)) // 256), 0), np.minimum(x.max(1) // 256, c["W"] - 1)
+        y0, y1 = np.maximum(-((-y.min(1)) // 256), 0), np.minimum(y.max(1) // 256, c["H"] - 1)
+        area = (x[:, 1] - x[:, 0]) * (y[:, 2] - y[:, 0]) - (y[:, 1] - y[:, 0]) * (x[:, 2] - x[:, 0])
+        meets = (flag[faces] == 0).all(1) & (area != 0) & (x0 <= x1) & (y0 <= y1) & (x0 <= tx0 + 15) & (x1 >= tx0) & (y0 <= ty0 + 15) & (y1 >= ty0)
+        swept = []
+        for base in range(0, len(faces), RASTER_THREADS):
+            n += int(meets[base:base + RASTER_THREADS].sum())
+            assert n <= RASTER_CAP
+            if n > RASTER_CAP - RASTER_THREADS:
+                swept.append(n)
+                n = 0
+        held.append((n, swept))
+    return held
+
+
+def slot_carry():
+    """32 x 32, one scene of two instances of 200 small triangles each, every one in the tile at the origin: triangle k covers the one
+    sample (1 + k % 14, 1 + k // 14 % 14) and lies at z = 1 m where k + slot is even, at 1.05 m where it is odd, so each instance
+    wins every other column of the 14 x 14 block.  The tile's record list holds 200 records after the first slot -- below the sweep's
+    threshold of 256 -- carries them into the second slot, holds 400 after that slot's only chunk and is swept there, inside the
+    walk: asserted here, so that the case cannot stop crossing the threshold with records of both slots in the list."""
+    f = 64.0
+    meshes = []
+    for slot in range(2):
+        v = []
+        for k in range(200):
+            cx, cy, z = 1 + k % 14, 1 + k // 14 % 14, 1.0 + 0.05 * ((k + slot) % 2)
+            v += [((cx - 0.6) * z / f, (cy - 0.6) * z / f, z), ((cx + 0.8) * z / f, (cy - 0.6) * z / f, z), ((cx - 0.6) * z / f, (cy + 0.8) * z / f, z)]
+        meshes.append((np.asarray(v, dtype=np.float32), np.arange(600, dtype=np.int32).reshape(200, 3)))
+    c = case(meshes, [[(0, CARRY_IDS[0], I3, Z3, 1.0), (1, CARRY_IDS[1], I3, Z3, 1.0)]], camk=(f, f, 0.0, 0.0), h=32, w=32)
+    assert tile_walk(c) == [(200, []), (0, [400])]
+    assert all(tile_walk(c, tile=t) == [(0, []), (0, [])] for t in ((1, 0), (0, 1), (1, 1)))
+    return c
+
+
 @functools.lru_cache(maxsize=None)
 def _reference(name, arg):
     c = BUILDERS[name]() if arg is None else BUILDERS[name](arg)
@@ -143,4 +193,4 @@ def reference(name, arg=None):
 
 
 BUILDERS = dict(rectangle=rectangle, slanted_plane=slanted_plane, cube=cube, rules=rules, tails=tails, tiny_triangles=tiny_triangles,
-                three_scenes=three_scenes)
+                three_scenes=three_scenes, slot_carry=slot_carry)

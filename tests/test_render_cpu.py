@@ -87,6 +87,19 @@ def test_rules():
     assert hit.sum() > 1000 and (ref["depth"][5] == 0).all() and np.allclose(ref["z"][5][hit], 70.0, rtol=1e-5)
 
 
+def test_slot_carry():
+    """the case whose record list crosses the sweep threshold with both slots' records in it (the builder asserts the counts): the
+    restatement gives the closed form -- the 14 x 14 block at (1, 1) at 1000 mm, its columns alternating between the two instances"""
+    c, ref = rc.reference("slot_carry")
+    want = np.zeros((32, 32), dtype=np.uint8)
+    want[1:15, 1:15] = np.where(np.arange(14) % 2 == 0, rc.CARRY_IDS[0], rc.CARRY_IDS[1])[None, :]
+    assert np.array_equal(ref["mask"][0], want) and np.array_equal(ref["depth"][0], np.where(want > 0, 1000, 0))
+    k = (np.arange(32)[:, None] - 1) * 14 + (np.arange(32)[None, :] - 1)                      # the face at a pixel of the block: 0 .. 195
+    assert np.array_equal(ref["face"][0], np.where(want > 0, k, -1))
+    assert ref["visible"].tolist() == [98, 98] and ref["bbox"].tolist() == [[1, 1, 15, 14], [1, 2, 15, 15]] and ref["dropped"].tolist() == [[0, 0]]
+    assert int((ref["mask"][0] > 0).sum()) == int(ref["visible"].sum())
+
+
 def test_render_abi():
     """the caps, and argument errors launch nothing (no GPU is touched); tests/test_abi_cpu.py holds the symbols and tgp_render_args
     against the header"""

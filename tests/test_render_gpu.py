@@ -47,13 +47,15 @@ def _assert_equal(out, ref):
 
 
 CASES = [("rectangle", s) for s in sorted(rc.RECT_SPLITS)] + [("slanted_plane", 1), ("slanted_plane", 24), ("rules", None), ("cube", None),
-                                                              ("tails", None), ("tiny_triangles", None), ("three_scenes", None)]
+                                                              ("tails", None), ("tiny_triangles", None), ("three_scenes", None),
+                                                              ("slot_carry", None)]
 
 
 @pytest.mark.parametrize("name,arg", CASES, ids=["%s-%s" % c if c[1] is not None else c[0] for c in CASES])
 def test_kernel_equals_restatement(name, arg):
     """the CPU file's closed-form cases; tile tails and triangles longer than the image at 123 x 157; 20 480 sub-pixel triangles
-    in one tile; three scenes of 0, 1 and 7 instances with a camk each and ids out of slot order"""
+    in one tile; three scenes of 0, 1 and 7 instances with a camk each and ids out of slot order; two instances whose records share
+    the tile's list when it crosses the sweep threshold"""
     c, ref = rc.reference(name, arg)
     out = _render(c)
     _assert_equal(out, ref)

@@ -1,9 +1,29 @@
-// The rasteriser's arithmetic, shared by the depth renderer (render.hip) and pose verification (verify.hip): DESIGN.md section 3 "The
-// depth renderer" states every rule below and tests/render_ref.py restates them in numpy.  A vertex is posed, projected and snapped to
-// 1/256 px; a triangle is dropped by the near rule or the guard band, or gets the pixel box of its snapped corners; a tile sets the
-// triangles that meet it up into LDS records at its first sample point and every lane runs the records against its own pixel, keeping
-// the smallest 64-bit key {z bits, lo}.  The loops around these steps -- which boxes a tile walks, when the list is swept -- belong
-// to the kernels.
+// The rasteriser, shared by the depth renderer (render.hip), pose verification (verify.hip) and two-pose VSD (vsd.hip): DESIGN.md
+// section 3 "The depth renderer" states every rule below and tests/render_ref.py restates them in numpy.  A vertex is posed,
+// projected and snapped to 1/256 px; a triangle is dropped by the near rule or the guard band, or gets the pixel box of its snapped
+// corners; a tile sets the triangles that meet it up into LDS records at its first sample point and every lane runs the records
+// against its own pixel, keeping the smallest 64-bit key {z bits, lo}.  The loops around these steps are here too, once for the
+// three files: the decode of a mesh of the set (raster_mesh, raster_job), the workspace's layout (RasterWorkspace), a face's box and
+// a workgroup's reduction of its boxes (raster_face_box, raster_box_reduce), the walk of a triangle list through the tile's records
+// (raster_reset, raster_bin, raster_flush) and the launch shape of the job kernels (raster_job_launch).  What a kernel does with a
+// pixel's winner is its own.
+//
+// The tile walk's contract.  s_rec[RASTER_CAP] and s_n live in the kernel's LDS; every lane of the workgroup enters each of the
+// three calls, in uniform control flow.
+//   raster_reset   empties the list: a barrier (every lane is behind the sweep that last read s_n and s_rec), lane 0 writes
+//                  s_n = 0, a barrier (no lane adds before the write).  The caller may write s_n = 0 itself where a barrier of
+//                  its own follows, as the renderer does at its start.
+//   raster_bin     walks one triangle list 256 boxes at a time.  It neither resets s_n nor sweeps on entry: it adds to the records
+//                  it finds.  Per chunk: the lanes whose box meets the tile append a record; a barrier (every append is done); every
+//                  lane reads n = s_n; a barrier (every lane has read s_n before a lane of the next chunk, or of the next call, adds to
+//                  it).  Where n > RASTER_CAP - RASTER_THREADS -- the next chunk could overflow -- every lane sweeps the n records, a
+//                  barrier (every lane is done with s_rec), lane 0 writes s_n = 0, a barrier.  So on return s_n <= RASTER_CAP -
+//                  RASTER_THREADS, the last barrier is behind every write of s_n and s_rec, and the records not yet swept stay.
+//   raster_flush   sweeps what is left; the barrier before it is raster_bin's last one (the reset's, where nothing was binned), and
+//                  it leaves none behind it: the caller resets, or is done with the list.
+// The renderer resets once, bins every instance slot of its scene -- records carry over from one slot to the next -- and flushes once
+// after the last slot; its low word is slot << 24 | face.  Verification and VSD reset before each surface and flush after it; their
+// low word is the face.
 #ifndef TGP_RASTER_H
 #define TGP_RASTER_H
 #include "tgp_common.h"
@@ -12,6 +32,8 @@
 #define RASTER_TILE 16
 #define RASTER_THREADS (RASTER_TILE * RASTER_TILE)
 #define RASTER_CAP (2 * RASTER_THREADS) // records held before a raster sweep: one chunk always fits behind a sweep's threshold
+#define RASTER_MAX_SIDE 16384           // a frame's side: at 256 units a pixel, the guard band
+#define RASTER_MAX_T 1024               // workgroups per job of a job kernel's tile pass
 
 struct RasterRec {
     long long e[3]; // edge functions at the tile's first sample point
@@ -116,6 +138,163 @@ __device__ __forceinline__ int raster_depth_mm(float z)
 {
     const float mm = rintf(z * 1000.f);
     return mm <= 65535.f ? (int)mm : 0;
+}
+
+struct RasterMesh {
+    int vbase, nv, fbase, nf;
+};
+
+// mesh `mesh` of a's set, cut to the arrays and to the host's bounds; false: it renders nothing
+template <class Args> __device__ __forceinline__ bool raster_mesh(const Args &a, int mesh, RasterMesh &m)
+{
+    if (mesh < 0 || mesh >= a.M) return false;
+    m.vbase = a.vptr[mesh];
+    m.fbase = a.fptr[mesh];
+    const long long nv = (long long)a.vptr[mesh + 1] - m.vbase, nf = (long long)a.fptr[mesh + 1] - m.fbase;
+    if (m.vbase < 0 || m.fbase < 0 || nv < 1 || nf < 1 || m.vbase + nv > a.n_verts || m.fbase + nf > a.n_faces) return false;
+    m.nv = (int)min(nv, (long long)a.max_verts);
+    m.nf = (int)min(nf, (long long)a.max_faces);
+    return true;
+}
+
+// the frame and the mesh of job j, the frame checked against the host's S; false: the job's rows stay zero
+template <class Args> __device__ __forceinline__ bool raster_job(const Args &a, int j, int &img, RasterMesh &m)
+{
+    img = a.job_img[j];
+    const int mesh = a.job_mesh[j]; // read beside job_img, not behind its check: one load's latency less at the head of every kernel
+    return img >= 0 && img < a.S && raster_mesh(a, mesh, m);
+}
+
+// the workspace of U units (instances, jobs or pseudo-jobs): U x max_verts vertex records, U x max_faces triangle boxes, then four
+// words per unit (first x, first y, last x, last y over the unit's boxes for a job; the renderer's bbox accumulators)
+__host__ __device__ inline int64_t raster_workspace_bytes(int64_t U, int max_verts, int max_faces)
+{
+    return U * max_verts * (int64_t)sizeof(int4) + U * max_faces * (int64_t)sizeof(short4) + U * 16 + 16;
+}
+
+struct RasterWorkspace {
+    int4 *v;
+    short4 *b;
+    int *ub;
+    int max_verts, max_faces;
+    __device__ __forceinline__ RasterWorkspace(void *workspace, int64_t U, int max_verts, int max_faces)
+        : v((int4 *)workspace), b((short4 *)(v + U * max_verts)), ub((int *)(b + U * max_faces)), max_verts(max_verts), max_faces(max_faces)
+    {
+    }
+    __device__ __forceinline__ int4 *vrec(size_t u) const { return v + u * max_verts; }
+    __device__ __forceinline__ short4 *boxes(size_t u) const { return b + u * max_faces; }
+    __device__ __forceinline__ int *unit_box(size_t u) const { return ub + u * 4; }
+};
+template <class Args> __device__ __forceinline__ RasterWorkspace raster_workspace(const Args &a, int64_t U)
+{
+    return RasterWorkspace(a.workspace, U, a.max_verts, a.max_faces);
+}
+
+// face t of mesh m: its corners checked against the mesh, its box from the vertex records vr into boxes[t] (empty where a corner is
+// outside the mesh or the triangle is dropped).  -> raster_box's rule
+__device__ __forceinline__ int raster_face_box(const int32_t *faces, const RasterMesh &m, int t, const int4 *vr, int W, int H, short4 *boxes,
+                                               short4 &box)
+{
+    const int32_t *f = faces + (size_t)(m.fbase + t) * 3;
+    const int f0 = f[0], f1 = f[1], f2 = f[2];
+    box = make_short4(0x7fff, -1, 0x7fff, -1); // x first, x last, y first, y last: empty, it meets no tile
+    int rule = 0;
+    if (f0 >= 0 && f0 < m.nv && f1 >= 0 && f1 < m.nv && f2 >= 0 && f2 < m.nv) rule = raster_box(vr[f0], vr[f1], vr[f2], W, H, box);
+    boxes[t] = box;
+    return rule;
+}
+
+// a workgroup's faces into their unit's box and dropped count: min / max / add in LDS, then one global atomic per class.  Entered by
+// every lane with raster_face_box's rule and box, a lane without a face with rule 0 and an empty box
+__device__ __forceinline__ void raster_box_reduce(int rule, const short4 box, int *unit_box, int32_t *dropped)
+{
+    __shared__ int s_bb[4];
+    __shared__ int s_drop;
+    if (threadIdx.x == 0) {
+        s_bb[0] = s_bb[1] = 0x7fffffff;
+        s_bb[2] = s_bb[3] = -1;
+        s_drop = 0;
+    }
+    __syncthreads();
+    if (rule) { // the near rule or the guard band
+        atomicAdd(&s_drop, 1);
+    } else if (box.x <= box.y) {
+        atomicMin(&s_bb[0], (int)box.x);
+        atomicMin(&s_bb[1], (int)box.z);
+        atomicMax(&s_bb[2], (int)box.y);
+        atomicMax(&s_bb[3], (int)box.w);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_drop) atomicAdd(dropped, s_drop);
+        if (s_bb[2] >= 0) {
+            atomicMin(unit_box + 0, s_bb[0]);
+            atomicMin(unit_box + 1, s_bb[1]);
+            atomicMax(unit_box + 2, s_bb[2]);
+            atomicMax(unit_box + 3, s_bb[3]);
+        }
+    }
+}
+
+// the tile walk: the contract is at the head of this file
+__device__ __forceinline__ void raster_reset(int &s_n)
+{
+    __syncthreads();
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+}
+
+// the nf triangles faces[fbase ..] with their boxes and vertex records, against the tile of pixels [tx0, tx1] x [ty0, ty1] whose
+// first sample is (tx0, ty0); a record's low word is lo_high | face; (li, lj) is the lane's pixel in the tile
+__device__ __forceinline__ void raster_bin(RasterRec *s_rec, int &s_n, const short4 *boxes, const int4 *vr, const int32_t *faces, int fbase,
+                                           int nf, int tx0, int ty0, int tx1, int ty1, uint32_t lo_high, int li, int lj,
+                                           unsigned long long &key)
+{
+    for (int base = 0; base < nf; base += RASTER_THREADS) {
+        const int t = base + threadIdx.x;
+        if (t < nf) {
+            const short4 b = boxes[t];
+            if (b.x <= tx1 && b.y >= tx0 && b.z <= ty1 && b.w >= ty0) { // false for an empty box
+                const int32_t *f = faces + (size_t)(fbase + t) * 3;
+                // at most RASTER_CAP - 256 records held + 256 of this chunk
+                raster_setup(s_rec[atomicAdd(&s_n, 1)], vr[f[0]], vr[f[1]], vr[f[2]], tx0, ty0, lo_high | (uint32_t)t);
+            }
+        }
+        __syncthreads();
+        const int n = s_n;
+        __syncthreads();
+        if (n > RASTER_CAP - RASTER_THREADS) {
+            raster_sweep(s_rec, n, li, lj, key);
+            __syncthreads();
+            if (threadIdx.x == 0) s_n = 0;
+            __syncthreads();
+        }
+    }
+}
+
+__device__ __forceinline__ void raster_flush(const RasterRec *s_rec, const int &s_n, int li, int lj, unsigned long long &key)
+{
+    raster_sweep(s_rec, s_n, li, lj, key);
+}
+
+// The launch shape of a job kernel (verification, VSD) over U units of J jobs: blocks of 256 per unit for the vertex and the box
+// pass, and T workgroups per job for the tile pass -- enough that a few jobs fill the device, few enough that many jobs do not flood
+// it with workgroups that find no tile; never more than the frame has tiles.  false: a grid would overflow
+struct RasterJobLaunch {
+    int vblocks, fblocks;
+    unsigned grid_v, grid_f, T;
+};
+static inline bool raster_side_ok(int H, int W) { return H <= RASTER_MAX_SIDE && W <= RASTER_MAX_SIDE; }
+static inline bool raster_job_launch(int64_t U, int J, int H, int W, int max_verts, int max_faces, RasterJobLaunch &l)
+{
+    l.vblocks = tgp_cdiv(max_verts, 256), l.fblocks = tgp_cdiv(max_faces, 256);
+    const int64_t grid_v = U * l.vblocks, grid_f = U * l.fblocks;
+    if (grid_v > 0x7fffffff || grid_f > 0x7fffffff) return false;
+    const int64_t frame_tiles = (int64_t)tgp_cdiv(W, RASTER_TILE) * tgp_cdiv(H, RASTER_TILE);
+    int64_t T = 4096 / J;
+    T = T < 16 ? 16 : T > RASTER_MAX_T ? RASTER_MAX_T : T;
+    l.grid_v = (unsigned)grid_v, l.grid_f = (unsigned)grid_f, l.T = (unsigned)(T > frame_tiles ? frame_tiles : T);
+    return true;
 }
 
 #endif

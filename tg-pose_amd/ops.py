@@ -1142,6 +1142,7 @@ class MeshSet(object):
         self.vptr = up(np.concatenate([[0], np.cumsum(self.n_verts)]).astype(np.int32))
         self.fptr = up(np.concatenate([[0], np.cumsum(self.n_faces)]).astype(np.int32))
         self._area_cdf = None
+        self._fields = {}                # fields()' dicts
         self._diameter = None            # (M) float64, each mesh's largest vertex-to-vertex distance: evaluation.bop.diameter fills it
         self.vert_normals = None         # (sum V,3) float32 unit vertex normals: mesh_vertex_normals makes them, tsdf_meshset(normals=True) keeps them
         self.normal_scale = None         # (M) float64 quantisation of mesh_vertex_normals; None: 2^40 / (largest extent)^2
@@ -1186,6 +1187,7 @@ class MeshSet(object):
         self.vptr = torch.from_numpy(vp.astype(np.int32)).to(self.device)
         self.fptr = torch.from_numpy(fp.astype(np.int32)).to(self.device)
         self._area_cdf = None
+        self._fields = {}
         self._diameter = None
         self.vert_normals = None
         self.normal_scale = None
@@ -1193,6 +1195,22 @@ class MeshSet(object):
 
     def __len__(self):
         return len(self.n_verts)
+
+    def fields(self, faces=True, maxima=False):
+        """the set as the keyword arguments of an argument struct (tgp_*_args): verts, vptr, M, n_verts; with ``faces`` faces, fptr,
+        n_faces; with ``maxima`` the largest mesh's max_verts (and max_faces).  The set does not change once it is packed, so each
+        dict is made once and kept (every call of an op asks for one): read it, do not write to it."""
+        kw = self._fields.get((faces, maxima))
+        if kw is None:
+            kw = dict(verts=_p(self.verts), vptr=_p(self.vptr), M=len(self), n_verts=self.verts.shape[0])
+            if faces:
+                kw.update(faces=_p(self.faces), fptr=_p(self.fptr), n_faces=self.faces.shape[0])
+            if maxima:
+                kw.update(max_verts=max(self.n_verts))
+            if maxima and faces:
+                kw.update(max_faces=max(self.n_faces))
+            self._fields[(faces, maxima)] = kw
+        return kw
 
     def area_cdf(self):
         """(sum F) float64 on the device: each mesh's cumulative triangle area over its own faces in tgp_mesh_area_cdf's fixed
@@ -1235,6 +1253,46 @@ def _mesh_jobs(meshset, job_mesh, what):
     if jm.numel() < 1:
         raise ValueError("%s: at least one job" % what)
     return jm
+
+
+def _gpu_args(who, dev, given, where="the mesh set's device"):
+    """every (tensor, name, dtype) of ``given`` is a contiguous GPU tensor of that dtype on ``dev``"""
+    for t, name, dt in given:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise TypeError("%s: %s must be a contiguous %s GPU tensor" % (who, name, str(dt).replace("torch.", "")))
+        if t.device != dev:
+            raise ValueError("%s: %s is not on %s" % (who, name, where))
+
+
+def _frame_jobs(who, dev, depth, camk, job_img, job_tensors, mask=None, job_mask_val=None, where="the mesh set's device"):
+    """The depth frames and the job table of pose_verify, pose_vsd and tsdf_integrate: depth (S,H,W) 16-bit and not empty, camk
+    (S,4) float32, job_img (J) int32, each (tensor, name, dtype, trailing shape[, the shape's text in the message]) of ``job_tensors``
+    a (J, ...) tensor, mask (S,H,W) uint8 with job_mask_val (J) uint8 or neither; all contiguous on ``dev``.  -> (S, H, W, J)"""
+    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in (torch.int16, torch.uint16) and depth.is_contiguous()):
+        raise TypeError("%s: depth must be a contiguous 16-bit GPU tensor" % who)
+    if (mask is None) != (job_mask_val is None):
+        raise ValueError("%s: mask and job_mask_val come together" % who)
+    given = [(depth, "depth", depth.dtype), (camk, "camk", torch.float32), (job_img, "job_img", torch.int32)] + [g[:3] for g in job_tensors]
+    if mask is not None:
+        given += [(mask, "mask", torch.uint8), (job_mask_val, "job_mask_val", torch.uint8)]
+    _gpu_args(who, dev, given, where)
+    if depth.dim() != 3 or depth.numel() == 0:
+        raise ValueError("%s: depth must be (S,H,W)" % who)
+    S, H, W = depth.shape
+    J = job_img.numel()
+    if camk.shape != (S, 4) or job_img.dim() != 1 or any(g[0].shape != (J,) + g[3] for g in job_tensors):
+        shapes = ["%s (%s)" % (g[1], g[4] if len(g) > 4 else ",".join(["J"] + ["%d" % d for d in g[3]])) for g in job_tensors]
+        raise ValueError("%s: %s are expected" % (who, ", ".join(["camk (S,4)", "job_img (J)"] + shapes)))
+    if mask is not None and (mask.shape != (S, H, W) or job_mask_val.shape != (J,)):
+        raise ValueError("%s: mask (S,H,W) and job_mask_val (J) are expected" % who)
+    return S, H, W, J
+
+
+def _workspace(dev, nbytes, who, dtype=torch.uint8):
+    """the workspace a tgp_*_workspace_bytes call asks for, in elements of ``dtype``; a negative size is that call's error code"""
+    if nbytes < 0:
+        check(nbytes, who)
+    return torch.empty(nbytes // dtype.itemsize, device=dev, dtype=dtype)
 
 
 def mesh_check_status(status, what="mesh_sample"):
@@ -1287,10 +1345,9 @@ def mesh_sample(meshset, job_mesh, n, *, u=None, keys=None, seed=0, normals=Fals
     out = {"points": torch.empty(B, n, 6 if normals else 3, device=dev, dtype=dtype), "status": torch.empty(B, device=dev, dtype=torch.int32)}
     if return_face:
         out["face"] = torch.empty(B, n, device=dev, dtype=torch.int32)
-    a = _lib.MeshSampleArgs(verts=_p(meshset.verts), faces=_p(meshset.faces), vptr=_p(meshset.vptr), fptr=_p(meshset.fptr),
-                            cdf=_p(meshset.area_cdf()), M=len(meshset), n_verts=meshset.verts.shape[0], n_faces=meshset.faces.shape[0],
-                            job_mesh=_p(jm), B=B, n=n, u=_p(u), keys=_p(kt), seed=int(seed) & (2 ** 64 - 1), normals=int(bool(normals)),
-                            f32=int(dtype == torch.float32), out=_p(out["points"]), face=_p(out.get("face")), status=_p(out["status"]))
+    a = _lib.MeshSampleArgs(cdf=_p(meshset.area_cdf()), job_mesh=_p(jm), B=B, n=n, u=_p(u), keys=_p(kt), seed=int(seed) & (2 ** 64 - 1),
+                            normals=int(bool(normals)), f32=int(dtype == torch.float32), out=_p(out["points"]), face=_p(out.get("face")),
+                            status=_p(out["status"]), **meshset.fields())
     check(_lib.lib().tgp_mesh_sample(ctypes.byref(a), _stream(meshset.verts)), "tgp_mesh_sample")
     if check_status:
         mesh_check_status(out["status"])
@@ -1334,12 +1391,9 @@ def render_depth(meshset, scene_ptr, inst_mesh, inst_id, inst_pose, camk, H, W, 
     refuse a scene above the cap."""
     if not isinstance(meshset, MeshSet):
         raise TypeError("render_depth: meshset must be an ops.MeshSet")
-    for t, name, dt in ((scene_ptr, "scene_ptr", torch.int32), (inst_mesh, "inst_mesh", torch.int32), (inst_id, "inst_id", torch.uint8),
-                        (inst_pose, "inst_pose", torch.float32), (camk, "camk", torch.float32)):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
-            raise TypeError("render_depth: %s must be a contiguous %s GPU tensor" % (name, str(dt).replace("torch.", "")))
-        if t.device != meshset.verts.device:
-            raise ValueError("render_depth: %s is not on the mesh set's device" % name)
+    _gpu_args("render_depth", meshset.verts.device, [(scene_ptr, "scene_ptr", torch.int32), (inst_mesh, "inst_mesh", torch.int32),
+                                                     (inst_id, "inst_id", torch.uint8), (inst_pose, "inst_pose", torch.float32),
+                                                     (camk, "camk", torch.float32)])
     S, I = scene_ptr.numel() - 1, inst_mesh.numel()
     H, W = int(H), int(W)
     if S < 1 or scene_ptr.dim() != 1 or camk.shape != (S, 4) or inst_mesh.dim() != 1 or inst_id.shape != (I,) or inst_pose.shape != (I, 3, 4):
@@ -1358,14 +1412,12 @@ def render_depth(meshset, scene_ptr, inst_mesh, inst_id, inst_pose, camk, H, W, 
         out["z"] = torch.empty(S, H, W, device=dev, dtype=torch.float32)
     if return_face:
         out["face"] = torch.empty(S, H, W, device=dev, dtype=torch.int32)
-    max_v, max_f = max(meshset.n_verts), max(meshset.n_faces)
-    ws = torch.empty(int(_lib.lib().tgp_render_workspace_bytes(I, max_v, max_f)), device=dev, dtype=torch.uint8)
-    a = _lib.RenderArgs(verts=_p(meshset.verts), faces=_p(meshset.faces), vptr=_p(meshset.vptr), fptr=_p(meshset.fptr), M=len(meshset),
-                        n_verts=meshset.verts.shape[0], n_faces=meshset.faces.shape[0], max_verts=max_v, max_faces=max_f,
-                        scene_ptr=_p(scene_ptr), inst_mesh=_p(inst_mesh), inst_id=_p(inst_id), inst_pose=_p(inst_pose), camk=_p(camk),
+    mesh = meshset.fields(maxima=True)
+    ws = _workspace(dev, _lib.lib().tgp_render_workspace_bytes(I, mesh["max_verts"], mesh["max_faces"]), "tgp_render_workspace_bytes")
+    a = _lib.RenderArgs(scene_ptr=_p(scene_ptr), inst_mesh=_p(inst_mesh), inst_id=_p(inst_id), inst_pose=_p(inst_pose), camk=_p(camk),
                         S=S, I=I, max_scene_inst=longest, H=H, W=W, near=float(near), workspace=_p(ws), depth=_p(out["depth"]),
                         mask=_p(out["mask"]), z=_p(out.get("z")), face=_p(out.get("face")), visible=_p(out["visible"]),
-                        bbox=_p(out["bbox"]), dropped=_p(out["dropped"]))
+                        bbox=_p(out["bbox"]), dropped=_p(out["dropped"]), **mesh)
     check(_lib.lib().tgp_render_depth(ctypes.byref(a), _stream(inst_pose)), "tgp_render_depth")
     return out
 
@@ -1390,27 +1442,8 @@ def pose_verify(meshset, depth, camk, job_img, job_mesh, job_pose, tau=5, near=0
     if not isinstance(meshset, MeshSet):
         raise TypeError("pose_verify: meshset must be an ops.MeshSet")
     dev = meshset.verts.device
-    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in (torch.int16, torch.uint16) and depth.is_contiguous()):
-        raise TypeError("pose_verify: depth must be a contiguous 16-bit GPU tensor")
-    given = [(depth, "depth", None), (camk, "camk", torch.float32), (job_img, "job_img", torch.int32), (job_mesh, "job_mesh", torch.int32),
-             (job_pose, "job_pose", torch.float32)]
-    if (mask is None) != (job_mask_val is None):
-        raise ValueError("pose_verify: mask and job_mask_val come together")
-    if mask is not None:
-        given += [(mask, "mask", torch.uint8), (job_mask_val, "job_mask_val", torch.uint8)]
-    for t, name, dt in given:
-        if dt is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
-            raise TypeError("pose_verify: %s must be a contiguous %s GPU tensor" % (name, str(dt).replace("torch.", "")))
-        if t.device != dev:
-            raise ValueError("pose_verify: %s is not on the mesh set's device" % name)
-    if depth.dim() != 3 or depth.numel() == 0:
-        raise ValueError("pose_verify: depth must be (S,H,W)")
-    S, H, W = depth.shape
-    J = job_img.numel()
-    if camk.shape != (S, 4) or job_img.dim() != 1 or job_mesh.shape != (J,) or job_pose.shape != (J, 3, 4):
-        raise ValueError("pose_verify: camk (S,4), job_img (J), job_mesh (J), job_pose (J,3,4) are expected")
-    if mask is not None and (mask.shape != (S, H, W) or job_mask_val.shape != (J,)):
-        raise ValueError("pose_verify: mask (S,H,W) and job_mask_val (J) are expected")
+    S, H, W, J = _frame_jobs("pose_verify", dev, depth, camk, job_img, [(job_mesh, "job_mesh", torch.int32, ()),
+                                                                         (job_pose, "job_pose", torch.float32, (3, 4))], mask, job_mask_val)
     if not (isinstance(tau, int) and 0 <= tau <= VERIFY_MAX_TAU):
         raise ValueError("pose_verify: tau must be an int in [0, %d] (millimetres)" % VERIFY_MAX_TAU)
     if not float(near) > 0.0:
@@ -1420,16 +1453,11 @@ def pose_verify(meshset, depth, camk, job_img, job_mesh, job_pose, tau=5, near=0
     out = {"counts": torch.empty(J, len(VERIFY_COUNTS), device=dev, dtype=torch.int32), "score": torch.empty(J, device=dev, dtype=torch.float32)}
     if J == 0:
         return out
-    max_v, max_f = max(meshset.n_verts), max(meshset.n_faces)
-    nbytes = _lib.lib().tgp_verify_workspace_bytes(J, max_v, max_f)
-    if nbytes < 0:
-        check(nbytes, "tgp_verify_workspace_bytes")
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    a = _lib.VerifyArgs(depth=_p(depth), camk=_p(camk), verts=_p(meshset.verts), faces=_p(meshset.faces), vptr=_p(meshset.vptr),
-                        fptr=_p(meshset.fptr), M=len(meshset), n_verts=meshset.verts.shape[0], n_faces=meshset.faces.shape[0],
-                        max_verts=max_v, max_faces=max_f, job_img=_p(job_img), job_mesh=_p(job_mesh), job_pose=_p(job_pose), mask=_p(mask),
+    mesh = meshset.fields(maxima=True)
+    ws = _workspace(dev, _lib.lib().tgp_verify_workspace_bytes(J, mesh["max_verts"], mesh["max_faces"]), "tgp_verify_workspace_bytes")
+    a = _lib.VerifyArgs(depth=_p(depth), camk=_p(camk), job_img=_p(job_img), job_mesh=_p(job_mesh), job_pose=_p(job_pose), mask=_p(mask),
                         job_mask_val=_p(job_mask_val), S=S, H=H, W=W, J=J, tau=tau, near=float(near), counts=_p(out["counts"]),
-                        score=_p(out["score"]), workspace=_p(ws), workspace_bytes=nbytes)
+                        score=_p(out["score"]), workspace=_p(ws), workspace_bytes=ws.numel(), **mesh)
     check(_lib.lib().tgp_pose_verify(ctypes.byref(a), _stream(job_pose)), "tgp_pose_verify")
     return out
 
@@ -1473,14 +1501,6 @@ class SymmetrySet(object):
         return np.concatenate([np.eye(3), np.zeros((3, 1))], 1)[None].astype(np.float32)
 
 
-def _gpu_args(who, dev, given):
-    for t, name, dt in given:
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
-            raise TypeError("%s: %s must be a contiguous %s GPU tensor" % (who, name, str(dt).replace("torch.", "")))
-        if t.device != dev:
-            raise ValueError("%s: %s is not on the mesh set's device" % (who, name))
-
-
 def pose_errors(meshset, job_mesh, pose_est, pose_gt, symset, job_sym, camk, near=0.01):
     """The point-based BOP pose errors of J (estimate, ground truth) pairs in one call (tgp_pose_errors, csrc/poseerr.hip;
     DESIGN.md section 3 "BOP pose errors").  Job j: the vertices of mesh job_mesh[j] of the set, pose_est[j] and pose_gt[j]
@@ -1510,14 +1530,11 @@ def pose_errors(meshset, job_mesh, pose_est, pose_gt, symset, job_sym, camk, nea
            "status": torch.empty(J, device=dev, dtype=torch.int32)}
     if J == 0:
         return out
-    nbytes = _lib.lib().tgp_pose_errors_workspace_bytes(J)
-    if nbytes < 0:
-        check(nbytes, "tgp_pose_errors_workspace_bytes")
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    a = _lib.PoseerrArgs(verts=_p(meshset.verts), vptr=_p(meshset.vptr), M=len(meshset), n_verts=meshset.verts.shape[0], sym=_p(symset.sym),
-                         sptr=_p(symset.sptr), G=len(symset), n_syms=symset.sym.shape[0], max_syms=max(symset.sizes), job_mesh=_p(job_mesh),
-                         job_sym=_p(job_sym), pose_est=_p(pose_est), pose_gt=_p(pose_gt), camk=_p(camk), J=J, near=float(near),
-                         err=_p(out["err"]), sym_best=_p(out["sym_best"]), status=_p(out["status"]), workspace=_p(ws), workspace_bytes=nbytes)
+    ws = _workspace(dev, _lib.lib().tgp_pose_errors_workspace_bytes(J), "tgp_pose_errors_workspace_bytes")
+    a = _lib.PoseerrArgs(sym=_p(symset.sym), sptr=_p(symset.sptr), G=len(symset), n_syms=symset.sym.shape[0], max_syms=max(symset.sizes),
+                         job_mesh=_p(job_mesh), job_sym=_p(job_sym), pose_est=_p(pose_est), pose_gt=_p(pose_gt), camk=_p(camk), J=J,
+                         near=float(near), err=_p(out["err"]), sym_best=_p(out["sym_best"]), status=_p(out["status"]), workspace=_p(ws),
+                         workspace_bytes=ws.numel(), **meshset.fields(faces=False))
     check(_lib.lib().tgp_pose_errors(ctypes.byref(a), _stream(pose_est)), "tgp_pose_errors")
     return out
 
@@ -1537,22 +1554,13 @@ def pose_vsd(meshset, depth, camk, job_img, job_mesh, pose_est, pose_gt, job_tau
     if not isinstance(meshset, MeshSet):
         raise TypeError("pose_vsd: meshset must be an ops.MeshSet")
     dev = meshset.verts.device
-    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in (torch.int16, torch.uint16) and depth.is_contiguous()):
-        raise TypeError("pose_vsd: depth must be a contiguous 16-bit GPU tensor")
-    if depth.device != dev:
-        raise ValueError("pose_vsd: depth is not on the mesh set's device")
-    _gpu_args("pose_vsd", dev, [(camk, "camk", torch.float32), (job_img, "job_img", torch.int32), (job_mesh, "job_mesh", torch.int32),
-                                (pose_est, "pose_est", torch.float32), (pose_gt, "pose_gt", torch.float32), (job_tau, "job_tau", torch.int32)])
-    if depth.dim() != 3 or depth.numel() == 0:
-        raise ValueError("pose_vsd: depth must be (S,H,W)")
-    S, H, W = depth.shape
-    J = job_img.numel()
-    if job_tau.dim() != 2 or not 1 <= job_tau.shape[1] <= VSD_MAX_TAUS:
+    n_tau = job_tau.shape[1] if torch.is_tensor(job_tau) and job_tau.dim() == 2 else 0                 # not a tensor: refused below
+    if torch.is_tensor(job_tau) and not 1 <= n_tau <= VSD_MAX_TAUS:
         raise ValueError("pose_vsd: job_tau must be (J, n_tau) with n_tau in [1, %d]" % VSD_MAX_TAUS)
-    n_tau = job_tau.shape[1]
-    if camk.shape != (S, 4) or job_img.dim() != 1 or job_mesh.shape != (J,) or pose_est.shape != (J, 3, 4) or pose_gt.shape != (J, 3, 4) or \
-            job_tau.shape[0] != J:
-        raise ValueError("pose_vsd: camk (S,4), job_img (J), job_mesh (J), pose_est (J,3,4), pose_gt (J,3,4), job_tau (J,n_tau) are expected")
+    S, H, W, J = _frame_jobs("pose_vsd", dev, depth, camk, job_img, [(job_mesh, "job_mesh", torch.int32, ()),
+                                                                      (pose_est, "pose_est", torch.float32, (3, 4)),
+                                                                      (pose_gt, "pose_gt", torch.float32, (3, 4)),
+                                                                      (job_tau, "job_tau", torch.int32, (n_tau,), "J,n_tau")])
     if not (isinstance(delta, int) and 0 <= delta <= 65535):
         raise ValueError("pose_vsd: delta must be an int in [0, 65535] (millimetres)")
     if not 0.0 < float(near) < float("inf"):
@@ -1563,16 +1571,11 @@ def pose_vsd(meshset, depth, camk, job_img, job_mesh, pose_est, pose_gt, job_tau
            "err": torch.empty(J, n_tau, device=dev, dtype=torch.float32)}
     if J == 0:
         return out
-    max_v, max_f = max(meshset.n_verts), max(meshset.n_faces)
-    nbytes = _lib.lib().tgp_vsd_workspace_bytes(J, max_v, max_f)
-    if nbytes < 0:
-        check(nbytes, "tgp_vsd_workspace_bytes")
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    a = _lib.VsdArgs(depth=_p(depth), camk=_p(camk), verts=_p(meshset.verts), faces=_p(meshset.faces), vptr=_p(meshset.vptr),
-                     fptr=_p(meshset.fptr), M=len(meshset), n_verts=meshset.verts.shape[0], n_faces=meshset.faces.shape[0], max_verts=max_v,
-                     max_faces=max_f, job_img=_p(job_img), job_mesh=_p(job_mesh), pose_est=_p(pose_est), pose_gt=_p(pose_gt),
+    mesh = meshset.fields(maxima=True)
+    ws = _workspace(dev, _lib.lib().tgp_vsd_workspace_bytes(J, mesh["max_verts"], mesh["max_faces"]), "tgp_vsd_workspace_bytes")
+    a = _lib.VsdArgs(depth=_p(depth), camk=_p(camk), job_img=_p(job_img), job_mesh=_p(job_mesh), pose_est=_p(pose_est), pose_gt=_p(pose_gt),
                      job_tau=_p(job_tau), S=S, H=H, W=W, J=J, n_tau=n_tau, delta=delta, near=float(near), counts=_p(out["counts"]),
-                     within=_p(out["within"]), err=_p(out["err"]), workspace=_p(ws), workspace_bytes=nbytes)
+                     within=_p(out["within"]), err=_p(out["err"]), workspace=_p(ws), workspace_bytes=ws.numel(), **mesh)
     check(_lib.lib().tgp_pose_vsd(ctypes.byref(a), _stream(pose_est)), "tgp_pose_vsd")
     return out
 
@@ -2659,15 +2662,11 @@ def pose_search(fields, job_model, clouds, counts, anchors, scales, rotations, K
         raise ValueError("pose_search: every tensor must be on one device")
     out = {"cost": torch.empty(J, top, device=dev, dtype=torch.int32), "rot": torch.empty(J, top, device=dev, dtype=torch.int32),
            "shift": torch.empty(J, top, device=dev, dtype=torch.int32), "poses": torch.empty(J, top, 3, 4, device=dev, dtype=torch.float32)}
-    nbytes = _lib.lib().tgp_pose_search_workspace_bytes(J, R)
-    if nbytes < 0:
-        check(nbytes, "tgp_pose_search_workspace_bytes")
-    table = torch.empty(J, R, 2, device=dev, dtype=torch.int32)
-    assert table.numel() * 4 == nbytes
+    table = _workspace(dev, _lib.lib().tgp_pose_search_workspace_bytes(J, R), "tgp_pose_search_workspace_bytes", torch.int32).view(J, R, 2)
     a = _lib.PoseSearchArgs(field=_p(fields.field), meta=_p(fields.meta), M=len(fields), G=fields.G, cap=fields.cap, job_model=_p(job_model),
                             clouds=_p(clouds), counts=_p(counts), anchors=_p(anchors), scales=_p(scales), J=J, n_cap=n_cap,
                             rotations=_p(rotations), R=R, K=K, stride=stride, top=top, cost=_p(out["cost"]), rot=_p(out["rot"]),
-                            shift=_p(out["shift"]), poses=_p(out["poses"]), workspace=_p(table), workspace_bytes=nbytes)
+                            shift=_p(out["shift"]), poses=_p(out["poses"]), workspace=_p(table), workspace_bytes=table.numel() * 4)
     check(_lib.lib().tgp_pose_search(ctypes.byref(a), _stream(clouds)), "tgp_pose_search")
     if return_table:
         out["table"] = table
@@ -2761,27 +2760,9 @@ def tsdf_integrate(volumes, depth, camk, job_img, job_model, job_pose, trunc_mm,
     if not isinstance(volumes, TsdfVolumes):
         raise TypeError("tsdf_integrate: volumes must be an ops.TsdfVolumes")
     dev = volumes.sum.device
-    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in (torch.int16, torch.uint16) and depth.is_contiguous()):
-        raise TypeError("tsdf_integrate: depth must be a contiguous 16-bit GPU tensor")
-    given = [(depth, "depth", None), (camk, "camk", torch.float32), (job_img, "job_img", torch.int32), (job_model, "job_model", torch.int32),
-             (job_pose, "job_pose", torch.float32)]
-    if (mask is None) != (job_mask_val is None):
-        raise ValueError("tsdf_integrate: mask and job_mask_val come together")
-    if mask is not None:
-        given += [(mask, "mask", torch.uint8), (job_mask_val, "job_mask_val", torch.uint8)]
-    for t, name, dt in given:
-        if dt is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
-            raise TypeError("tsdf_integrate: %s must be a contiguous %s GPU tensor" % (name, str(dt).replace("torch.", "")))
-        if t.device != dev:
-            raise ValueError("tsdf_integrate: %s is not on the volumes' device" % name)
-    if depth.dim() != 3 or depth.numel() == 0:
-        raise ValueError("tsdf_integrate: depth must be (S,H,W)")
-    S, H, W = depth.shape
-    J = job_img.numel()
-    if camk.shape != (S, 4) or job_img.dim() != 1 or job_model.shape != (J,) or job_pose.shape != (J, 3, 4):
-        raise ValueError("tsdf_integrate: camk (S,4), job_img (J), job_model (J), job_pose (J,3,4) are expected")
-    if mask is not None and (mask.shape != (S, H, W) or job_mask_val.shape != (J,)):
-        raise ValueError("tsdf_integrate: mask (S,H,W) and job_mask_val (J) are expected")
+    S, H, W, J = _frame_jobs("tsdf_integrate", dev, depth, camk, job_img, [(job_model, "job_model", torch.int32, ()),
+                                                                            (job_pose, "job_pose", torch.float32, (3, 4))],
+                             mask, job_mask_val, where="the volumes' device")
     import numpy as np
     trunc = np.float32(trunc_mm)
     if not (np.isfinite(trunc) and trunc > 0):
@@ -3044,12 +3025,8 @@ def _raycast_jobs(volumes, camk, job_img, job_model, job_pose, who):
     if not isinstance(volumes, TsdfVolumes):
         raise TypeError("%s: volumes must be an ops.TsdfVolumes" % who)
     dev = volumes.sum.device
-    for t, name, dt in ((camk, "camk", torch.float32), (job_img, "job_img", torch.int32), (job_model, "job_model", torch.int32),
-                        (job_pose, "job_pose", torch.float32)):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
-            raise TypeError("%s: %s must be a contiguous %s GPU tensor" % (who, name, str(dt).replace("torch.", "")))
-        if t.device != dev:
-            raise ValueError("%s: %s is not on the volumes' device" % (who, name))
+    _gpu_args(who, dev, [(camk, "camk", torch.float32), (job_img, "job_img", torch.int32), (job_model, "job_model", torch.int32),
+                         (job_pose, "job_pose", torch.float32)], where="the volumes' device")
     J = job_img.numel()
     if camk.dim() != 2 or camk.shape[1] != 4 or camk.shape[0] < 1 or job_img.dim() != 1 or job_model.shape != (J,) or job_pose.shape != (J, 3, 4):
         raise ValueError("%s: camk (S,4), job_img (J), job_model (J), job_pose (J,3,4) are expected" % who)
@@ -3274,17 +3251,14 @@ def segment_depth(depth, *, max_step=10, connectivity=4, min_pixels=50, max_segm
                                  and camk.shape == (S, 4) and camk.is_contiguous()):
         raise ValueError("segment_depth: camk must be a contiguous (S,4) float32 tensor on the depth's device")
     dev = depth.device
-    nbytes = _lib.lib().tgp_segment_workspace_bytes(S, H, W)
-    if nbytes < 0:
-        check(nbytes, "tgp_segment_workspace_bytes")
-    work = torch.empty(nbytes // 4, device=dev, dtype=torch.int32)
+    work = _workspace(dev, _lib.lib().tgp_segment_workspace_bytes(S, H, W), "tgp_segment_workspace_bytes", torch.int32)
     labels = torch.empty(S, H, W, device=dev, dtype=torch.uint8)
     info = torch.empty(S, 4, device=dev, dtype=torch.int32)
     stats = torch.empty(S, max_segments, SEG_STAT_COLS, device=dev, dtype=torch.int64)
     centers = torch.empty(S, max_segments, 3, device=dev, dtype=torch.float32) if camk is not None else None
     a = _lib.SegmentArgs(depth=_p(depth), camk=_p(camk), S=S, H=H, W=W, max_step=max_step, connectivity=int(connectivity),
                          min_pixels=min(min_pixels, 2 ** 31 - 1), max_segments=max_segments, labels=_p(labels), info=_p(info),
-                         stats=_p(stats), centers=_p(centers), workspace=_p(work), workspace_bytes=nbytes)
+                         stats=_p(stats), centers=_p(centers), workspace=_p(work), workspace_bytes=work.numel() * 4)
     check(_lib.lib().tgp_segment_depth(ctypes.byref(a), _stream(depth)), "tgp_segment_depth")
     return Segments(labels, info, stats, centers, max_step, int(connectivity), min_pixels, max_segments)
 
