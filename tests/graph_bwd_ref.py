@@ -57,12 +57,17 @@ def _dot3(d, s):
     return d[..., 0:1] * s[0] + d[..., 1:2] * s[1] + d[..., 2:3] * s[2]
 
 
-def _setup(xyz, idx, proj, sdn, C, surface):
-    """the quantities the forward, the mask and the explicit backward share, all float64"""
+def _setup(xyz, idx, proj, sdn, C, surface, rows=None):
+    """the quantities the forward, the mask and the explicit backward share, all float64.  rows (a slice of points): those points'
+    share alone -- n is then the slice's length and 'proj' holds their rows -- for forwards too large to hold whole
+    (tests/graph_fwd_ref.py); the backward needs every point."""
     xyz, sdn, idx = _up(xyz), _up(sdn), idx.detach().cpu().long()
+    own = xyz
+    if rows is not None:
+        idx, own = idx[:, rows], xyz[:, rows]
     B, n, k = idx.shape
     b = torch.arange(B).view(B, 1, 1)
-    u = xyz[b, idx] - xyz.unsqueeze(2)                               # (B, n, k, 3)
+    u = xyz[b, idx] - own.unsqueeze(2)                               # (B, n, k, 3)
     r = u.square().sum(-1, keepdim=True).sqrt()
     dirs = u / r.clamp_min(1e-12)                                    # F.normalize(u, eps=1e-12)
     raw = _dot3(dirs, sdn).view(B, n, k, S, C)                       # theta before the ReLU
@@ -71,10 +76,11 @@ def _setup(xyz, idx, proj, sdn, C, surface):
     if surface:
         sup, val = None, th
     else:
-        sup = _up(proj)[..., C:].reshape(B, n, S, C)[b, idx]        # (B, n, k, S, C)
+        sup = _up(proj)[..., C:].reshape(B, -1, S, C)[b, idx]       # (B, n, k, S, C)
         val = th * sup
+    own_proj = None if surface else (_up(proj) if rows is None else _up(proj)[:, rows])
     return dict(xyz=xyz, sdn=sdn, idx=idx, u=u, r=r, dirs=dirs, raw=raw, absth=absth, th=th, sup=sup, val=val, B=B, n=n, k=k, C=C,
-                surface=surface, proj=None if surface else _up(proj))
+                surface=surface, proj=own_proj)
 
 
 def hs_forward(xyz, idx, proj, sdn, C, surface=False):
