@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define TGP_ABI_VERSION 8
+#define TGP_ABI_VERSION 9
 #define TGP_EINVAL (-1)       /* null pointer / non-positive size / misaligned stride */
 #define TGP_EUNSUPPORTED (-2) /* shape outside what the kernels are built for */
 
@@ -61,16 +61,10 @@ int tgp_knn_xyz(const float *xyz, int B, int n, int k, int32_t *idx, tgp_stream_
 int64_t tgp_knn_feat_workspace_bytes(int B, int n, int d);
 
 /* gcn3d.py:14-23 get_neighbor_index in feature space (mode 'RF-F', gcn3d.py:149,201-206).
- * feat (B,n,d) with row stride ld; d a multiple of 32, d <= 480. */
+ * feat (B,n,d) with row stride ld; d a multiple of 32, d <= 480.
+ * (ABI 9) The variant of this call that took a kernel form from the caller is removed: the library has one kernel per shape. */
 int tgp_knn_feat(const float *feat, int ld, int B, int n, int d, int k, int32_t *idx, void *workspace,
                  int64_t workspace_bytes, tgp_stream_t stream);
-/* (ABI 5) the same with the kernel form chosen by the caller -- 0: the library's choice; 1: 32-row blocks, one workgroup per CU
- * (v_mfma_f32_32x32x2_f32); 2: 16-row blocks, two workgroups per CU whose distance and selection phases overlap
- * (v_mfma_f32_16x16x4_f32, the same ascending-k chain); 3 (ABI 7): the 16-row arithmetic on producer / consumer waves of one 512-thread
- * workgroup per CU over a double-buffered LDS image (half of the waves multiply block j + 1 while the other half select block j):
- * the library's choice where a workgroup gets at least four row blocks to walk.  Identical index lists; a measurement / test handle. */
-int tgp_knn_feat_form(const float *feat, int ld, int B, int n, int d, int k, int32_t *idx, void *workspace, int64_t workspace_bytes,
-                      int form, tgp_stream_t stream);
 /* (ABI 6) tgp_knn_feat that also leaves, beside each list, the unit directions from the point to its selected neighbours in the
  * level's coordinates xyz (B, n, 3) (gcn3d.py:48-58 get_neighbor_direction_norm): dirs (B, n, k) float4 = (x, y, z, 0), 16-byte
  * aligned -- what tgp_gconv_hs_fwd_dirs takes, so the graph convolution that walks the list needs no direction launch.  The fused

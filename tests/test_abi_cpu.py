@@ -92,7 +92,7 @@ def test_every_constant_matches_the_compilers_value(c_view):
     assert consts == _lib.CONSTANTS and len(consts) >= 46
     for name, v in consts.items():
         assert getattr(_lib, name) == v, name
-    assert _lib.ABI_VERSION == 8 and _lib.EINVAL == -1 and _lib.EUNSUPPORTED == -2
+    assert _lib.ABI_VERSION == 9 and _lib.EINVAL == -1 and _lib.EUNSUPPORTED == -2
     assert sorted(_lib.PD_STATUS) == list(range(1, 9)) and sorted(_lib._ERR) == [-2, -1]
     assert all(("TGP_PD_" + n[3:]) in _lib.PD_STATUS[v] for n, v in consts.items() if n.startswith("PD_E"))
 
@@ -130,6 +130,7 @@ def test_c_abi_exports_every_declared_symbol():
     handle = _lib.lib()                                # dlopen + symbol lookup for each; raises if one is missing
     for n in names:
         assert hasattr(handle, n)
+    assert not hasattr(handle, "tgp_knn_feat_form")
     assert handle.tgp_version() == _lib.ABI_VERSION
     assert handle.tgp_knn_max_points() >= 1028 and handle.tgp_knn_max_k() >= 20
 

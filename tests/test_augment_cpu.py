@@ -180,7 +180,7 @@ def test_augment_abi_refuses_bad_arguments_without_launching():
     """host-side checks only: every call below returns TGP_EINVAL before anything reaches a device (none is needed here)"""
     from tgpose_amd import _lib
     lib = _lib.lib()
-    assert lib.tgp_version() == 8 == _lib.ABI_VERSION
+    assert lib.tgp_version() == 9 == _lib.ABI_VERSION
     assert lib.tgp_augment_max_points() == 2048
     fake = 1 << 20                      # never dereferenced: each call fails a host check
 

@@ -22,7 +22,7 @@ def test_header_declares_and_library_exports_the_entry_points():
     for name in ("tgp_pose_errors", "tgp_pose_errors_workspace_bytes", "tgp_pose_vsd", "tgp_vsd_workspace_bytes"):
         assert name in _lib.SIGNATURES, name
         assert getattr(handle, name) is not None
-    assert _lib.ABI_VERSION == 8 and "tgp_poseerr_args" in _lib.STRUCTS and "tgp_vsd_args" in _lib.STRUCTS
+    assert _lib.ABI_VERSION == 9 and "tgp_poseerr_args" in _lib.STRUCTS and "tgp_vsd_args" in _lib.STRUCTS
     assert [f[0] for f in _lib.PoseerrArgs._fields_] == [
         "verts", "vptr", "M", "n_verts", "sym", "sptr", "G", "n_syms", "max_syms", "job_mesh", "job_sym", "pose_est", "pose_gt", "camk", "J",
         "near", "err", "sym_best", "status", "workspace", "workspace_bytes"]

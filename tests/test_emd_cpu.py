@@ -120,7 +120,7 @@ def test_emd_abi():
     """the caps, and argument errors launch nothing (no GPU is touched); tests/test_abi_cpu.py holds the symbols against the header"""
     from tgpose_amd import _lib
     lib = _lib.lib()
-    assert lib.tgp_version() == 8 and _lib.ABI_VERSION == 8
+    assert lib.tgp_version() == 9 and _lib.ABI_VERSION == 9
     cap = lib.tgp_emd_max_points()
     assert cap >= 2048
     assert lib.tgp_emd_workspace_bytes(32, cap) >= 0

@@ -72,7 +72,7 @@ def test_fps_abi():
     """the cap, and argument errors launch nothing (no GPU is touched); tests/test_abi_cpu.py holds the symbols against the header"""
     from tgpose_amd import _lib, ops
     lib = _lib.lib()
-    assert lib.tgp_version() == 8 and _lib.ABI_VERSION == 8
+    assert lib.tgp_version() == 9 and _lib.ABI_VERSION == 9
     cap = lib.tgp_fps_max_points()
     assert cap >= 8192 and ops.fps_max_points() == cap
     buf = (ctypes.c_float * 64)()

@@ -73,7 +73,7 @@ def test_header_and_library_declare_icp():
     handle = ctypes.CDLL(_lib.LIB_PATH)                                          # the built library exports them (host calls only)
     assert hasattr(handle, "tgp_icp_refine")
     assert _lib.lib().tgp_icp_max_points() == 2048
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     # argument errors are answered before anything touches a device
     a = _lib.IcpArgs()
     assert _lib.lib().tgp_icp_refine(ctypes.byref(a), None) == _lib.EINVAL

@@ -67,7 +67,7 @@ def test_new_symbols_are_declared_bound_and_exported():
     """the ABI number and the mesh constants against the NumPy restatement's; tests/test_abi_cpu.py holds every symbol, type and value
     against the header"""
     from tgpose_amd import _lib
-    assert _lib.lib().tgp_version() == _lib.ABI_VERSION == 8
+    assert _lib.lib().tgp_version() == _lib.ABI_VERSION == 9
     assert {k: v for k, v in _lib.CONSTANTS.items() if k.startswith("MESH_")} == {"MESH_SITE": 8, "MESH_AREA_CHUNK": 64}
     assert _lib.MESH_SITE == mr.SITE == 8 and _lib.MESH_AREA_CHUNK == mr.CHUNK == 64
     assert _lib.MESH_SITE == _lib.SITE_SHUFFLE + 1                              # the next free draw site

@@ -92,7 +92,7 @@ def test_h2_takes_h1_range_and_empty_dimension_is_zero():
 def test_pd_abi_refuses_bad_arguments_without_launching():
     from tgpose_amd import _lib
     lib = _lib.lib()
-    assert lib.tgp_version() == 8 and lib.tgp_pd_max_points() == 1024 and lib.tgp_pd_workspace_bytes() > 0
+    assert lib.tgp_version() == 9 and lib.tgp_pd_max_points() == 1024 and lib.tgp_pd_workspace_bytes() > 0
     fake = 1 << 20
 
     def args(**kw):

@@ -21,7 +21,7 @@ def test_header_declares_and_library_exports_the_entry_points():
     for name in NAMES:
         assert name in _lib.SIGNATURES, name
         assert getattr(handle, name) is not None
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     assert "tgp_plane_fit_args" in _lib.STRUCTS
     fields = [f[0] for f in _lib.PlaneFitArgs._fields_]
     assert fields == ["depth", "camk", "keys", "seed", "S", "H", "W", "hypotheses", "tol", "refine_iters", "min_inliers", "plane", "info", "counts"]

@@ -124,7 +124,7 @@ def test_ranger_abi_refuses_bad_arguments_without_launching():
     """host-side checks only: every call below returns TGP_EINVAL before anything reaches a device (none is needed here)"""
     from tgpose_amd import _lib
     lib = _lib.lib()
-    assert lib.tgp_version() == 8 == _lib.ABI_VERSION
+    assert lib.tgp_version() == 9 == _lib.ABI_VERSION
     fake = 1 << 20                      # never dereferenced: the plan is host-only
 
     def table(**kw):

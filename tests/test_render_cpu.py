@@ -105,7 +105,7 @@ def test_render_abi():
     against the header"""
     from tgpose_amd import _lib, ops
     lib = _lib.lib()
-    assert lib.tgp_version() == 8 and _lib.ABI_VERSION == 8
+    assert lib.tgp_version() == 9 and _lib.ABI_VERSION == 9
     assert lib.tgp_render_max_faces() == 1 << 24 and lib.tgp_render_max_instances() == 255
     assert ops.render_max_faces() == 1 << 24 and ops.render_max_instances() == 255
     assert lib.tgp_render_workspace_bytes(3, 100, 200) >= 3 * (100 * 16 + 200 * 8 + 16)

@@ -26,7 +26,7 @@ def test_header_declares_and_library_exports_the_entry_points():
     for name in NAMES:
         assert name in _lib.SIGNATURES, name
         assert getattr(handle, name) is not None
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     assert "tgp_verify_args" in _lib.STRUCTS
     assert [f[0] for f in _lib.VerifyArgs._fields_] == FIELDS
     assert _lib.SIGNATURES["tgp_verify_workspace_bytes"] == (ctypes.c_int64, [ctypes.c_int] * 3)

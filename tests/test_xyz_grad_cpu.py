@@ -13,7 +13,7 @@ def test_bad_arguments_return_negative_without_launch():
     launch (the pointers below are never dereferenced: every check runs on the host first)"""
     import ctypes
     lib = _lib.lib()
-    assert lib.tgp_version() == _lib.ABI_VERSION == 8
+    assert lib.tgp_version() == _lib.ABI_VERSION == 9
     P = ctypes.c_void_p(256)                    # a non-null dummy: the calls must return before anything reads it
     assert lib.tgp_gconv_dirgrad(None, None, None, 0, None, None, 0, None, 1, 1, 1, 7, 128, None, None) == -1
     assert lib.tgp_gconv_dirgrad(P, P, None, 0, P, P, 64, None, 1, 1, 20, 7, 128, P, None) == -1           # ldg < C

@@ -9,8 +9,10 @@
 // Selection: one 64-lane wavefront per query row.  Each lane keeps n/64 candidate distances in
 // registers; k+1 rounds of (lane-local min, 6-step butterfly argmin over the wave, retire the
 // winner) emit the neighbours in ascending (distance, index) order.  No N x N matrix exists for
-// the 3-d case (the object's cloud sits in LDS as float4 {x,y,z,|p|^2}); the feature-space case
-// reads rows of a distance matrix produced by the MFMA GEMM (gemm.hip, DIST epilogue).
+// the 3-d case (the object's cloud sits in LDS as float4 {x,y,z,|p|^2}) nor for the feature-space
+// case at d = 128 / 256 (knn_feat_fused16_kernel: a block of rows' distances in LDS, selected by
+// rank counting); other feature widths read rows of a distance matrix produced by the MFMA GEMM
+// (gemm.hip, DIST epilogue).
 #include <stdlib.h>
 
 #include "tgp_common.h"
@@ -296,7 +298,7 @@ __device__ __forceinline__ uint32_t wave_umax(uint32_t v)
     return a > b ? a : b;
 }
 
-// Top-(k+1) of one row WITHOUT a serial chain of k+1 wave reductions (the fused feature-space kernel's consumers run one wave
+// Top-(k+1) of one row WITHOUT a serial chain of k+1 wave reductions (the fused feature-space kernel selects with two waves
 // per SIMD: a chain of dependent cross-lane steps would leave the vector pipe idle most of the time).  key[t] is the
 // order-preserving key of candidate lane + 64 t; the order is (key, index), as in wave_select.
 //   1. every lane takes the minimum of its own keys; its rank among the 64 lane minima is a count of smaller ones (the minima
@@ -305,23 +307,20 @@ __device__ __forceinline__ uint32_t wave_umax(uint32_t v)
 //      k + 1 nearest; on average ~26 of the 1028 candidates survive;
 //   3. the survivors are compacted into a per-wave list in LDS (ballot prefix sums), lane l takes survivor l and counts the
 //      survivors that precede it in (key, index) order: that count is its rank; ranks 1 .. k are written out.
-// Returns false (wave-uniform, nothing written) if more than 64 candidates survive; the caller then runs wave_select.
-// (round 5) slot / nbr (may be NULL): the list entry this LANE wrote -- slot in [0, k), its neighbour's id -- or slot = -1: the caller that
+// Returns false (wave-uniform, nothing written) if more than 64 candidates survive; the caller then runs wave_select_serial_keys.
+// slot / nbr (may be NULL): the list entry this LANE wrote -- slot in [0, k), its neighbour's id -- or slot = -1: the caller that
 // goes on to use the list (the neighbour directions) has it in registers and need not wait for its own stores and read them back.
-// (round 5) The compiler turned the first form's booleans into 64-bit lane masks in scalar registers: every (key, index) comparison was
-// three vector compares, two scalar mask operations and a select, every conditional list write a save / restore of the execution
-// mask -- ~110 mask operations and ~120 hazard no-ops per row, each a round trip between the vector and the scalar unit on a wave that
-// runs alone: ~10 k cycles per row (scripts/knn_pc_stamps.py), which -- not the matrix pipe -- bounded the fused kernels.  Now an entry is
-// ONE 64-bit integer (key << 32 | index): a comparison is v_cmp_lt_u64 + add-with-carry; and every candidate is WRITTEN, a survivor to
-// its place in the list, the others to a scratch entry of the lane's own (no execution-mask changes).  Same comparisons, same lists.
+// An entry is ONE 64-bit integer (key << 32 | index), so a (key, index) comparison is v_cmp_lt_u64 + add-with-carry; and every
+// candidate is WRITTEN, a survivor to its place in the list, the others to a scratch entry of the lane's own.  Written with
+// booleans -- separate key and index compares, conditional list writes -- the compiler keeps them as 64-bit lane masks in scalar
+// registers: ~110 mask operations, execution-mask saves / restores and ~120 hazard no-ops per row, each a round trip between the
+// vector and the scalar unit (~10 k cycles per row measured), which -- not the matrix pipe -- then bounds the fused kernel.
 #define KNN_LIST 136                       // entries per wave: 64 survivors + 8 sentinels, then one scratch entry per lane
 template <int NT>
 __device__ __forceinline__ bool wave_select_ranked(const uint32_t (&key)[NT], int lane, int k, int32_t *__restrict__ out_row,
                                                    uint32_t *__restrict__ lmin, uint2 *__restrict__ list /* KNN_LIST entries, 16-byte aligned */,
-                                                   int *slot = nullptr, int *nbr = nullptr, unsigned long long *ph = nullptr)
+                                                   int *slot = nullptr, int *nbr = nullptr)
 {
-#define KNN_PH(I) do { if (ph) { const unsigned long long t_ = __builtin_readcyclecounter(); ph[I] += t_ - ph[5]; ph[5] = t_; } } while (0)
-    if (ph) ph[5] = __builtin_readcyclecounter();
     uint32_t mn = key[0];
 #pragma unroll
     for (int t = 1; t < NT; ++t) mn = key[t] < mn ? key[t] : mn;
@@ -334,7 +333,6 @@ __device__ __forceinline__ bool wave_select_ranked(const uint32_t (&key)[NT], in
         rank += (v.x < mn) + (v.y < mn) + (v.z < mn) + (v.w < mn);
     }
     const uint32_t tau = wave_umax(rank <= k ? mn : 0u);
-    KNN_PH(0);
     int cnt = 0;
 #pragma unroll
     for (int t = 0; t < NT; ++t) cnt += key[t] <= tau;
@@ -350,7 +348,6 @@ __device__ __forceinline__ bool wave_select_ranked(const uint32_t (&key)[NT], in
         pos += (int)(__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))) << bit;
         total += __popcll(m) << bit;
     }
-    KNN_PH(1);
     if (total > 64) return false;                                     // wave-uniform
     // an entry = (index, key) as it lies: read as one 64-bit integer it is key << 32 | index, the (key, index) order
     unsigned long long *list64 = reinterpret_cast<unsigned long long *>(list);
@@ -362,7 +359,6 @@ __device__ __forceinline__ bool wave_select_ranked(const uint32_t (&key)[NT], in
     }
     if (lane < 8) list64[total + lane] = ~0ull;                       // sentinels: the rank loop reads whole groups of 8
     __builtin_amdgcn_s_waitcnt(0xc07f);
-    KNN_PH(2);
     const unsigned long long mine = list64[lane < total ? lane : 0];
     int r = 0;
     for (int j = 0; j < total; j += 8) {                              // wave-uniform trip count; broadcast reads, issued together
@@ -375,8 +371,6 @@ __device__ __forceinline__ bool wave_select_ranked(const uint32_t (&key)[NT], in
     const bool has = lane < total && r >= 1 && r <= k;
     if (has) out_row[r - 1] = (int32_t)(uint32_t)mine;
     if (slot) *slot = has ? r - 1 : -1, *nbr = (int)(uint32_t)mine;
-    KNN_PH(3);
-#undef KNN_PH
     return true;
 }
 
@@ -543,21 +537,36 @@ __global__ __launch_bounds__(256) void sqnorm_aten_kernel(const float *__restric
 }
 
 // ------------------------------------------------------------------------------------------------
-// Feature-space kNN WITHOUT the (B, n, n) matrix (gcn3d.py:14-23 with d = 128 / 256).  One 512-thread workgroup per 32-row
-// block of an object's distance matrix, two phases:
-//   1. all eight waves compute the block's 32 x n distances on the fp32 matrix cores -- the block's own 32 feature rows stay
-//      in registers as the A operand (lane (r, h) holds x[i0 + r][2 s + h] for every MFMA step s), the object's other rows
-//      stream past as the B operand straight from the XCD's L2 (an object's features are 0.5 MB; all its row blocks run on one
-//      XCD), prefetched one chunk ahead -- in the same ascending-k FMA chain and the same three roundings as the stored-matrix
-//      form (bit-identical distances), and leave them in LDS (32 x n floats, 135 KB at n = 1028);
-//   2. every wave takes four rows out of LDS and selects their k + 1 nearest by (distance, index) with wave_select_ranked.
+// Feature-space kNN WITHOUT the (B, n, n) matrix (gcn3d.py:14-23 with d = 128 / 256).  One 256-thread workgroup per 16-row block
+// of an object's distance matrix, two phases:
+//   1. the four waves compute the block's 16 x n distances on the fp32 matrix cores (v_mfma_f32_16x16x4_f32) and leave them in LDS
+//      (16 x ldw floats, <= 74 KB: TWO workgroups per CU);
+//   2. every wave takes four rows out of LDS and selects their k + 1 nearest by (distance, index): wave_select_ranked, and
+//      wave_select_serial_keys for the rare row that leaves more than 64 candidates under its bound.
 // The distances never leave the CU: HBM sees the features once (16.8 MB at B = 32, n = 1028, d = 128) and the index lists
-// (2.6 MB) instead of 2 x 135 MB of matrix.
-// Tail rows.  The LDS block admits one workgroup per CU, so the launch runs in rounds of 256 row blocks, and the network's
-// clouds are 32 m + 4 (1028) or 32 m + 1 (257) rows: a 33rd / 9th block per object with 4 / 1 live rows cost a whole extra
-// round (1056 blocks = 4.1 rounds, 288 = 1.1).  When the tail is that short (n_extra <= 8 rows) those rows ride along instead:
-// block rb < n_extra also takes row 32 * nrb + rb, its distances computed on the vector pipe (the same ascending-k FMA chain,
-// one column per thread and pass) into a 33rd LDS row, selected by wave 7 after its four rows.
+// (2.6 MB) instead of 2 x 135 MB of matrix.  Phase 1 idles the vector pipe and phase 2 the matrix cores; the two workgroups of a
+// CU are independent and drift apart by themselves, one selecting while the other multiplies.
+// Operands.  xt is the object's features transposed, (B, DIM, ldw) with ldw = 32 ceil(n / 32) columns, zero beyond n (knn_prep*):
+// loads then run along the points -- whole 128-byte lines -- where a row-major operand would make every lane walk its own row
+// (one line touched per lane and load for a few useful bytes: the vector-memory pipe, not the matrix cores, then sets the pace).
+// A = the block's 16 rows, one float per lane and step, in registers for the whole phase: lane (c, g) holds x[i0 + c][4 s + g] for
+// every MFMA step s.  B = the object's other rows, streamed from the XCD's L2 (an object's features are 0.5 MB; all its row blocks
+// run on one XCD) three chunks of CH steps ahead of the MFMAs (a chunk is ~0.3 us of matrix work against ~1 us of loaded L2
+// latency), four column sets at once: lane (c, g) loads the float4 xt[4 s + g][64 grp + 4 c ..+3] (a wave-instruction reads four
+// 256-byte runs), component j being column 64 grp + 4 c + j of set j.  Every wave so keeps four independent accumulator chains,
+// enough to fill the matrix pipe of its SIMD alone.
+// Arithmetic.  In step s lane (c, g) supplies k = 4 s + g of row / column c, and the matrix core adds the four products to the
+// accumulator in ascending k with one rounding each: over the steps, the ascending-k FMA chain from 0 that bmm computes.  Then
+// the same three roundings as the stored-matrix path (gemm.hip, DIST epilogue) and the oracle: inner * -2, + |x_j|^2, + |x_i|^2.
+// The distances carry the oracle's bits, so the neighbour order is the oracle's.
+// Tail rows.  The network's clouds are 16 m + 4 (1028) or 16 m + 1 (257) rows, and a last block with 4 / 1 live rows per object is a
+// whole extra round of workgroups (2080 = 4.06 rounds of 512 slots; 544 = 1.06).  A tail of at most 8 rows (and no more than there
+// are full blocks) rides along instead: block rb < n_extra also takes row 16 nrb + rb, its distances computed on the vector pipe
+// (the same ascending-k FMA chain) by waves 1-3 -- which have one column group less than wave 0 -- into a 17th LDS row that wave 3
+// selects after its four.
+// (Measured and dropped: a start skew -- the workgroups of the launch's second half-round, i.e. the second slot of every CU, pausing for
+// about one selection phase once, so that the two workgroups of a CU would not run their phases in step: 18.92 k against 18.97 k
+// objects/s without it, two runs each on one box.)
 #ifdef TGP_DEV   // development build: rows whose rank-counting selection met more than 64 survivors and took the serial form
 __device__ unsigned long long tgp_knn_serial_rows = 0ull;
 extern "C" int tgp_debug_knn_serial_rows(unsigned long long *out, int reset)
@@ -571,168 +580,21 @@ extern "C" int tgp_debug_knn_serial_rows(unsigned long long *out, int reset)
 #else
 #define KNN_COUNT_SERIAL() do { } while (0)
 #endif
-typedef float knn_f32x16 __attribute__((ext_vector_type(16)));
-
-#define KF_ROWS 32
-#define KF_MAX_LDW 1152      // 33 x 1152 x 4 B = 148.5 KiB of LDS (+ 6.5 KiB of selection scratch)
-
-// xt: the object's features transposed, (B, DIM, ldw) with ldw = 32 * ncb columns (zero beyond n): lane (r, h) of a 32-wide
-// block then reads xt[k = 2 s + h][32 cb + r] -- 32 consecutive floats per half wave, a fully used 128-byte line -- where a
-// row-major operand would make every lane walk its own row (32 lines touched per load instruction for 16 useful bytes each;
-// measured: the vector-memory pipe, not the matrix cores, then sets the pace: 43 instead of 18 us per row block).
-template <int DIM, int NT, int CH>   // CH: MFMA steps (k pairs) per prefetched chunk
-__global__ __launch_bounds__(512, 2) void knn_feat_fused_kernel(const float *__restrict__ xt, const float *__restrict__ q, int B, int n, int k,
-                                                                int32_t *__restrict__ idx, int nrb, int ncb, int ldw, int n_extra,
-                                                                unsigned long long *stamps)
-{
-    extern __shared__ __attribute__((aligned(16))) float dblk[];      // [32 (+ 1 with tail rows)][ldw]
-    __shared__ uint32_t s_lmin[8][64];
-    __shared__ __attribute__((aligned(16))) uint2 s_list[8][KNN_LIST];
-    constexpr int STEPS = DIM / 2;                                    // MFMA steps per column block (k pairs)
-    constexpr int NCHUNK = STEPS / CH;
-    constexpr int RING = 4;                                           // B-operand chunks in flight: three ahead of the MFMAs
-    static_assert(NCHUNK % RING == 0, "the chunk ring's phase must repeat per column block");
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    int b, rb;
-    if (!tgp_xcd_object_tile(blockIdx.x, B, nrb, b, rb)) return;
-    const int i0 = rb * KF_ROWS;
-    const bool has_extra = rb < n_extra;                              // workgroup-uniform
-    const int ix = nrb * KF_ROWS + rb;                                // the tail row this block takes along
-    const float *xb = xt + (size_t)b * DIM * ldw + (size_t)h * ldw + r;      // + 2 s ldw + 32 cb: the lane's element of step s, block cb
-    const float *qb = q + (size_t)b * n;
-    // development builds: 12 stamps per workgroup -- start, wave 0's phase 1 end, after the barrier, end; then each wave's phase-1 end
-    unsigned long long *st = (stamps && threadIdx.x == 0) ? stamps + 12 * (size_t)blockIdx.x : nullptr;
-    if (st) st[0] = __builtin_amdgcn_s_memrealtime();
-    {
-        // ---- phase 1: distances of rows [i0, i0 + 32) against the column blocks cb = wave, wave + 8, ...
-        float a[STEPS];
-#pragma unroll
-        for (int s2 = 0; s2 < STEPS; ++s2) a[s2] = xb[(size_t)2 * s2 * ldw + i0];
-        float qrow[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) qrow[e] = qb[min(i0 + (e & 3) + 8 * (e >> 2) + 4 * h, n - 1)];
-        // a chunk of CH MFMA steps is CH x 64 cycles of matrix work (0.27 us at CH = 8) against ~1 us of loaded L2 latency: with one
-        // chunk of lookahead the matrix cores waited for operands 40 % of this phase; three chunks ahead they do not
-        float buf[RING][CH];
-        auto fetch = [&](int cb, int c, float (&dst)[CH]) {
-            const float *br = xb + (size_t)2 * c * CH * ldw + cb * 32;
-#pragma unroll
-            for (int t = 0; t < CH; ++t) dst[t] = br[(size_t)2 * t * ldw];
-        };
-        if (wave < ncb) {
-#pragma unroll
-            for (int c = 0; c < RING - 1; ++c) fetch(wave, c, buf[c]);
-        }
-        for (int cb = wave; cb < ncb; cb += 8) {
-            knn_f32x16 acc;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-            for (int c = 0; c < NCHUNK; ++c) {                        // compile-time chunk index: a[] and the ring stay in registers
-                constexpr int AHEAD = RING - 1;
-                if (c + AHEAD < NCHUNK) fetch(cb, c + AHEAD, buf[(c + AHEAD) % RING]);
-                else if (cb + 8 < ncb) fetch(cb + 8, c + AHEAD - NCHUNK, buf[(c + AHEAD) % RING]);   // NCHUNK % RING == 0: same slot
-#pragma unroll
-                for (int t = 0; t < CH; ++t)                          // ascending k: step s = c CH + t takes k = 2 s + h
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c * CH + t], buf[c % RING][t], acc, 0, 0, 0);
-            }
-            const int col = cb * 32 + r;
-            const float qc = qb[min(col, n - 1)];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = (e & 3) + 8 * (e >> 2) + 4 * h;
-                const float t1 = acc[e] * -2.0f;                      // inner * (-2)
-                const float t2 = t1 + qc;                             // + quadratic.unsqueeze(1)
-                dblk[row * ldw + col] = col < n ? t2 + qrow[e] : INFINITY;           // + quadratic.unsqueeze(2)
-            }
-        }
-    }
-    if (has_extra && wave != 0) {
-        // the tail row against every column: inner = x[0] y[0], then fmaf in ascending k -- what the MFMA chain computes.  Done by
-        // waves 1-7, which have one column block less than wave 0 (33 = 8 x 4 + 1): three columns per thread, their chains
-        // interleaved so that 48 loads are in flight, in the shadow of wave 0's fifth block
-        const float *xo = xt + (size_t)b * DIM * ldw;
-        const float qx = qb[ix];
-        const int t0 = (wave - 1) * 64 + lane;
-        for (int cbase = t0; cbase < ldw; cbase += 3 * 448) {
-            const int c0 = cbase, c1 = cbase + 448, c2 = cbase + 896;
-            const int l0 = c0, l1 = min(c1, ldw - 1), l2 = min(c2, ldw - 1);
-            const float x0 = xo[ix];
-            float in0 = x0 * xo[l0], in1 = x0 * xo[l1], in2 = x0 * xo[l2];
-#pragma unroll 16
-            for (int kk = 1; kk < DIM; ++kk) {
-                const float xv = xo[(size_t)kk * ldw + ix];
-                in0 = fmaf(xv, xo[(size_t)kk * ldw + l0], in0);
-                in1 = fmaf(xv, xo[(size_t)kk * ldw + l1], in1);
-                in2 = fmaf(xv, xo[(size_t)kk * ldw + l2], in2);
-            }
-            auto put = [&](int col, float inner) {
-                if (col < ldw) {
-                    const float t1 = inner * -2.0f;
-                    const float t2 = t1 + qb[min(col, n - 1)];
-                    dblk[KF_ROWS * ldw + col] = col < n ? t2 + qx : INFINITY;
-                }
-            };
-            put(c0, in0), put(c1, in1), put(c2, in2);
-        }
-    }
-    if (st) st[1] = __builtin_amdgcn_s_memrealtime();
-    if (stamps && lane == 0) stamps[12 * (size_t)blockIdx.x + 4 + wave] = __builtin_amdgcn_s_memrealtime();
-    __syncthreads();
-    if (st) st[2] = __builtin_amdgcn_s_memrealtime();
-    // ---- phase 2: four rows per wave
-#pragma unroll 1
-    for (int rr = 0; rr < 5; ++rr) {
-        if (rr == 4 && !(has_extra && wave == 7)) break;              // wave-uniform: the tail row is wave 7's fifth
-        const int lrow = rr == 4 ? KF_ROWS : wave * 4 + rr, i = rr == 4 ? ix : i0 + lrow;
-        if (i >= n) break;                                            // wave-uniform
-        uint32_t key[NT];
-        const float *row = dblk + lrow * ldw;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int j = lane + (t << 6);
-            key[t] = tgp_float_key(j < n ? row[j] : INFINITY);
-        }
-        int32_t *out = idx + ((size_t)b * n + i) * k;
-        if (!wave_select_ranked<NT>(key, lane, k, out, s_lmin[wave], s_list[wave]))
-            wave_select_serial_keys<NT>(key, lane, k, out);           // more than 64 candidates under the bound (rare)
-    }
-    if (st) st[3] = __builtin_amdgcn_s_memrealtime();
-}
-
-// ------------------------------------------------------------------------------------------------
-// (round 4) The same on 16-row blocks: 256 threads, v_mfma_f32_16x16x4_f32, 16 x ldw distances in LDS (<= 74 KB) -- TWO workgroups per
-// CU.  The 32-row form holds the CU alone (135 KB of LDS) and runs its two phases one after the other: 28 us of matrix work during
-// which the vector pipe idles, 11 us of selection during which the matrix cores idle (profiles/r02_f_knn_feat_fused_*.txt).  Two
-// independent half-size workgroups drift apart by themselves, one selecting while the other multiplies; the producer / consumer split
-// INSIDE a workgroup (round 2) failed because one MFMA wave per SIMD could not feed the pipe -- here every wave keeps four
-// independent accumulator chains (four interleaved column sets), enough to fill it alone.
-// Arithmetic: lane (c, g) of the 16x16x4 instruction supplies k = 4 s + g of row / column c in step s, and the matrix core adds the
-// four products to the accumulator in ascending k with one rounding each -- the same chain as two steps of the 32x32x2 form, so the
-// distances carry the same bits (tests/test_gpu_parity.py::test_knn_feat_bit_exact_vs_oracle runs both forms).
-// Operands: A = the block's 16 rows, one float per lane and step (registers); B = four column sets at once -- lane (c, g) loads the
-// float4 xt[k][64 grp + 4 c ..+3] (a wave-instruction reads four 256-byte runs), component j being column 64 grp + 4 c + j of set j.
 typedef float knn_f32x4 __attribute__((ext_vector_type(4)));
 
 #define KF16_ROWS 16
-// Tail rows: the network's clouds are 16 m + 4 (1028) or 16 m + 1 (257) rows, and a last block with 4 / 1 live rows per object is a
-// whole extra round of workgroups (2080 = 4.06 rounds of 512 slots; 544 = 1.06).  As in the 32-row form, a short tail (n_extra <= 8
-// rows) rides along: block rb < n_extra also takes row 16 nrb + rb, its distances computed on the vector pipe (the same ascending-k
-// FMA chain) by waves 1-3 -- which have one column group less than wave 0 -- into a 17th LDS row that wave 3 selects after its four.
-// (Measured and dropped: a start skew -- the workgroups of the launch's second half-round, i.e. the second slot of every CU, pausing for
-// about one selection phase once, so that the two workgroups of a CU would not run their phases in step: 18.92 k against 18.97 k
-// objects/s without it, two runs each on one box; the workgroups drift apart by themselves within a round.)
-// (round 4) The unit directions to a row's neighbours (gcn3d.py:48-58 get_neighbor_direction_norm), for the LDS-staged graph
-// convolution that walks this list next (gconv.hip, nbr_dirs_kernel: the same arithmetic) -- written by the wave that has just
-// selected the row, instead of by a launch of its own.  The wave reads its own list back: its stores are acknowledged (vmcnt 0)
-// and the loads go past the L1 (sc1).
+// The widest cloud the fused kernel serves, in columns: n <= 1152.  It decides which shapes take the matrix path and what
+// tgp_knn_feat_workspace_bytes answers (tests/test_host_cpu.py pins both), so it is a routing constant first; the image it allows,
+// 17 x 1152 x 4 B = 76.5 KiB, fits the CU's LDS with the selection's lists beside it (static_assert at the launch).
+#define KF_MAX_LDW 1152
+
+// The unit directions to a row's neighbours (gcn3d.py:48-58 get_neighbor_direction_norm), for the LDS-staged graph convolution
+// that walks this list next (gconv.hip, nbr_dirs_kernel: the same arithmetic) -- written by the wave that has just selected the
+// row, instead of by a launch of its own, and from the selecting lane's registers (slot, nb: what wave_select_ranked hands back):
+// reading the list back costs four dependent memory round trips per row, ~5 us each, on a wave that selects four rows per block.
 __device__ __forceinline__ void knn_emit_dirs(const float *__restrict__ xyz, float4 *__restrict__ dirs, const int slot, const int nb,
                                               const int64_t rowi, const int b, const int n, const int k)
 {
-    // (round 5) from the selecting lane's registers.  Round 4 read the list back -- `s_waitcnt vmcnt(0)` for the stores' acknowledgements,
-    // then sc1 loads, then the two coordinate loads: four dependent memory round trips per row on a wave that selects four rows per
-    // block, ~5 us each -- which, not the matrix pipe, was what the kernel waited for (its selection phase took ~30 us per block).
     if (slot < 0) return;
     const float *pc = xyz + rowi * 3;
     const float *pn = xyz + ((int64_t)b * n + nb) * 3;
@@ -874,209 +736,8 @@ __global__ __launch_bounds__(256, 2) void knn_feat_fused16_kernel(const float *_
     }
 }
 
-// (round 5) The same two phases as PRODUCER and CONSUMER waves of one workgroup: 512 threads, waves 0-3 compute the distances of row block
-// j + 1 into one half of a double-buffered LDS image (2 x 17 rows x ldw: 144 KB at n = 1028) while waves 4-7 select block j from the
-// other half; one barrier per block; a workgroup walks `bpw` consecutive row blocks of one object (B x 8 workgroups for the
-// benchmark's B = 32, n = 1028: one per CU, ONE round instead of four).  Wave w and wave w + 4 share a SIMD, so every SIMD holds one
-// wave on the matrix pipe and one on the vector / LDS pipes at all times -- in the 16-row form two workgroups per CU were meant to
-// alternate like that but nothing kept them out of phase (SQ counters, round 4: matrix pipe busy 34 %).  Per element the same arithmetic
-// in the same order as knn_feat_fused16_kernel (and the same selection): the same lists, bit for bit.
-// MEASURED, NOT THE DEFAULT (scripts/knn_time.py, scripts/knn_pc_stamps.py, B = 32, n = 1028, d = 128): 255 us against 165-180 us for the
-// 16-row form.  Stamps per wave: producers 26-32 k cycles per block inside their loop, consumers 36-43 k (9-10 k per row, with a selection of
-// ~600 instructions), producers parked at the barrier for 40 % of the kernel.  The premise was wrong: the distance products are exact fp32
-// MFMAs, which run at the fp32 VECTOR rate on the lanes the selection's vector instructions need, so a selecting wave beside a multiplying
-// wave gets a fraction of the SIMD's issue slots (s_setprio 2 for the selectors: -4 %) -- the two phases do not overlap on one SIMD, they add
-// (~17 k cycles of MFMA + ~16 k of selection per block and SIMD: the 16-row form's 163 us) -- and here only four waves select instead of
-// eight.  What it did show: the selection, not the matrix pipe, is the longer half; its rewrite on 64-bit compares (wave_select_ranked)
-// took 7 % off every form.
-template <int DIM, int NT, int CH>
-__global__ __launch_bounds__(512, 2) void knn_feat_pc_kernel(const float *__restrict__ xt, const float *__restrict__ q, int B, int n, int k,
-                                                             int32_t *__restrict__ idx, int nrb, int ldw, int n_extra,
-                                                             const float *__restrict__ xyz, float4 *__restrict__ dirs, int bpw, int chunks,
-                                                             unsigned long long *stamps)
-{
-    extern __shared__ __attribute__((aligned(16))) float dpc[];       // [2][16 + 1][ldw]
-    unsigned long long t_body = 0, t_bar = 0, t_keys = 0;
-    unsigned long long ph[6] = {0, 0, 0, 0, 0, 0};
-    __shared__ uint32_t s_lmin[4][64];
-    __shared__ __attribute__((aligned(16))) uint2 s_list[4][KNN_LIST];
-    constexpr int STEPS = DIM / 4;
-    constexpr int NCHUNK = STEPS / CH;
-    constexpr int RING = 4;
-    static_assert(NCHUNK % RING == 0, "the chunk ring's phase must repeat per column group");
-    const int lane = threadIdx.x & 63, wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wave = wave8 & 3, consumer = wave8 >> 2;
-    const int c = lane & 15, g = lane >> 4;
-    int b, chunk;
-    if (!tgp_xcd_object_tile(blockIdx.x, B, chunks, b, chunk)) return;
-    const int rb0 = chunk * bpw, nb = min(nrb, rb0 + bpw) - rb0;
-    // the selecting waves are the second-dispatched half of the workgroup: at equal priority they lose the arbitration for the SIMD's issue
-    // slots against their producer partner on every instruction (micro-architecture guide, "Two waves per SIMD", item 4), and they are the
-    // longer of the two chains
-    if (consumer) __builtin_amdgcn_s_setprio(2);
-    const size_t bufsz = (size_t)(KF16_ROWS + 1) * ldw;
-    const float *qb = q + (size_t)b * n;
-    const int ngrp = (ldw + 63) >> 6;
-    const float *xo = xt + (size_t)b * DIM * ldw + (size_t)g * ldw;
-#pragma unroll 1
-    for (int it = 0; it <= nb; ++it) {
-        const unsigned long long t0 = stamps ? __builtin_readcyclecounter() : 0ull;
-        if (!consumer && it < nb) {
-            // ---- phase 1 of block rb0 + it (knn_feat_fused16_kernel's, on the same four-wave split)
-            const int rb = rb0 + it;
-            const int i0 = rb * KF16_ROWS;
-            float *dblk16 = dpc + (size_t)(it & 1) * bufsz;
-            const bool has_extra = rb < n_extra;
-            const int ix = nrb * KF16_ROWS + rb;
-            {
-                float a[STEPS];
-#pragma unroll
-                for (int s2 = 0; s2 < STEPS; ++s2) a[s2] = xo[(size_t)4 * s2 * ldw + i0 + c];
-                float qrow[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) qrow[e] = qb[min(i0 + 4 * g + e, n - 1)];
-                float4 buf[RING][CH];
-                auto fetch = [&](int grp, int cc, float4 (&dst)[CH]) {
-                    const int col = min(64 * grp + 4 * c, ldw - 4);
-                    const float *br = xo + (size_t)4 * cc * CH * ldw + col;
-#pragma unroll
-                    for (int t = 0; t < CH; ++t) dst[t] = *reinterpret_cast<const float4 *>(br + (size_t)4 * t * ldw);
-                };
-                if (wave < ngrp) {
-#pragma unroll
-                    for (int cc = 0; cc < RING - 1; ++cc) fetch(wave, cc, buf[cc]);
-                }
-                for (int grp = wave; grp < ngrp; grp += 4) {
-                    knn_f32x4 acc[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[j] = knn_f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int cc = 0; cc < NCHUNK; ++cc) {
-                        constexpr int AHEAD = RING - 1;
-                        if (cc + AHEAD < NCHUNK) fetch(grp, cc + AHEAD, buf[(cc + AHEAD) % RING]);
-                        else if (grp + 4 < ngrp) fetch(grp + 4, cc + AHEAD - NCHUNK, buf[(cc + AHEAD) % RING]);
-#pragma unroll
-                        for (int t = 0; t < CH; ++t) {                // ascending k: step s = cc CH + t takes k = 4 s + g
-                            const float av = a[cc * CH + t];
-                            const float4 bv = buf[cc % RING][t];
-                            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv.x, acc[0], 0, 0, 0);
-                            acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv.y, acc[1], 0, 0, 0);
-                            acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv.z, acc[2], 0, 0, 0);
-                            acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv.w, acc[3], 0, 0, 0);
-                        }
-                    }
-                    const int col0 = 64 * grp + 4 * c;
-                    if (col0 < ldw) {
-                        float qc[4];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) qc[j] = qb[min(col0 + j, n - 1)];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            float4 o;
-                            float *op = reinterpret_cast<float *>(&o);
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) {
-                                const float t1 = acc[j][e] * -2.0f;           // inner * (-2)
-                                const float t2 = t1 + qc[j];                  // + quadratic.unsqueeze(1)
-                                op[j] = col0 + j < n ? t2 + qrow[e] : INFINITY;   // + quadratic.unsqueeze(2)
-                            }
-                            *reinterpret_cast<float4 *>(dblk16 + (4 * g + e) * ldw + col0) = o;
-                        }
-                    }
-                }
-            }
-            if (has_extra && wave != 0) {
-                const float *xa = xt + (size_t)b * DIM * ldw;
-                const float qx = qb[ix];
-                const int t0 = (wave - 1) * 64 + lane;
-                for (int cbase = t0; cbase < ldw; cbase += 3 * 192) {
-                    const int c0 = cbase, c1 = cbase + 192, c2 = cbase + 384;
-                    const int l0 = c0, l1 = min(c1, ldw - 1), l2 = min(c2, ldw - 1);
-                    const float x0 = xa[ix];
-                    float in0 = x0 * xa[l0], in1 = x0 * xa[l1], in2 = x0 * xa[l2];
-#pragma unroll 16
-                    for (int kk = 1; kk < DIM; ++kk) {
-                        const float xv = xa[(size_t)kk * ldw + ix];
-                        in0 = fmaf(xv, xa[(size_t)kk * ldw + l0], in0);
-                        in1 = fmaf(xv, xa[(size_t)kk * ldw + l1], in1);
-                        in2 = fmaf(xv, xa[(size_t)kk * ldw + l2], in2);
-                    }
-                    auto put = [&](int col, float inner) {
-                        if (col < ldw) {
-                            const float t1 = inner * -2.0f;
-                            const float t2 = t1 + qb[min(col, n - 1)];
-                            dblk16[KF16_ROWS * ldw + col] = col < n ? t2 + qx : INFINITY;
-                        }
-                    };
-                    put(c0, in0), put(c1, in1), put(c2, in2);
-                }
-            }
-        } else if (consumer && it >= 1) {
-            // ---- phase 2 of block rb0 + it - 1: four rows per wave (wave 3: the tail row as its fifth)
-            const int rb = rb0 + it - 1;
-            const int i0 = rb * KF16_ROWS;
-            const float *dblk16 = dpc + (size_t)((it - 1) & 1) * bufsz;
-            const bool has_extra = rb < n_extra;
-            const int ix = nrb * KF16_ROWS + rb;
-#pragma unroll 1
-            for (int rr = 0; rr < 5; ++rr) {
-                if (rr == 4 && !(has_extra && wave == 3)) break;
-                const int lrow = rr == 4 ? KF16_ROWS : wave * 4 + rr, i = rr == 4 ? ix : i0 + lrow;
-                if (i >= n) break;
-                uint32_t key[NT];
-                const float *row = dblk16 + lrow * ldw;
-                const unsigned long long tk0 = stamps ? __builtin_readcyclecounter() : 0ull;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    const int j = lane + (t << 6);
-                    key[t] = tgp_float_key(j < n ? row[j] : INFINITY);
-                }
-                int32_t *out = idx + ((size_t)b * n + i) * k;
-                int slot, nb;
-                if (stamps) t_keys += __builtin_readcyclecounter() - tk0;
-                if (!wave_select_ranked<NT>(key, lane, k, out, s_lmin[wave], s_list[wave], &slot, &nb, stamps ? ph : nullptr)) {
-                    KNN_COUNT_SERIAL();
-                    wave_select_serial_keys<NT>(key, lane, k, out, &slot, &nb);
-                }
-                if (dirs) knn_emit_dirs(xyz, dirs, slot, nb, (int64_t)b * n + i, b, n, k);
-            }
-        }
-        const unsigned long long t1 = stamps ? __builtin_readcyclecounter() : 0ull;
-        __syncthreads();
-        if (stamps) t_body += t1 - t0, t_bar += __builtin_readcyclecounter() - t1;
-    }
-    if (stamps && lane == 0) {
-        stamps[(size_t)blockIdx.x * 16 + wave8 * 2] = t_body, stamps[(size_t)blockIdx.x * 16 + wave8 * 2 + 1] = t_bar;
-        if (wave8 == 5) {          // one consumer wave's phases: keys, lane minima + bound, count + prefix, compaction, ranks
-            unsigned long long *o = stamps + (size_t)gridDim.x * 16 + (size_t)blockIdx.x * 8;
-            o[0] = t_keys, o[1] = ph[0], o[2] = ph[1], o[3] = ph[2], o[4] = ph[3];
-        }
-    }
-}
-
-#ifdef TGP_DEV
-static unsigned long long *tgp_knn_stamps = nullptr;
-extern "C" void tgp_debug_set_knn_stamps(unsigned long long *buf) { tgp_knn_stamps = buf; }
-static int tgp_knn_pc_mode = 0;            // 1: the library picks the producer / consumer form where a workgroup gets >= 4 row blocks (A/B runs)
-extern "C" void tgp_debug_set_knn_pc(int v) { tgp_knn_pc_mode = v; }
-#else
-static constexpr unsigned long long *tgp_knn_stamps = nullptr;
-static constexpr int tgp_knn_pc_mode = 0;  // measured SLOWER (below): form 3 stays a test / measurement handle
-#endif
-
 // implemented in gemm.hip: D[b,i,j] = fl(fl(-2*<x_i,x_j> + q_j) + q_i), natural-k MFMA chain
 int tgp_launch_dist_gemm(const float *x, int ld, const float *q, int B, int n, int d, float *D, hipStream_t stream);
-
-// xt[b][c][j] = x[b][j][c] for j < n, 0 for n <= j < ldt (32 x 32 tiles through LDS)
-__global__ __launch_bounds__(256) void knn_transpose_kernel(const float *__restrict__ x, int ld, int n, int d, float *__restrict__ xt, int ldt)
-{
-    __shared__ float tile[32][33];
-    const int b = blockIdx.z, j0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int rr = ty; rr < 32; rr += 8) tile[rr][tx] = (j0 + rr < n) ? x[((size_t)b * n + j0 + rr) * ld + c0 + tx] : 0.f;
-    __syncthreads();
-    for (int cc = ty; cc < 32; cc += 8) xt[((size_t)b * d + c0 + cc) * ldt + j0 + tx] = tile[tx][cc];
-}
 
 // Both pre-passes of the fused kernel in ONE launch (round 3; they were two: 4 feature-space graphs x 2 launches per forward): a
 // workgroup takes 32 rows of an object and walks their d / 32 column tiles; each tile goes through LDS once and leaves as a
@@ -1177,72 +838,33 @@ extern "C" int64_t tgp_knn_feat_workspace_bytes(int B, int n, int d)
     return (extra + (int64_t)B * n) * (int64_t)sizeof(float);
 }
 
-// form: 0 = the library's choice, 1 = 32-row blocks (one workgroup per CU), 2 = 16-row blocks (two per CU)
+// CH: MFMA steps per prefetched chunk (four, three chunks ahead; eight measured the same: 18.68 vs 18.67 k objects/s)
 template <int DIM, int NT, int CH>
-static int launch_knn_fused(const float *xt, const float *q, int B, int n, int k, int32_t *idx, hipStream_t stream, int form,
-                            const float *xyz = nullptr, float4 *dirs = nullptr)
+static int launch_knn_fused(const float *xt, const float *q, int B, int n, int k, int32_t *idx, hipStream_t stream,
+                            const float *xyz, float4 *dirs)
 {
-    const int ncb = tgp_cdiv(n, 32), ldw = ncb * 32;
-    if (form != 1) {
-        const int tail16 = n % KF16_ROWS, n_extra16 = (tail16 > 0 && tail16 <= 8 && tail16 <= n / KF16_ROWS) ? tail16 : 0;
-        const int nrb16 = n_extra16 ? n / KF16_ROWS : tgp_cdiv(n, KF16_ROWS);
-        const size_t lds16 = (size_t)(KF16_ROWS + (n_extra16 ? 1 : 0)) * ldw * sizeof(float);
-        // (round 5) producer / consumer waves over a double-buffered image: form 3, and the library's choice when a workgroup gets at
-        // least four row blocks of an object to walk (one workgroup per CU: B x chunks of them) and the image fits
-        {
-            static int cus = 0;
-            if (!cus) {
-                int dev = 0;
-                if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-                    cus = 256;
-            }
-            const size_t ldspc = (size_t)2 * (KF16_ROWS + 1) * ldw * sizeof(float);
-            const int want = B >= cus ? 1 : cus / B;                   // workgroups per object for about one per CU
-            const int bpw = tgp_cdiv(nrb16, want < nrb16 ? want : nrb16), chunks = tgp_cdiv(nrb16, bpw);
-            if (ldspc <= 152 * 1024 && (form == 3 || (form == 0 && bpw >= 4 && tgp_knn_pc_mode))) {
-                static TgpLdsAttr attrpc;
-                if (const int e = tgp_lds_attr(attrpc, reinterpret_cast<const void *>(knn_feat_pc_kernel<DIM, NT, CH / 2>), 152 * 1024)) return e;
-                hipLaunchKernelGGL((knn_feat_pc_kernel<DIM, NT, CH / 2>), dim3(tgp_xcd_grid(B, chunks)), dim3(512), ldspc, stream, xt, q, B, n, k,
-                                   idx, nrb16, ldw, n_extra16, xyz, dirs, bpw, chunks, tgp_knn_stamps);
-                return TGP_LAUNCH_RESULT();
-            }
-        }
-        static TgpLdsAttr attr16;
-        if (const int e = tgp_lds_attr(attr16, reinterpret_cast<const void *>(knn_feat_fused16_kernel<DIM, NT, CH / 2>),
-                                       (KF16_ROWS + 1) * KF_MAX_LDW * (int)sizeof(float))) return e;
-        // (four steps per prefetched chunk, three chunks ahead; eight measured the same: 18.68 vs 18.67 k objects/s)
-        hipLaunchKernelGGL((knn_feat_fused16_kernel<DIM, NT, CH / 2>), dim3(tgp_xcd_grid(B, nrb16)), dim3(256), lds16, stream, xt, q, B, n, k,
-                           idx, nrb16, ldw, n_extra16, xyz, dirs);
-        return TGP_LAUNCH_RESULT();
-    }
-    if (dirs) return TGP_EUNSUPPORTED;
-    // a tail of at most 8 rows (and fewer than there are full blocks) rides along with the first blocks instead of forming its own
-    const int tail = n % KF_ROWS, n_extra = (tail > 0 && tail <= 8 && tail <= n / KF_ROWS) ? tail : 0;
-    const int nrb = n_extra ? n / KF_ROWS : tgp_cdiv(n, KF_ROWS);
-    const size_t lds = (size_t)(KF_ROWS + (n_extra ? 1 : 0)) * ldw * sizeof(float);
+    static_assert((KF16_ROWS + 1) * KF_MAX_LDW * sizeof(float) + 4 * 64 * sizeof(uint32_t) + 4 * KNN_LIST * sizeof(uint2) <= 160 * 1024,
+                  "the widest image, s_lmin and s_list must fit the CU's LDS");
+    const int ldw = tgp_cdiv(n, 32) * 32;
+    // a tail of at most 8 rows (and no more than there are full blocks) rides along with the first blocks instead of forming its own
+    const int tail = n % KF16_ROWS, n_extra = (tail > 0 && tail <= 8 && tail <= n / KF16_ROWS) ? tail : 0;
+    const int nrb = n_extra ? n / KF16_ROWS : tgp_cdiv(n, KF16_ROWS);
+    const size_t lds = (size_t)(KF16_ROWS + (n_extra ? 1 : 0)) * ldw * sizeof(float);
     static TgpLdsAttr attr;
-    if (const int e = tgp_lds_attr(attr, reinterpret_cast<const void *>(knn_feat_fused_kernel<DIM, NT, CH>),
-                                   (KF_ROWS + 1) * KF_MAX_LDW * (int)sizeof(float))) return e;
-    hipLaunchKernelGGL((knn_feat_fused_kernel<DIM, NT, CH>), dim3(tgp_xcd_grid(B, nrb)), dim3(512), lds, stream, xt, q, B, n, k, idx, nrb, ncb,
-                       ldw, n_extra, tgp_knn_stamps);
+    if (const int e = tgp_lds_attr(attr, reinterpret_cast<const void *>(knn_feat_fused16_kernel<DIM, NT, CH>),
+                                   (KF16_ROWS + 1) * KF_MAX_LDW * (int)sizeof(float))) return e;
+    hipLaunchKernelGGL((knn_feat_fused16_kernel<DIM, NT, CH>), dim3(tgp_xcd_grid(B, nrb)), dim3(256), lds, stream, xt, q, B, n, k, idx, nrb,
+                       ldw, n_extra, xyz, dirs);
     return TGP_LAUNCH_RESULT();
 }
 
-extern "C" int tgp_knn_feat_form(const float *feat, int ld, int B, int n, int d, int k, int32_t *idx, void *workspace,
-                                 int64_t workspace_bytes, int form, tgp_stream_t stream);
+static int knn_feat_go(const float *feat, int ld, int B, int n, int d, int k, int32_t *idx, void *workspace, int64_t workspace_bytes,
+                       const float *xyz, float4 *dirs, tgp_stream_t stream);
+
 extern "C" int tgp_knn_feat(const float *feat, int ld, int B, int n, int d, int k, int32_t *idx, void *workspace,
                             int64_t workspace_bytes, tgp_stream_t stream)
 {
-    return tgp_knn_feat_form(feat, ld, B, n, d, k, idx, workspace, workspace_bytes, 0, stream);
-}
-
-static int knn_feat_go(const float *feat, int ld, int B, int n, int d, int k, int32_t *idx, void *workspace, int64_t workspace_bytes,
-                       int form, const float *xyz, float4 *dirs, tgp_stream_t stream);
-
-extern "C" int tgp_knn_feat_form(const float *feat, int ld, int B, int n, int d, int k, int32_t *idx, void *workspace,
-                                 int64_t workspace_bytes, int form, tgp_stream_t stream)
-{
-    return knn_feat_go(feat, ld, B, n, d, k, idx, workspace, workspace_bytes, form, nullptr, nullptr, stream);
+    return knn_feat_go(feat, ld, B, n, d, k, idx, workspace, workspace_bytes, nullptr, nullptr, stream);
 }
 
 // tgp_knn_feat that also leaves the unit directions to the selected neighbours in the points' xyz (B, n, 3): dirs (B, n, k) float4
@@ -1253,13 +875,13 @@ extern "C" int tgp_knn_feat_dirs(const float *feat, int ld, int B, int n, int d,
 {
     TGP_REQUIRE(xyz && dirs && (reinterpret_cast<uintptr_t>(dirs) & 15) == 0);
     if (!knn_feat_fused_ok(n, d)) return TGP_EUNSUPPORTED;
-    return knn_feat_go(feat, ld, B, n, d, k, idx, workspace, workspace_bytes, 0, xyz, reinterpret_cast<float4 *>(dirs), stream);
+    return knn_feat_go(feat, ld, B, n, d, k, idx, workspace, workspace_bytes, xyz, reinterpret_cast<float4 *>(dirs), stream);
 }
 
 static int knn_feat_go(const float *feat, int ld, int B, int n, int d, int k, int32_t *idx, void *workspace, int64_t workspace_bytes,
-                       int form, const float *xyz, float4 *dirs, tgp_stream_t stream)
+                       const float *xyz, float4 *dirs, tgp_stream_t stream)
 {
-    TGP_REQUIRE(feat && idx && workspace && form >= 0 && form <= 3);
+    TGP_REQUIRE(feat && idx && workspace);
     const int chk = knn_check(B, n, k);
     if (chk) return chk;
     if (d <= 0 || (d & 31) || (d >> 5) >= 16) return TGP_EUNSUPPORTED;
@@ -1277,8 +899,8 @@ static int knn_feat_go(const float *feat, int ld, int B, int n, int d, int k, in
         else
             hipLaunchKernelGGL(knn_prep_kernel, dim3(ldt / 32, B), dim3(256), 0, tgp_hs(stream), feat, ld, n, d, D, ldt, q);
 #define LAUNCH_FUSED(NT) \
-    (d == 128 ? launch_knn_fused<128, NT, 8>(D, q, B, n, k, idx, tgp_hs(stream), form, xyz, dirs)                     \
-              : launch_knn_fused<256, NT, 8>(D, q, B, n, k, idx, tgp_hs(stream), form, xyz, dirs))
+    (d == 128 ? launch_knn_fused<128, NT, 4>(D, q, B, n, k, idx, tgp_hs(stream), xyz, dirs)                     \
+              : launch_knn_fused<256, NT, 4>(D, q, B, n, k, idx, tgp_hs(stream), xyz, dirs))
         if (nt <= 1) return LAUNCH_FUSED(1);
         if (nt <= 2) return LAUNCH_FUSED(2);
         if (nt <= 5) return LAUNCH_FUSED(5);

@@ -108,11 +108,8 @@ def knn_xyz(xyz, k):
     return idx
 
 
-KNN_FEAT_FORM = int(os.environ.get("TGP_KNN_FEAT_FORM", "0"))     # 0: the library's choice (tgp_knn_feat_form)
-
-
 @_timed("graph")
-def knn_feat(feat, k, workspace=None, form=None, xyz=None):
+def knn_feat(feat, k, workspace=None, xyz=None):
     """feat (B,n,d) rows contiguous (row stride may exceed d) -> idx (B,n,k) int32.
     xyz (B,n,3): returns (idx, dirs) -- dirs (B,n,k,4) the unit directions to the selected neighbours (tgp_knn_feat_dirs: written by
     the selecting waves; gconv_hs(dirs=...) takes them) or None where the fused kernel does not serve the shape."""
@@ -132,9 +129,8 @@ def knn_feat(feat, k, workspace=None, form=None, xyz=None):
         if rc != -2:
             check(rc, "tgp_knn_feat_dirs")
         dirs = None
-    check(_lib.lib().tgp_knn_feat_form(_p(feat), ld, B, n, d, int(k), _p(idx), _p(workspace),
-                                       workspace.numel() * workspace.element_size(), KNN_FEAT_FORM if form is None else int(form),
-                                       _stream(feat)), "tgp_knn_feat")
+    check(_lib.lib().tgp_knn_feat(_p(feat), ld, B, n, d, int(k), _p(idx), _p(workspace), workspace.numel() * workspace.element_size(),
+                                  _stream(feat)), "tgp_knn_feat")
     return idx if xyz is None else (idx, None)
 
 
