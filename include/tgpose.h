@@ -1779,6 +1779,69 @@ typedef struct tgp_tsdf_raycast_args {
 } tgp_tsdf_raycast_args;
 int tgp_tsdf_raycast(const tgp_tsdf_raycast_args *args, tgp_stream_t stream);
 
+/* ---- Dense projective ICP against ray-cast maps (csrc/icp_dense.hip; additive, ABI stays 9) -------------------------------------------
+ * DESIGN.md section 3 "Dense projective registration" is the contract; tests/icp_dense_ref.py restates it in NumPy.  Registration of
+ * depth frames to the vertex / normal maps of ONE tgp_tsdf_raycast call: the map is indexed by pixel, so a source pixel finds its
+ * model point by projection, not by search.  J jobs in ONE launch, one workgroup per job, every iteration inside the kernel; nothing
+ * allocated, nothing read by the host, graph-capturable.  A job's result depends on neither the other jobs nor J; no atomics:
+ * bit-repeatable.
+ *
+ * depth (S,H,W) uint16 millimetres, camk (S,4) = fx, fy, cx, cy, mask (S,H,W) uint8 or NULL with job_mask_val (J), as
+ * tgp_tsdf_integrate takes them.  The maps: vertex, normal (J,h,w,3) float32 in the MODEL frame, z (J,h,w) float32 (a cell is a hit
+ * iff z > 0), job_window (J,4) = u0, v0, du, dv, job_ref (J,3,4) float32 = the [s R | t] the maps were cast from (the job_pose whose
+ * inverse tgp_tsdf_raycast took).  job_img (J): the job's frame and intrinsics.  job_rect (J,4) int32 = x0, y0, x1, y1 inclusive and
+ * stride >= 1: the job's source pixels are (x0 + i stride, y0 + k stride), i, k >= 0, that lie in the rectangle clipped to the frame
+ * [0, W-1] x [0, H-1], numbered row-major among themselves, e = k' nx + i' (nx of them a row); no cap on their number.  Start pose R
+ * (J,3,3), t (J,3), s (J): x = s R y + t from model to camera, as tgp_icp_refine takes it; max_dist (J): the gate in metres; iters,
+ * tol_rot, tol_trans, min_inliers with tgp_icp_refine's meaning.  The state (R, t) is float64 throughout; s does not move.
+ * Per iteration, for each source pixel (x, y) with d = depth[img, y, x] != 0 and (with a mask) mask[img, y, x] == job_mask_val[j];
+ * float32, every operation rounded on its own, correctly rounded divisions, no contraction, except where float64 is named:
+ *   p   = tgp_pixel_point of (x, y, d) (csrc/pixel_point.h: the crops' bits);
+ *   q   = float32(R^T (p - t) / s): tgp_icp_refine's float64 sequence, rounded once;
+ *   c_r = ((T_r0 q_x + T_r1 q_y) + T_r2 q_z) + T_r3, T = job_ref;                                skipped unless c_z > 1e-6f
+ *   u   = K0 (c_x / c_z) + K2, v = K1 (c_y / c_z) + K3 (tgp_tsdf_integrate's projection);
+ *   col = rintf((u - u0) / du), row = rintf((v - v0) / dv), ties to even; the pixel is ASSOCIATED iff 0 <= col <= w - 1, 0 <= row <=
+ *         h - 1 and z[row, col] > 0 (a NaN fails every comparison);
+ *   y, n = vertex, normal[row, col]; e = q - y; the pixel is an INLIER iff ((e_x e_x + e_y e_y) + e_z e_z) <= float32((max_dist / s)^2)
+ *         (the threshold in float64, rounded once, as tgp_icp_refine forms it);
+ *   the inliers' rows [q x n, n] and residuals (q - y) . n, in float64 on the float32 values, go into tgp_icp_refine's mode 1: the 21
+ *   + 6 + 1 sums, fewer than max(min_inliers, 6) inliers: status 1; damping 1e-9 trace(A) / 6, Cholesky (a non-positive pivot or a
+ *   non-finite step: status 2), R <- R exp(w)^T, t <- t - s R v, the same stop rule (csrc/icp_solve.h is the one text of both).
+ * The sums are float64 in a fixed order: per lane over e = tid, tid + 512, ... in that order, a shuffle tree across the wave, the
+ * waves serially.  After the last iteration one more association pass runs at the final pose.  A job that fails (status 1 or 2)
+ * goes back to the pose it came with: R_out, t_out are the inputs' bits, and the final pass runs there.
+ * -> R_out, t_out, s_out (s_out = s); info (J,4) int32 = status (0 ok, 1 too few inliers, 2 singular or not finite, 3 job_img
+ * outside [0, S): nothing else is read, the pose is copied through, rmse NaN, corr -1), final inliers, iterations done, candidates =
+ * the source pixels associated at the START pose, before the distance gate; rmse (J): root mean square of s |q - y| over the final
+ * inliers (float64 on the float32 values), NaN without any; corr (J, corr_cap) int32 or NULL: for e < corr_cap the final pass's cell
+ * row w + col of source pixel e if it is an inlier, else -1 (beyond the job's pixel count too).
+ * TGP_EINVAL (before any launch, the outputs untouched): a NULL required pointer, mask without job_mask_val, S, H or W < 1, J < 0, h
+ * or w < 1, stride < 1, iters < 1, a negative or NaN tolerance, min_inliers < 0, corr_cap < 0, corr_cap > 0 without corr.
+ * TGP_EUNSUPPORTED: h or w > TGP_RAYCAST_MAX_SIDE, H or W > 16384, J > 65535.  J == 0 returns 0. */
+typedef struct tgp_icp_dense_args {
+    const uint16_t *depth;
+    const float *camk;
+    int S, H, W;
+    const uint8_t *mask;            /* may be NULL */
+    const uint8_t *job_mask_val;    /* required with mask, not read without */
+    const float *vertex, *normal, *z;
+    int h, w;
+    const float *job_window, *job_ref;
+    const int32_t *job_img, *job_rect;
+    int J, stride;
+    const float *R, *t, *s;
+    const float *max_dist;
+    int iters;
+    float tol_rot, tol_trans;
+    int min_inliers;
+    float *R_out, *t_out, *s_out;
+    int32_t *info;
+    float *rmse;
+    int32_t *corr;                  /* may be NULL */
+    int corr_cap;
+} tgp_icp_dense_args;
+int tgp_icp_dense(const tgp_icp_dense_args *args, tgp_stream_t stream);
+
 /* ---- Indexed meshes from volumes: welding and vertex normals (csrc/weld.hip; additive, ABI stays 8) ---------------------------------
  * DESIGN.md section 3 "Indexed meshes from volumes" is the contract; tests/weld_ref.py restates every kernel in NumPy, bit for bit.
  * The volumes, the cubes that mesh, the tetrahedra and the triangles' order are tgp_tsdf_mesh_count / _emit's above.

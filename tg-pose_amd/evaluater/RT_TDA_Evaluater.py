@@ -509,7 +509,7 @@ class myEvaluater:
             return volumes, ops.tsdf_meshset(volumes, min_weight, indexed=indexed, cluster=cluster)
 
     def scan_track(self, sequence, init, camK=lde.REAL_INTRINSICS, ratio=None, volumes=None, G=64, trunc_mm=None, refine_kw=None,
-                   n_pts=1024, sampler=None, use_mask=True, support=None, min_inlier_frac=0.5, max_rmse=None, near=0.01):
+                   n_pts=1024, sampler=None, use_mask=True, support=None, min_inlier_frac=0.5, max_rmse=None, near=0.01, register="sparse"):
         """Track objects that have no model while scanning them (DESIGN.md section 3 "Ray casting and frame-to-model tracking"): each
         frame is registered to the TSDF volumes as they stand and is then fused into them.  One pose per object in frame 0 is all it
         needs.
@@ -528,9 +528,16 @@ class myEvaluater:
         -> (results, volumes): per frame ``track``'s {'pred_RTs', 'pred_scales', 'status', 'tracked'} plus 'icp_status',
         'icp_inliers' (int32), 'icp_rmse' (float32), 'ray_hits' (int32) and 'fused' (bool: registered, and so fused), (n,) each
         (frame 0: status 0, no ICP, fused).  Mesh the volumes with ops.tsdf_meshset (indexed=True, cluster=c for a welded or a
-        decimated model, as ``scan`` takes them)."""
-        from ..pose import RaycastRefine, verify_job_pose
-        if ratio is None:
+        decimated model, as ``scan`` takes them).
+        register='dense' (DESIGN.md section 3 "Dense projective registration"): frame k >= 1 is not cropped; after the optional
+        plane cut the frame itself, with its instance mask when it has one, is registered by pose.DenseRefine (refine_kw: its
+        keywords; ratio, n_pts and sampler are not used).  An object is registered when its status is 0 and its inliers reach
+        min_inlier_frac x its candidates (the pixels its map associated at the previous pose), plus max_rmse; 'status' is 0 for
+        every object.  The result keys are the same."""
+        from ..pose import DenseRefine, RaycastRefine, verify_job_pose
+        if register not in ("sparse", "dense"):
+            raise ValueError("scan_track: register must be 'sparse' or 'dense'")
+        if ratio is None and register == "sparse":
             raise ValueError("scan_track: ratio is required (the reference fixes none)")
         if support is not None and not isinstance(support, SupportPlane):
             raise TypeError("scan_track: support must be a pose.SupportPlane")
@@ -554,7 +561,7 @@ class myEvaluater:
         kw = dict(refine_kw or {})
         kw.setdefault("max_dist", 3.0 * voxel_m)
         kw.setdefault("near", near)
-        refine = RaycastRefine(volumes, kw.pop("max_dist"), **kw)
+        refine = (DenseRefine if register == "dense" else RaycastRefine)(volumes, kw.pop("max_dist"), **kw)
         rts, scales = torch.from_numpy(rts0).to(dev), torch.from_numpy(scales0).to(dev)
         inst_ids = init.get("inst_ids") if use_mask else None
         mask_val = torch.as_tensor(np.asarray(inst_ids), dtype=torch.uint8).to(dev) if inst_ids is not None else None
@@ -584,6 +591,14 @@ class myEvaluater:
                     rmse = torch.zeros(n, dtype=torch.float32, device=dev)
                     hits = torch.zeros(n, dtype=torch.int32, device=dev)
                     ok = torch.ones(n, dtype=torch.bool, device=dev)
+                elif register == "dense":
+                    new_rts, info, rmse, hits = refine(depth, rts, camk, job_img, mask=inst.view(torch.uint8) if masks is not None else None,
+                                                       job_mask_val=mask_val if masks is not None else None)
+                    ok = (info[:, 0] == 0) & (info[:, 1].float() >= float(min_inlier_frac) * info[:, 3].float())
+                    if max_rmse is not None:
+                        ok = ok & (rmse <= float(max_rmse))
+                    rts = torch.where(ok[:, None, None], new_rts, rts)
+                    status = torch.zeros(n, dtype=torch.int32, device=dev)
                 else:
                     crop = dict(depth=depth) if inst is None else dict(depth=depth, inst_mask=inst)
                     pts, ok, _, counts = lde.clouds_from_poses(crop, job_img, rts, scales, ratio, camK, n_pts=n_pts, sampler=sampler, masks=masks,

@@ -3103,6 +3103,86 @@ def tsdf_windows(volumes, camk, job_img, job_model, job_pose, h, w, H, W, pad=1.
     return torch.where(good[:, None], win, torch.full_like(win, float("nan"))).contiguous()
 
 
+# ------------------------------------------------------------------------------------------------------------ dense projective ICP
+def dense_rects(window, h, w, H, W):
+    """The frame pixels that the h x w ray grids of ``window`` (J,4) float32 = (u0, v0, du, dv) cover, as icp_dense's job_rect: (J,4)
+    int32 (x0, y0, x1, y1) inclusive = the floor of the smaller and the ceil of the larger of each axis' two ends (u0 and u0 +
+    (w - 1) du, float32), clamped to the frame [0, W-1] x [0, H-1].  A window with a NaN in an end (tsdf_windows' empty window)
+    gives the empty rectangle (0, 0, -1, -1).  Torch operations on the window's device (tests/icp_dense_ref.py rects); nothing is
+    read back."""
+    if not (torch.is_tensor(window) and window.dtype == torch.float32 and window.dim() == 2 and window.shape[1] == 4):
+        raise ValueError("dense_rects: window must be a (J,4) float32 tensor")
+    if not all(isinstance(v, int) and v >= 1 for v in (h, w, H, W)):
+        raise ValueError("dense_rects: h, w, H, W must be ints >= 1")
+    ua, va = window[:, 0], window[:, 1]
+    ub, vb = ua + float(w - 1) * window[:, 2], va + float(h - 1) * window[:, 3]
+    bad = torch.isnan(ua) | torch.isnan(ub) | torch.isnan(va) | torch.isnan(vb)
+    box = torch.stack([torch.minimum(ua, ub).floor().clamp(0.0, float(W - 1)), torch.minimum(va, vb).floor().clamp(0.0, float(H - 1)),
+                       torch.maximum(ua, ub).ceil().clamp(0.0, float(W - 1)), torch.maximum(va, vb).ceil().clamp(0.0, float(H - 1))], 1)
+    empty = -(torch.arange(4, dtype=torch.int32, device=window.device) // 2)               # (0, 0, -1, -1), made on the device
+    box = torch.where(bad[:, None], torch.zeros_like(box), box).to(torch.int32)           # a NaN has no integer
+    return torch.where(bad[:, None], empty[None], box).contiguous()
+
+
+def icp_dense(depth, camk, job_img, rect, rc, window, ref_pose, R, t, s, max_dist, *, stride=1, mask=None, job_mask_val=None, iters=30,
+              tol_rot=1e-5, tol_trans=1e-6, min_inliers=6, corr_cap=0):
+    """tgp_icp_dense (csrc/icp_dense.hip; DESIGN.md section 3 "Dense projective registration"): J poses registered to depth frames
+    against the maps of one tsdf_raycast call, in one launch, every iteration on the device.  A source pixel finds its model point
+    by projecting into the map (no search), so every depth pixel of the object can take part.  depth (S,H,W) 16-bit millimetres,
+    camk (S,4), job_img (J) int32, mask (S,H,W) uint8 with job_mask_val (J) uint8 or neither, as tsdf_integrate takes them; rect
+    (J,4) int32 (x0, y0, x1, y1) inclusive (dense_rects) and ``stride``: the job's source pixels (x0 + i stride, y0 + k stride)
+    inside the frame; rc: tsdf_raycast's dict (z, vertex, normal of J jobs), window (J,4) and ref_pose (J,3,4) [s R | t]: the window
+    and pose that call cast from; R (J,3,3), t (J,3), s (J): the start x = s R y + t; max_dist (J) float32 (or one number): the
+    gate in metres; iters, tol_rot, tol_trans, min_inliers as icp_refine takes them.
+    -> (R, t, s, info (J,4) int32 = status, final inliers, iterations, candidates (pixels associated at the start pose before the
+    gate); rmse (J)[, corr (J, corr_cap) int32 with corr_cap > 0: source pixel e's final map cell, -1 for a non-inlier]).  A job that
+    fails (ICP_STATUS; 3: job_img out of range) returns the pose it came with.  Nothing is read back (icp_check_status does)."""
+    if not (isinstance(stride, int) and stride >= 1):
+        raise ValueError("icp_dense: stride must be an int >= 1")
+    if not (isinstance(iters, int) and iters >= 1):
+        raise ValueError("icp_dense: iters must be an int >= 1")
+    if not (tol_rot >= 0 and tol_trans >= 0 and isinstance(min_inliers, int) and min_inliers >= 0):
+        raise ValueError("icp_dense: tol_rot, tol_trans and min_inliers must not be negative")
+    if not (isinstance(corr_cap, int) and corr_cap >= 0):
+        raise ValueError("icp_dense: corr_cap must be an int >= 0")
+    if not (isinstance(rc, dict) and all(k in rc for k in ("z", "vertex", "normal"))):
+        raise TypeError("icp_dense: rc must be tsdf_raycast's dict (z, vertex, normal)")
+    if not (torch.is_tensor(job_img) and job_img.is_cuda):
+        raise TypeError("icp_dense: job_img must be a contiguous int32 GPU tensor")
+    dev = job_img.device
+    J = job_img.numel()
+    if not torch.is_tensor(max_dist):
+        max_dist = torch.full((J,), float(max_dist), device=dev, dtype=torch.float32)
+    S, H, W, J = _frame_jobs("icp_dense", dev, depth, camk, job_img,
+                             [(rect, "rect", torch.int32, (4,)), (window, "window", torch.float32, (4,)),
+                              (ref_pose, "ref_pose", torch.float32, (3, 4)), (R, "R", torch.float32, (3, 3)), (t, "t", torch.float32, (3,)),
+                              (s, "s", torch.float32, ()), (max_dist, "max_dist", torch.float32, ())],
+                             mask, job_mask_val, where="job_img's device")
+    z, vertex, normal = rc["z"], rc["vertex"], rc["normal"]
+    _gpu_args("icp_dense", dev, [(z, "rc['z']", torch.float32), (vertex, "rc['vertex']", torch.float32), (normal, "rc['normal']", torch.float32)],
+              where="job_img's device")
+    if z.dim() != 3 or z.shape[0] != J or vertex.shape != z.shape + (3,) or normal.shape != z.shape + (3,):
+        raise ValueError("icp_dense: rc must hold z (J,h,w), vertex and normal (J,h,w,3) of the %d jobs" % J)
+    h, w = z.shape[1:]
+    if not (1 <= h <= RAYCAST_MAX_SIDE and 1 <= w <= RAYCAST_MAX_SIDE):
+        raise ValueError("icp_dense: the maps' h and w must be in [1, %d]" % RAYCAST_MAX_SIDE)
+    if J > 65535 or H > 16384 or W > 16384:
+        raise ValueError("icp_dense: at most 65535 jobs a call and frames of at most 16384 pixels a side")
+    R_out, t_out, s_out = torch.empty_like(R), torch.empty_like(t), torch.empty_like(s)
+    info = torch.empty(J, 4, device=dev, dtype=torch.int32)
+    rmse = torch.empty(J, device=dev, dtype=torch.float32)
+    corr = torch.empty(J, corr_cap, device=dev, dtype=torch.int32) if corr_cap else None
+    if J > 0:
+        a = _lib.IcpDenseArgs(depth=_p(depth), camk=_p(camk), S=S, H=H, W=W, mask=_p(mask), job_mask_val=_p(job_mask_val), vertex=_p(vertex),
+                              normal=_p(normal), z=_p(z), h=h, w=w, job_window=_p(window), job_ref=_p(ref_pose), job_img=_p(job_img),
+                              job_rect=_p(rect), J=J, stride=stride, R=_p(R), t=_p(t), s=_p(s), max_dist=_p(max_dist), iters=iters,
+                              tol_rot=float(tol_rot), tol_trans=float(tol_trans), min_inliers=min_inliers, R_out=_p(R_out), t_out=_p(t_out),
+                              s_out=_p(s_out), info=_p(info), rmse=_p(rmse), corr=_p(corr), corr_cap=corr_cap)
+        check(_lib.lib().tgp_icp_dense(ctypes.byref(a), _stream(job_img)), "tgp_icp_dense")
+    out = (R_out, t_out, s_out, info, rmse)
+    return out + (corr,) if corr_cap else out
+
+
 # ------------------------------------------------------------------------------------------------------------ the supporting plane
 PLANE_STATUS = {1: "no hypothesis reached min_inliers", 2: "a refit was not finite (the plane of before it is returned)"}
 

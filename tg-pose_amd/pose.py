@@ -246,6 +246,52 @@ class RaycastRefine(object):
         return torch.where(few[:, None, None], RTs, new), info, rmse, rc["count"]
 
 
+class DenseRefine(object):
+    """Frame-to-model registration against TSDF volumes by dense projective ICP (DESIGN.md section 3 "Dense projective
+    registration"): the surface each volume shows from its object's current pose is ray-cast into h x w vertex and normal maps
+    (ops.tsdf_windows, ops.tsdf_raycast), and the frame's depth pixels under each map (ops.dense_rects, every ``stride``-th a side)
+    are registered to it by ONE ops.icp_dense call -- no crop, no sampler, no sort and no nearest-neighbour search between the ray
+    cast and the solve.  volumes: ops.TsdfVolumes; job_model: one volume index per object (default: object j is volume j);
+    max_dist: the gate in metres; min_weight, step, near: the ray cast's; kw: ops.icp_dense's keywords (iters, tol_rot, ...).
+    __call__(depth (S,H,W) 16-bit millimetres, RTs (J,4,4) [s R | t], camk (S,4), job_img (J) int32, mask (S,H,W) uint8 with
+    job_mask_val (J) uint8 or neither) -> (RTs (J,4,4), info (J,4) int32 = status, inliers, iterations, candidates, rmse (J,), hits
+    (J,) int32).  A job with fewer than ``min_hits`` hits keeps the pose it came with and has status RAYCAST_FEW_HITS in info[:, 0].
+    Two launches and torch's glue; nothing is read back."""
+
+    def __init__(self, volumes, max_dist, h=96, w=128, stride=1, min_weight=1, step=1.0, near=0.01, min_hits=64, job_model=None, **kw):
+        if not isinstance(volumes, ops.TsdfVolumes):
+            raise TypeError("DenseRefine: volumes must be an ops.TsdfVolumes")
+        if not (isinstance(h, int) and isinstance(w, int) and 1 <= h <= ops.RAYCAST_MAX_SIDE and 1 <= w <= ops.RAYCAST_MAX_SIDE):
+            raise ValueError("DenseRefine: h and w must be ints in [1, %d]" % ops.RAYCAST_MAX_SIDE)
+        if not (isinstance(stride, int) and stride >= 1):
+            raise ValueError("DenseRefine: stride must be an int >= 1")
+        if not (isinstance(min_hits, int) and min_hits >= 0):
+            raise ValueError("DenseRefine: min_hits must be an int >= 0")
+        if kw.get("corr_cap"):
+            raise ValueError("DenseRefine: corr_cap is ops.icp_dense's")
+        dev = volumes.sum.device
+        self.volumes, self.h, self.w, self.stride, self.min_weight, self.step, self.near, self.min_hits = volumes, h, w, stride, min_weight, step, near, min_hits
+        self.job_model = None if job_model is None else torch.as_tensor(job_model, dtype=torch.int32).to(dev).contiguous()
+        self.max_dist = max_dist.to(dev).float().contiguous() if torch.is_tensor(max_dist) else float(max_dist)
+        self.kw = dict(kw)
+
+    def __call__(self, depth, RTs, camk, job_img, mask=None, job_mask_val=None):
+        J, dev = RTs.shape[0], RTs.device
+        H, W = depth.shape[1:]
+        job_model = self.job_model if self.job_model is not None else torch.arange(J, dtype=torch.int32, device=dev)
+        P = verify_job_pose(RTs)
+        win = ops.tsdf_windows(self.volumes, camk, job_img, job_model, P, self.h, self.w, H, W)
+        rc = ops.tsdf_raycast(self.volumes, camk, job_img, job_model, P, win, self.h, self.w, min_weight=self.min_weight, step=self.step,
+                              near=self.near)
+        rect = ops.dense_rects(win, self.h, self.w, H, W)
+        R, t, s = split_RT(RTs)
+        R, t, s, info, rmse = ops.icp_dense(depth, camk, job_img, rect, rc, win, P, R, t, s, self.max_dist, stride=self.stride, mask=mask,
+                                            job_mask_val=job_mask_val, **self.kw)
+        few = rc["count"] < self.min_hits
+        info = torch.cat([torch.where(few, torch.full_like(info[:, 0], RAYCAST_FEW_HITS), info[:, 0])[:, None], info[:, 1:]], 1)
+        return torch.where(few[:, None, None], RTs, join_RT(R, t, s)), info, rmse, rc["count"]
+
+
 def cloud_anchors(clouds, counts=None):
     """The mean of each cloud's finite rows (of the first counts[j] rows): float64 sums on the device, rounded once -> (J,3) float32;
     a cloud without a finite row gives 0."""
