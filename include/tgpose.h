@@ -1932,6 +1932,61 @@ typedef struct tgp_mesh_normals_args {
 } tgp_mesh_normals_args;
 int tgp_mesh_vertex_normals(const tgp_mesh_normals_args *args, tgp_stream_t stream);
 
+/* ---- Vertex / normal maps of posed meshes (csrc/meshmaps.hip; additive, ABI stays 9) -------------------------------------------------
+ * DESIGN.md section 3 "Mesh maps and dense model-based tracking" is the contract; tests/meshmaps_ref.py restates it in NumPy on
+ * tests/render_ref.py.  J jobs in one call; job j = (intrinsics camk[job_img[j]] = fx, fy, cx, cy, mesh job_mesh[j] of the packed
+ * mesh set as tgp_pose_verify takes it, pose job_pose[j] (3,4) fp32 [s R | t], window job_window[j] = (u0, v0, du, dv)).  Cell (r, c) of
+ * the job's h x w maps is the pixel coordinate (u0 + c du, v0 + r dv): tgp_tsdf_raycast's convention, so tgp_icp_dense takes the maps
+ * (z, vertex, normal, with job_window and job_ref = job_pose) as it takes a ray cast's.
+ * The window is a camera: K' = (fx / du, fy / dv, (cx - u0) / du, (cy - v0) / dv) in float32, correctly rounded divisions, every
+ * operation rounded on its own.  The job is rasterised as a w x h frame under K' by tgp_render_depth's rules unchanged (the vertex
+ * arithmetic, the 1/256 snapping, the near rule and the guard band, coverage, z, the smallest key {z bits, face}, both windings): with
+ * window (0, 0, 1, 1) and (h, w) = (H, W), K' is K in every bit and z and face are tgp_render_depth's of a one-instance scene.  A
+ * window holding a NaN or a zero step leaves no vertex inside the guard band, an infinite step leaves no triangle an area: every
+ * triangle goes and every cell misses, by the arithmetic alone.
+ * The winner of a cell, face f with snapped corner records v_0..v_2 and model corners p_0..p_2 (corners 1 and 2 change places where
+ * the snapped area is negative), float32, every operation rounded on its own, no contraction:
+ *    e_k = the edge integers at the cell's sample (256 c, 256 r), as the rasteriser's sweep forms them; w_k = (float)e_k / (float)area;
+ *    z = the key's high word; b_k = (w_k iz_k) z; vertex_a = (b_0 p0_a + b_1 p1_a) + b_2 p2_a   (perspective-correct, MODEL frame)
+ *    vnormals == NULL (face normals): u = p1 - p0, v = p2 - p0, n = (u_y v_z - u_z v_y, u_z v_x - u_x v_z, u_x v_y - u_y v_x);
+ *    vnormals (n_verts,3) given: n_a = (b_0 n0_a + b_1 n1_a) + b_2 n2_a over the corners' rows;
+ *    s = sqrtf((n_x n_x + n_y n_y) + n_z n_z); the cell is a MISS unless 0 < s < inf; normal = n / s.  Face normals only: m_r = (T_r0
+ *    n_x + T_r1 n_y) + T_r2 n_z on the unit normal, T = job_pose; ray = (((float)c - K'2) / K'0, ((float)r - K'3) / K'1, 1); the normal
+ *    is negated iff (m_x ray_x + m_y ray_y) + m_z > 0.  Vertex normals are not flipped.
+ * -> z (J,h,w) fp32, 0 on a miss; depth (J,h,w) uint16 = rint(1000 z), 0 above 65535; vertex, normal (J,h,w,3) fp32, zeros on a miss;
+ * face (J,h,w) int32 or NULL, -1 on a miss; count (J) int32 = the job's hits; dropped (J) int32 = triangles dropped by the near rule
+ * and the guard band, summed; status (J) int32 = 1 for a job whose job_img is outside [0, S) or whose mesh renders nothing by the
+ * renderer's rules: all its cells miss.  EVERY cell of every job is written, and count and dropped are zeroed by the call: no output
+ * needs clearing.  Integer atomics only: two calls give identical bytes, and a job's bytes do not depend on the other jobs.
+ * workspace: tgp_mesh_maps_workspace_bytes(J, max_verts, max_faces) bytes, 16-byte aligned, nothing in it needs initialising.  Three
+ * kernels on the caller's stream, nothing read by the host; graph-capturable.
+ * TGP_EINVAL (before any launch, the outputs untouched): a NULL required pointer (with J > 0: the job arrays, the outputs but face,
+ * the workspace), S, M, h, w, n_verts, n_faces, max_verts or max_faces < 1, J < 0, near <= 0 or not finite, workspace_bytes too small.
+ * TGP_EUNSUPPORTED: h or w > TGP_RAYCAST_MAX_SIDE, J > TGP_MAPS_MAX_JOBS, max_faces >= tgp_render_max_faces().
+ * tgp_mesh_maps_workspace_bytes returns TGP_EINVAL / TGP_EUNSUPPORTED by the same rule.  J == 0 launches nothing and returns 0. */
+#define TGP_MAPS_MAX_JOBS 65535
+typedef struct tgp_mesh_maps_args {
+    const float *camk;
+    const float *verts;
+    const int32_t *faces;
+    const int32_t *vptr, *fptr;
+    int M, n_verts, n_faces, max_verts, max_faces;
+    const float *vnormals;          /* may be NULL: face normals */
+    const int32_t *job_img, *job_mesh;
+    const float *job_pose, *job_window;
+    int S, J, h, w;
+    float near;
+    float *z;
+    uint16_t *depth;
+    float *vertex, *normal;
+    int32_t *face;                  /* may be NULL */
+    int32_t *count, *dropped, *status;
+    void *workspace;
+    int64_t workspace_bytes;
+} tgp_mesh_maps_args;
+int64_t tgp_mesh_maps_workspace_bytes(int J, int max_verts, int max_faces);
+int tgp_mesh_maps(const tgp_mesh_maps_args *args, tgp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

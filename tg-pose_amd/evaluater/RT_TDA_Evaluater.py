@@ -22,7 +22,7 @@ from .. import ops
 from ..evaluation import load_data_eval as lde
 from ..evaluation.metrics import compute_degree_cm_mAP
 from ..losses.utils_v2.model_utils import calc_cd, calc_emd
-from ..pose import IcpRefine, ModelSearch, Segmenter, SupportPlane, Verify, infer_device, scan_models
+from ..pose import DenseModelRefine, IcpRefine, ModelSearch, Segmenter, SupportPlane, Verify, infer_device, scan_models
 
 SYNSET_NAMES = ['BG', 'bottle', 'bowl', 'camera', 'can', 'laptop', 'mug']                                   # :115
 MEAN_SHAPE_MM = {1: (87, 220, 89), 2: (165, 80, 165), 3: (88, 128, 156), 4: (68, 146, 72), 5: (346, 200, 335), 6: (146, 83, 114)}
@@ -359,13 +359,22 @@ class myEvaluater:
         there).  The results gain 'verify_counts' (n,8) int32 (ops.VERIFY_COUNTS), 'verify_score' (n,) float32 and 'verified' (n,)
         bool = score >= verify.min_score, fetched with the others.  Verification reports and does not gate: the poses carried to
         the next frame, and every other result, are those of the same call without ``verify``.
+
+        refine may also be a pose.DenseModelRefine (DESIGN.md section 3 "Mesh maps and dense model-based tracking"): the frame
+        itself -- uploaded once, after the optional plane cut, with its 'inst_mask' and inst_ids as the mask when use_mask and both
+        are there -- is registered to the objects' rasterised meshes by dense projective ICP.  With init_from='previous' there is no
+        crop and no forward: ratio may be None, n_pts and sampler are not used, and 'status' is 0 for every object.  With
+        init_from='net' the crop and the forward run as above and the registration starts from the network's poses.  An object
+        whose ICP status is not 0 (ops.ICP_STATUS, pose.RAYCAST_FEW_HITS, pose.DENSE_GATED) keeps its previous pose; the results
+        gain 'icp_status', 'icp_inliers', 'icp_candidates', 'ray_hits' (int32) and 'icp_rmse' (float32), (n,) each.
         -> list over frames of {'pred_RTs' (n,4,4), 'pred_scales' (n,3), 'status' (n,) int32, 'tracked' (n,) bool} ndarrays."""
-        if ratio is None:
-            raise ValueError("track: ratio is required (the reference fixes none)")
         if init_from not in ("net", "previous"):
             raise ValueError("track: init_from must be 'net' or 'previous'")
-        if refine is not None and not isinstance(refine, IcpRefine):
-            raise TypeError("track: refine must be a pose.IcpRefine")
+        dense = isinstance(refine, DenseModelRefine)
+        if ratio is None and not (dense and init_from == "previous"):
+            raise ValueError("track: ratio is required (the reference fixes none)")
+        if refine is not None and not isinstance(refine, (IcpRefine, DenseModelRefine)):
+            raise TypeError("track: refine must be a pose.IcpRefine or a pose.DenseModelRefine")
         if support is not None and not isinstance(support, SupportPlane):
             raise TypeError("track: support must be a pose.SupportPlane")
         if verify is not None and not isinstance(verify, Verify):
@@ -387,6 +396,7 @@ class myEvaluater:
         rts, scales = t(init["RTs"]).reshape(n, 4, 4), t(init["scales"]).reshape(n, 3)
         inst_ids = init.get("inst_ids") if use_mask else None
         job_img = torch.zeros(n, dtype=torch.int32, device=dev)
+        mask_val = torch.as_tensor(np.asarray(inst_ids), dtype=torch.uint8).to(dev) if dense and inst_ids is not None else None
         results, pending = [], None
 
         def fetch(item):
@@ -402,6 +412,8 @@ class myEvaluater:
             results.append(dict(pred_RTs=r, pred_scales=s, status=st, tracked=st == 0))
             if icp:
                 results[-1].update(icp_status=icp[0][:, 0].copy(), icp_inliers=icp[0][:, 1].copy(), icp_rmse=icp[1])
+            if len(icp) == 3:                                # a DenseModelRefine's
+                results[-1].update(icp_candidates=icp[0][:, 3].copy(), ray_hits=icp[2])
             if pl:
                 results[-1].update(plane=pl[0][0].copy(), plane_status=pl[1][0, 0].copy(), plane_inliers=pl[1][0, 2].copy())
             if vf:
@@ -410,7 +422,7 @@ class myEvaluater:
             masks = inst_ids if inst_ids is not None and "inst_mask" in frame else None
             with torch.no_grad():
                 pl = ()
-                on_device = support is not None or verify is not None
+                on_device = support is not None or verify is not None or dense
                 if on_device:                                # the frame is uploaded here, once: the crop reads the same tensors
                     depth, inst, camk = lde._depth_frames([frame], camK, dev)
                     if support is not None:
@@ -418,16 +430,26 @@ class myEvaluater:
                         pl = (plane, pinfo)
                     frame = dict(depth=depth) if inst is None else dict(depth=depth, inst_mask=inst)
                 frames = frame if on_device else [frame]
-                pts, ok, _, counts = lde.clouds_from_poses(frames, job_img, rts, scales, ratio, camK, n_pts=n_pts, sampler=sampler,
-                                                           masks=masks, seed=self.seed + k, fps_pool=self.fps_pool, device=dev,
-                                                           return_counts=True)
+                if dense and init_from == "previous":        # no crop: the frame itself is registered
+                    ok = torch.ones(n, dtype=torch.bool, device=dev)
+                    status = torch.zeros(n, dtype=torch.int32, device=dev)
+                else:
+                    pts, ok, _, counts = lde.clouds_from_poses(frames, job_img, rts, scales, ratio, camK, n_pts=n_pts, sampler=sampler,
+                                                               masks=masks, seed=self.seed + k, fps_pool=self.fps_pool, device=dev,
+                                                               return_counts=True)
+                    status = counts[:, 3].contiguous()
                 if init_from == "net":
                     new_rts, new_scales = infer_device(self.net1, torch.nan_to_num(pts, nan=0.0), cat, mean, sym, self.max_batch,
                                                        eval_outputs_only=self.eval_outputs_only)
                 else:
                     new_rts, new_scales = rts, scales
                 icp = ()
-                if refine is not None:
+                if dense:
+                    new_rts, info, rmse, hits = refine(depth, new_rts, camk, job_img, mask=inst.view(torch.uint8) if masks is not None else None,
+                                                       job_mask_val=mask_val if masks is not None else None)
+                    ok = ok & (info[:, 0] == 0)
+                    icp = (info, rmse, hits)
+                elif refine is not None:
                     new_rts, info, rmse = refine(pts, new_rts)      # a failed crop's NaN rows are never inliers: status 1
                     ok = ok & (info[:, 0] == 0)
                     icp = (info, rmse)
@@ -441,7 +463,7 @@ class myEvaluater:
                     vf = (v["counts"], v["score"], v["verified"])
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(dev))
-            item = (rts, scales, counts[:, 3].contiguous(), done, icp, pl, vf)
+            item = (rts, scales, status, done, icp, pl, vf)
             if pending is not None:
                 fetch(pending)
             pending = item

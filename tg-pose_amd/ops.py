@@ -1208,6 +1208,19 @@ class MeshSet(object):
             self._fields[(faces, maxima)] = kw
         return kw
 
+    def bounds(self):
+        """(M,2,3) float32 on the device: each mesh's least and greatest vertex coordinates (ops.mesh_windows frames a mesh by this
+        box).  Made by torch reductions on the device at first use and kept; nothing is read back."""
+        b = getattr(self, "_bounds", None)
+        if b is None:
+            rows, lo = [], 0
+            for nv in self.n_verts:
+                v = self.verts[lo:lo + nv]
+                rows.append(torch.stack([v.amin(0), v.amax(0)]))
+                lo += nv
+            b = self._bounds = torch.stack(rows).contiguous()
+        return b
+
     def area_cdf(self):
         """(sum F) float64 on the device: each mesh's cumulative triangle area over its own faces in tgp_mesh_area_cdf's fixed
         order (chunks of 64 faces; DESIGN.md section 3 "Mesh surface sampling").  Built by one launch on the current stream at
@@ -3181,6 +3194,103 @@ def icp_dense(depth, camk, job_img, rect, rc, window, ref_pose, R, t, s, max_dis
         check(_lib.lib().tgp_icp_dense(ctypes.byref(a), _stream(job_img)), "tgp_icp_dense")
     out = (R_out, t_out, s_out, info, rmse)
     return out + (corr,) if corr_cap else out
+
+
+# ------------------------------------------------------------------------------------------------------------ maps of posed meshes
+MESH_MAPS_MAX_JOBS = _lib.MAPS_MAX_JOBS
+
+
+def _mesh_map_jobs(meshset, camk, job_img, job_mesh, job_pose, who):
+    if not isinstance(meshset, MeshSet):
+        raise TypeError("%s: meshset must be an ops.MeshSet" % who)
+    dev = meshset.verts.device
+    _gpu_args(who, dev, [(camk, "camk", torch.float32), (job_img, "job_img", torch.int32), (job_mesh, "job_mesh", torch.int32),
+                         (job_pose, "job_pose", torch.float32)])
+    J = job_img.numel()
+    if camk.dim() != 2 or camk.shape[1] != 4 or camk.shape[0] < 1 or job_img.dim() != 1 or job_mesh.shape != (J,) or job_pose.shape != (J, 3, 4):
+        raise ValueError("%s: camk (S,4), job_img (J), job_mesh (J), job_pose (J,3,4) are expected" % who)
+    if J > MESH_MAPS_MAX_JOBS:
+        raise ValueError("%s: at most %d jobs" % (who, MESH_MAPS_MAX_JOBS))
+    return dev, J
+
+
+def mesh_maps(meshset, camk, job_img, job_mesh, job_pose, window, h, w, *, near=0.01, normals="face", return_face=False):
+    """The surface of posed meshes as cameras see it, as tsdf_raycast's maps (tgp_mesh_maps, csrc/meshmaps.hip; DESIGN.md section 3
+    "Mesh maps and dense model-based tracking").  Job j rasterises mesh job_mesh[j] of the set at job_pose[j] (3,4) [s R | t] (model ->
+    camera, metres) under the intrinsics camk[job_img[j]] into an h x w grid whose cell (r, c) is the pixel coordinate (u0 + c du, v0 +
+    r dv) of window[j] = (u0, v0, du, dv): render_depth's surface, sampled by the window.  All tensors on the mesh set's GPU: camk (S,4)
+    float32, job_img, job_mesh (J) int32, job_pose (J,3,4), window (J,4) float32.  normals: 'face' (the winning triangle's normal,
+    turned towards the camera) or 'vertex' (meshset.vert_normals interpolated over the triangle and renormalised; not turned).
+    -> dict: z (J,h,w) float32 camera depth in metres (0: a miss), depth (J,h,w) int16-viewed uint16 millimetres, vertex, normal
+    (J,h,w,3) float32 in the MODEL frame (zeros on a miss), count (J) int32 hits, dropped (J) int32 triangles dropped by the near rule
+    and the guard band, status (J) int32: 1 for a job whose frame or mesh index is out of range (all its cells miss); with
+    return_face face (J,h,w) int32 within the mesh, -1 on a miss.  icp_dense(rc=...) and IcpModels.from_raycast take the dict as it
+    stands.  Nothing is read back."""
+    dev, J = _mesh_map_jobs(meshset, camk, job_img, job_mesh, job_pose, "mesh_maps")
+    if not (torch.is_tensor(window) and window.is_cuda and window.dtype == torch.float32 and window.is_contiguous() and window.device == dev
+            and window.shape == (J, 4)):
+        raise ValueError("mesh_maps: window must be a contiguous (J,4) float32 tensor on the mesh set's device")
+    if not (isinstance(h, int) and isinstance(w, int) and 1 <= h <= RAYCAST_MAX_SIDE and 1 <= w <= RAYCAST_MAX_SIDE):
+        raise ValueError("mesh_maps: h and w must be ints in [1, %d]" % RAYCAST_MAX_SIDE)
+    if not (0.0 < float(near) < math.inf):
+        raise ValueError("mesh_maps: near must be positive and finite")
+    if normals not in ("face", "vertex"):
+        raise ValueError("mesh_maps: normals must be 'face' or 'vertex'")
+    vn = None
+    if normals == "vertex":
+        vn = meshset.vert_normals
+        if vn is None:
+            raise ValueError("mesh_maps: normals='vertex' needs meshset.vert_normals (ops.mesh_vertex_normals makes them)")
+        _gpu_args("mesh_maps", dev, [(vn, "meshset.vert_normals", torch.float32)])
+        if vn.shape != meshset.verts.shape:
+            raise ValueError("mesh_maps: meshset.vert_normals must be (sum V,3), one row per vertex")
+    out = {"z": torch.empty(J, h, w, device=dev, dtype=torch.float32), "depth": torch.empty(J, h, w, device=dev, dtype=torch.int16),
+           "vertex": torch.empty(J, h, w, 3, device=dev, dtype=torch.float32), "normal": torch.empty(J, h, w, 3, device=dev, dtype=torch.float32),
+           "count": torch.empty(J, device=dev, dtype=torch.int32), "dropped": torch.empty(J, device=dev, dtype=torch.int32),
+           "status": torch.empty(J, device=dev, dtype=torch.int32)}
+    if return_face:
+        out["face"] = torch.empty(J, h, w, device=dev, dtype=torch.int32)
+    if J == 0:
+        return out
+    mesh = meshset.fields(maxima=True)
+    ws = _workspace(dev, _lib.lib().tgp_mesh_maps_workspace_bytes(J, mesh["max_verts"], mesh["max_faces"]), "tgp_mesh_maps_workspace_bytes")
+    a = _lib.MeshMapsArgs(camk=_p(camk), vnormals=_p(vn), job_img=_p(job_img), job_mesh=_p(job_mesh), job_pose=_p(job_pose),
+                          job_window=_p(window), S=camk.shape[0], J=J, h=h, w=w, near=float(near), z=_p(out["z"]), depth=_p(out["depth"]),
+                          vertex=_p(out["vertex"]), normal=_p(out["normal"]), face=_p(out.get("face")), count=_p(out["count"]),
+                          dropped=_p(out["dropped"]), status=_p(out["status"]), workspace=_p(ws), workspace_bytes=ws.numel(), **mesh)
+    check(_lib.lib().tgp_mesh_maps(ctypes.byref(a), _stream(job_pose)), "tgp_mesh_maps")
+    return out
+
+
+def mesh_windows(meshset, camk, job_img, job_mesh, job_pose, h, w, H, W, pad=1.0):
+    """The map windows that frame each job's mesh: tsdf_windows' rule on the eight corners of the mesh's axis-aligned bounding box
+    (MeshSet.bounds, made once on the device) instead of a cube's: (J,4) float32 (u0, v0, du, dv) on the device, an h x w grid that spans
+    the box of the projected corners grown by ``pad`` pixels and clamped to the frame [0, W-1] x [0, H-1] (du = (u1 - u0) / (w - 1); 1
+    for a single column).  A box with a corner at or behind the camera (z <= 1e-6), or whose projection is not finite, gets four NaN:
+    every cell of it misses.  Indices out of range are clamped here (mesh_maps refuses the job).  Made of torch operations, float32 one
+    operation at a time (tests/meshmaps_ref.py windows); nothing is read back."""
+    dev, J = _mesh_map_jobs(meshset, camk, job_img, job_mesh, job_pose, "mesh_windows")
+    if not all(isinstance(v, int) and v >= 1 for v in (h, w, H, W)):
+        raise ValueError("mesh_windows: h, w, H, W must be ints >= 1")
+    bounds = meshset.bounds()[job_mesh.long().clamp(0, len(meshset) - 1)]            # (J,2,3): the least and the greatest coordinates
+    K = camk[job_img.long().clamp(0, camk.shape[0] - 1)]
+    k = torch.arange(8, device=dev)
+    high = torch.stack([k // 4 % 2, k // 2 % 2, k % 2], 1).bool()                            # (8,3), made on the device
+    p = torch.where(high[None], bounds[:, None, 1], bounds[:, None, 0])                     # (J,8,3)
+    T = job_pose
+    c = [((T[:, None, r, 0] * p[:, :, 0] + T[:, None, r, 1] * p[:, :, 1]) + T[:, None, r, 2] * p[:, :, 2]) + T[:, None, r, 3] for r in range(3)]
+    us = K[:, None, 0] * (c[0] / c[2]) + K[:, None, 2]
+    vs = K[:, None, 1] * (c[1] / c[2]) + K[:, None, 3]
+    good = (c[2] > 1e-6).all(1) & torch.isfinite(us).all(1) & torch.isfinite(vs).all(1)
+    u0 = (us.min(1).values - float(pad)).clamp(0.0, float(W - 1))
+    u1 = (us.max(1).values + float(pad)).clamp(0.0, float(W - 1))
+    v0 = (vs.min(1).values - float(pad)).clamp(0.0, float(H - 1))
+    v1 = (vs.max(1).values + float(pad)).clamp(0.0, float(H - 1))
+    # a tensor divided by a tensor is a correctly rounded division; by a Python number it may become a product with the reciprocal
+    du = (u1 - u0) / torch.full_like(u0, float(w - 1)) if w > 1 else torch.ones_like(u0)
+    dv = (v1 - v0) / torch.full_like(v0, float(h - 1)) if h > 1 else torch.ones_like(v0)
+    win = torch.stack([u0, v0, du, dv], 1)
+    return torch.where(good[:, None], win, torch.full_like(win, float("nan"))).contiguous()
 
 
 # ------------------------------------------------------------------------------------------------------------ the supporting plane

@@ -292,6 +292,70 @@ class DenseRefine(object):
         return torch.where(few[:, None, None], RTs, join_RT(R, t, s)), info, rmse, rc["count"]
 
 
+DENSE_GATED = 5                # DenseModelRefine's status beside 1..4: the solve succeeded and failed the inlier / rmse gate
+
+
+class DenseModelRefine(object):
+    """Frame-to-model registration against MESH models by dense projective ICP (DESIGN.md section 3 "Mesh maps and dense model-based
+    tracking"): each object's mesh is rasterised at its current pose into h x w vertex and normal maps (ops.mesh_windows,
+    ops.mesh_maps), and the frame's depth pixels under each map (ops.dense_rects, every ``stride``-th a side) are registered to it by
+    ONE ops.icp_dense call -- DenseRefine with a mesh where it has a volume: no crop, no sampler, no nearest-neighbour search, and
+    every depth pixel of the object takes part.  meshset: ops.MeshSet in the model's units, posed by RTs = [s R | t] as they stand
+    (pose.Verify's and IcpRefine's convention); job_mesh: one mesh index per object; max_dist: the gate in metres; near, normals:
+    ops.mesh_maps'; kw: ops.icp_dense's keywords (iters, tol_rot, ...).
+    __call__(depth (S,H,W) 16-bit millimetres, RTs (J,4,4) [s R | t], camk (S,4), job_img (J) int32, mask (S,H,W) uint8 with
+    job_mask_val (J) uint8 or neither) -> (RTs (J,4,4), info (J,4) int32 = status, inliers, iterations, candidates, rmse (J,), hits
+    (J,) int32).  A job keeps the pose it came with unless its status is 0: RAYCAST_FEW_HITS for fewer than ``min_hits`` map hits;
+    ops.ICP_STATUS' 1..3 from the solve; DENSE_GATED for a solve that succeeded with fewer inliers than ``min_inlier_frac`` x its
+    candidates (the pixels its map associated at the start pose) or, with ``max_rmse`` (metres), a larger rmse.  Three launches and
+    torch's glue; nothing is read back (it runs under torch.cuda.set_sync_debug_mode("error"))."""
+
+    def __init__(self, meshset, job_mesh, max_dist, h=96, w=128, stride=1, near=0.01, min_hits=64, normals="face", min_inlier_frac=0.5,
+                 max_rmse=None, **kw):
+        self.job_mesh = ops._mesh_jobs(meshset, job_mesh, "DenseModelRefine")
+        if not (isinstance(h, int) and isinstance(w, int) and 1 <= h <= ops.RAYCAST_MAX_SIDE and 1 <= w <= ops.RAYCAST_MAX_SIDE):
+            raise ValueError("DenseModelRefine: h and w must be ints in [1, %d]" % ops.RAYCAST_MAX_SIDE)
+        if not (isinstance(stride, int) and stride >= 1):
+            raise ValueError("DenseModelRefine: stride must be an int >= 1")
+        if not (isinstance(min_hits, int) and min_hits >= 0):
+            raise ValueError("DenseModelRefine: min_hits must be an int >= 0")
+        if normals not in ("face", "vertex") or (normals == "vertex" and meshset.vert_normals is None):
+            raise ValueError("DenseModelRefine: normals must be 'face' or 'vertex', and 'vertex' needs meshset.vert_normals")
+        if not 0.0 <= float(min_inlier_frac) <= 1.0:
+            raise ValueError("DenseModelRefine: min_inlier_frac must be in [0, 1]")
+        if not float(near) > 0.0:
+            raise ValueError("DenseModelRefine: near must be positive")
+        if kw.get("corr_cap"):
+            raise ValueError("DenseModelRefine: corr_cap is ops.icp_dense's")
+        dev = meshset.verts.device
+        self.meshset, self.h, self.w, self.stride, self.near, self.min_hits, self.normals = meshset, h, w, stride, float(near), min_hits, normals
+        self.min_inlier_frac, self.max_rmse = float(min_inlier_frac), None if max_rmse is None else float(max_rmse)
+        self.max_dist = max_dist.to(dev).float().contiguous() if torch.is_tensor(max_dist) else float(max_dist)
+        self.kw = dict(kw)
+
+    def __call__(self, depth, RTs, camk, job_img, mask=None, job_mask_val=None):
+        J = RTs.shape[0]
+        if self.job_mesh.numel() != J:
+            raise ValueError("DenseModelRefine: %d mesh indices for %d poses" % (self.job_mesh.numel(), J))
+        H, W = depth.shape[1:]
+        P = verify_job_pose(RTs)
+        win = ops.mesh_windows(self.meshset, camk, job_img, self.job_mesh, P, self.h, self.w, H, W)
+        maps = ops.mesh_maps(self.meshset, camk, job_img, self.job_mesh, P, win, self.h, self.w, near=self.near, normals=self.normals)
+        rect = ops.dense_rects(win, self.h, self.w, H, W)
+        R, t, s = split_RT(RTs)
+        R, t, s, info, rmse = ops.icp_dense(depth, camk, job_img, rect, maps, win, P, R, t, s, self.max_dist, stride=self.stride, mask=mask,
+                                            job_mask_val=job_mask_val, **self.kw)
+        solved = info[:, 0] == 0
+        passed = info[:, 1].float() >= self.min_inlier_frac * info[:, 3].float()
+        if self.max_rmse is not None:
+            passed = passed & (rmse <= self.max_rmse)
+        few = maps["count"] < self.min_hits
+        status = torch.where(solved & ~passed, torch.full_like(info[:, 0], DENSE_GATED), info[:, 0])
+        status = torch.where(few, torch.full_like(status, RAYCAST_FEW_HITS), status)
+        info = torch.cat([status[:, None], info[:, 1:]], 1)
+        return torch.where((status == 0)[:, None, None], join_RT(R, t, s), RTs), info, rmse, maps["count"]
+
+
 def cloud_anchors(clouds, counts=None):
     """The mean of each cloud's finite rows (of the first counts[j] rows): float64 sums on the device, rounded once -> (J,3) float32;
     a cloud without a finite row gives 0."""
